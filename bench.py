@@ -4,16 +4,18 @@ max_words=48 x max_frames=48, BERT-base text encoder + 6-layer visual encoder (B
 One step = exactly the reference's loop body (main_task_retrieval.py:333-353):
     loss = model(...); loss.backward(); float(loss); clip_grad_norm_(params, 1.0); optimizer.step(); zero_grad()
 dropout 0.1 active, bf16 MFMA operands / fp32 accumulate + fp32 master weights, BertAdam state in fp32.
-`value` is measured with the batch resident in HBM (the bench contract); the PCIe-inclusive rate with the batch handed
-over as pageable host tensors every step (what the reference's loaders produce) is measured in the same run and printed
-as `pcie_inclusive`.
+`value` is measured with the batch resident in HBM (the bench contract).
 
-    python bench.py                         one GPU
+    python bench.py                         one GPU: set-up, pre-heat, W warm-up + K timed steps, the headline line
+    python bench.py --full                  ... and every side measurement below, `other_configs`, `parity`, `cpu_baseline`
+    python bench.py --dump-outputs DIR      ... and what the last timed step computed, as DIR/*.npy (dump_outputs)
     python bench.py --gpus N                N ranks on one node: re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N      (the driver's form) is used as is
 
 One process per GPU, per-GPU batch fixed (weak scaling), gradient exchange over RCCL overlapped with the backward.
-Prints ONE JSON line (rank 0) with
+Prints ONE JSON line (rank 0); with --full it also carries
+  pcie_inclusive  the same step with the batch handed over as pageable host tensors every step (what the reference's loaders
+                produce)
   roofline      the kernel family that owns the step (every gemm_kernel / gemm_pair_kernel / gemm_group_kernel launch of one step, replayed
                 alone as a hipGraph and timed with HIP events on the launch stream): algorithmic bytes and flops taken from
                 the launch descriptors, fractions of the 8 TB/s HBM and 2.5 PFLOP/s bf16 MFMA peaks; plus `adam` (the fused
@@ -65,6 +67,11 @@ def get_args():
     ap.add_argument("--grad-exchange", default=None, choices=["fp32", "bf16"],
                     help="N > 1: dtype the gradient buckets cross the wire in (default: UNIVL_GRAD_EXCHANGE or fp32, the reference's DDP "
                          "semantics; bf16 halves the bytes -- every exchanged element rounded to 8 mantissa bits, gated in tests/test_ddp_gpu.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: PCIe-inclusive rate, roofline, the exchange timing, cfg3's share "
+                         "at N > 1, `other_configs`, `parity`, `like_for_like` and `cpu_baseline` (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the benchmarked step's outputs (loss, similarity logits, pooled embeddings) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the roofline / PCIe-inclusive side measurements")
     ap.add_argument("--no-others", action="store_true",
@@ -77,7 +84,7 @@ def get_args():
                          "decoding (univl_amd.decode.CaptionBeamSearch, main_task_caption.py:434-522); prints one JSON line")
     ap.add_argument("--eval-items", type=int, default=0, help="--measure eval_*: number of (text, video) items (default 1024 joint / 128 align)")
     ap.add_argument("--cfg3-row", action="store_true",
-                    help="also time BASELINE cfg3's share of the global batch of 128 (128 / world pairs per GPU) in THIS run (default at N > 1)")
+                    help="also time BASELINE cfg3's share of the global batch of 128 (128 / world pairs per GPU) in THIS run (default at N > 1 with --full)")
     ap.add_argument("--watchdog-s", type=float, default=240.0,
                     help="N > 1 / --force-dp: bound (s) on every phase that can hang on a collective (process-group init, communicator "
                          "construction + captured self-test, first captured step, each timed region); on expiry every rank prints a JSON "
@@ -93,7 +100,10 @@ def get_args():
     ap.add_argument("--preheat-max-s", type=float, default=6.0)
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--profile-tag", default="")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.measure:
+        ap.error("--dump-outputs writes the training step's outputs; --measure times another caller")
+    return args
 
 
 # per --kind: (max_words, max_frames, task-config overrides, algorithmic fwd+bwd GFLOP per row -- SURVEY section 8d / BASELINE.md section 2,
@@ -236,7 +246,7 @@ def other_configs(args):
         if left < 20:
             rows.append(dict(name=name, skipped="others budget spent"))
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--steps", str(args.steps), "--warmup", str(args.warmup),
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--full", "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--dtype", args.dtype, "--dropout", str(args.dropout)] + extra       # later arguments win (argparse)
         env = dict(os.environ)
         env.update(env_extra)
@@ -368,6 +378,37 @@ def parity_leg(batch, kind, dtype):
     except Exception as ex:      # noqa: BLE001
         out["error"] = "%s: %s | %s" % (type(ex).__name__, ex, (r.stdout or r.stderr)[-200:])
     return out
+
+
+def dump_outputs(out_dir, model_args, dev, call_args, inputs, kind, rows, loss):
+    """--dump-outputs: the benchmarked step's outputs as DIR/<name>.npy.  loss_last_step.npy is the loss the last timed step returned.
+    The arrays are those of the same step (same plans, same inputs, same dropout draws) run once on a fresh model built from the
+    same seed: the loss, the similarity logits and the pooled, normalised text / video embeddings behind them (univl_amd/steps.py:
+    JointSim, PoolerSim).  They are not taken after the timed steps because that state is not reproducible: the default mode sums
+    with fp32 atomics, Adam turns the rounding noise of gradients that are zero in exact arithmetic (the key biases) into updates
+    of either sign, and over hundreds of steps on one batch the trajectories of two runs of one build drift apart by far more than
+    rounding (the similarity logits by 10 % after 50 timed steps, 80 % after 2000)."""
+    import numpy as np
+    from univl_amd import UniVL
+    torch.manual_seed(0)                                            # main()'s seed: the same initial weights
+    m = UniVL.from_pretrained(*model_args[0], task_config=model_args[1])
+    m.to(dev).train()
+    a, kw = call_args(inputs)
+    first = float(m(*a, **kw))
+    torch.cuda.synchronize()
+    st = next(v for v in m._steps.values() if getattr(v, "kind", None) == kind and getattr(v, "B", None) == rows and v.cx.training)
+    out = dict(loss_last_step=np.array([loss], dtype=np.float64), loss=np.array([first], dtype=np.float64))
+    if st.joint is not None:
+        out.update(similarity=st.joint.sim[:rows, :rows], text_embedding=st.joint.tn[:rows], video_embedding=st.joint.vn[:rows])
+    elif st.pooler is not None:
+        out.update(similarity=st.pooler.sim.view(rows, rows))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        if isinstance(arr, torch.Tensor):
+            arr = arr.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    del m, st
+    torch.cuda.empty_cache()
 
 
 class Watchdog:
@@ -802,9 +843,12 @@ def main():
     elapsed, last = timed(main_src, args.steps, args.warmup)
     ms_per_step = elapsed / args.steps * 1e3
     pairs_per_s = args.batch * world / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (("bert-base-uncased", "visual-base", "cross-base", "decoder-base"), tc), dev, call_args, inputs,
+                     args.kind, args.batch, last)
 
     pcie = None
-    if not args.no_extras and not args.host_inputs and not args.child:
+    if args.full and not args.no_extras and not args.host_inputs and not args.child:
         k = max(10, min(args.steps, 50))
         el2, _ = timed(host_inputs, k, 3)
         pcie = dict(value=round(args.batch * world / (el2 / k), 2), ms_per_step=round(el2 / k * 1e3, 4), steps=k,
@@ -902,7 +946,7 @@ def main():
 
     roofline = None
     try:
-        roofline = None if args.no_extras else side_measurements()
+        roofline = side_measurements() if args.full and not args.no_extras else None
     except Exception as ex:      # noqa: BLE001 -- a failing side measurement must never cost the headline line
         print("[bench] rank %d: roofline side measurements failed (%s: %s)" % (rank, type(ex).__name__, ex), file=sys.stderr)
         roofline = dict(error="%s: %s" % (type(ex).__name__, ex))
@@ -920,7 +964,7 @@ def main():
                                 backend="loopback" if red.loopback else "rccl", wire_dtype="bf16" if red.bf16 else "fp32",
                                 graphs_per_iteration=(2 if (gstep is not None and gstep._g_rest is not None) else 1) if gstep is not None and gstep.mode == "whole" else None,
                                 captured_in_step_graph=bool(red.capturable and gstep is not None and gstep.mode == "whole"))
-                if red.capturable:
+                if red.capturable and args.full:
                     # Where the step's time goes once gradients cross xGMI: a few EAGER iterations (events cannot be timed inside a
                     # graph) with HIP events around every collective on the communication stream and around the join that precedes the
                     # clip.  exposed_ms = what the compute stream waits for after its last backward kernel; algbw_gbs = exchanged
@@ -964,7 +1008,7 @@ def main():
     # the 4-pair headline is exchange-bound by construction (521 MB of gradients against a 2.2 ms step), cfg3 is the configuration the
     # reference trains at.  `--cfg3-row` forces it on one rank (with --force-dp: the N > 1 code path on world-size-1 RCCL).
     cfg3 = None
-    if (world > 1 or args.cfg3_row) and args.kind == "joint" and 128 // world != args.batch and 128 % world == 0:
+    if ((world > 1 and args.full) or args.cfg3_row) and args.kind == "joint" and 128 // world != args.batch and 128 % world == 0:
         b3 = 128 // world
         try:
             if gstep is not None:
@@ -1026,17 +1070,17 @@ def main():
         dist.destroy_process_group()
         if rank == 0 and os.environ.get("UNIVL_BENCH_WORKER"):
             return
-    if rank == 0 and world == 1 and not args.child and not args.no_others and args.kind == "joint" and not args.force_dp:
+    if args.full and rank == 0 and world == 1 and not args.child and not args.no_others and args.kind == "joint" and not args.force_dp:
         try:
             out["other_configs"] = out.get("other_configs", []) + other_configs(args)
         except Exception as ex:      # noqa: BLE001 -- never at the price of the headline line
             out["other_configs"] = out.get("other_configs", []) + [dict(error="%s: %s" % (type(ex).__name__, ex))]
-    if rank == 0 and world == 1 and not args.child and not args.no_extras and not args.force_dp:
+    if args.full and rank == 0 and world == 1 and not args.child and not args.no_extras and not args.force_dp:
         try:
             out["parity"] = parity_leg(args.batch, args.kind, args.dtype)
         except Exception as ex:      # noqa: BLE001
             out["parity"] = dict(error="%s: %s" % (type(ex).__name__, ex))
-    if rank == 0 and world == 1 and not args.child:
+    if args.full and rank == 0 and world == 1 and not args.child:
         # NOT measured by this run: the builder's alternating comparison of the previous round's HEAD with this one on ONE box (box-to-box
         # variance is as large as a round's gain: VERDICT r5 weak 7), carried in the line so that the record holds it
         try:
@@ -1052,7 +1096,7 @@ def main():
                 change={c: round(sum(d["r06"]) / len(d["r06"]) / (sum(d["r05"]) / len(d["r05"])) - 1.0, 4) for c, d in lf.items() if "r05" in d and "r06" in d})
         except Exception:   # noqa: BLE001
             pass
-    if rank == 0 and world == 1 and not args.child and not args.no_cpu_baseline and args.kind == "joint":
+    if args.full and rank == 0 and world == 1 and not args.child and not args.no_cpu_baseline and args.kind == "joint":
         # after every GPU measurement (round 3 ran it first: ~25 s of idle GPU in front of the timed steps)
         try:
             out["cpu_baseline"] = cpu_baseline(args.batch)

@@ -351,6 +351,58 @@ def test_bench_refuses_more_gpus_than_visible():
     assert "--gpus 2 requested but only" in r.stderr
 
 
+def test_bench_dump_outputs_writes_the_benchmarked_steps_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the last timed step's loss, and the loss and similarity head's outputs (the [rows, rows] logits,
+    the pooled text / video embeddings) of the benchmarked step run once on a fresh model built from main()'s seed, as
+    DIR/<name>.npy in float32 / float64; nothing of a step with another batch."""
+    import sys
+    import types
+    import numpy as np
+    import univl_amd
+    sys.path.insert(0, ROOT)
+    import bench
+    B, ld, H = 4, 8, 16
+    seen = {}
+
+    def step(rows, fill):
+        joint = types.SimpleNamespace(sim=torch.full((ld, ld), fill), tn=torch.full((rows, H), fill + 1), vn=torch.full((rows, H), fill + 2))
+        return types.SimpleNamespace(kind="joint", B=rows, cx=types.SimpleNamespace(training=True), joint=joint, pooler=None)
+
+    class Fake:
+        _steps = {("a",): step(16, 9.0), ("b",): step(B, 1.0)}
+
+        @classmethod
+        def from_pretrained(cls, *names, task_config):
+            seen["init"] = float(torch.rand(1))
+            return cls()
+
+        def to(self, dev):
+            return self
+
+        def train(self):
+            return self
+
+        def __call__(self, *a, **kw):
+            seen["args"] = (a, kw)
+            return torch.tensor(0.5)
+    monkeypatch.setattr(univl_amd, "UniVL", Fake)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(torch.cuda, "empty_cache", lambda *a: None)
+    torch.manual_seed(0)
+    want_init = float(torch.rand(1))
+    torch.manual_seed(123)
+    inputs = dict(x=torch.ones(2))
+    bench.dump_outputs(str(tmp_path), (("bert-base-uncased",), None), "cpu", lambda src: ((src["x"],), {}), inputs, "joint", B, 0.25)
+    assert seen["init"] == want_init and seen["args"][0][0] is inputs["x"]          # main()'s seed, the benchmark's inputs
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["loss", "loss_last_step", "similarity", "text_embedding", "video_embedding"]
+    assert got["loss_last_step"].dtype == np.float64 and got["loss_last_step"].tolist() == [0.25] and got["loss"].tolist() == [0.5]
+    assert got["similarity"].shape == (B, B) and got["text_embedding"].shape == got["video_embedding"].shape == (B, H)
+    for k in ("similarity", "text_embedding", "video_embedding"):
+        assert got[k].dtype == np.float32
+    assert (got["similarity"] == 1.0).all() and (got["video_embedding"] == 3.0).all()
+
+
 def test_word_table_chunks_start_on_row_boundaries_and_plan_ops_are_capturable():
     """Host logic of round 3: (1) the optimizer's chunk table cuts the word-embedding table into whole rows (UnivlAdam.row_flags
     tests rows, so a chunk must not straddle one), covers it exactly once, and leaves every other tensor on 8192-element chunks;
