@@ -311,10 +311,13 @@ def _reference_decode_functions():
     return ns, Beam
 
 
-def generate_beam(name="caption_small", n_inst=3, n_bm=5, max_len=5, bos=101):
+def generate_beam(name="caption_small", n_inst=3, n_bm=5, max_len=5, bos=101, out_name=None, trace=False):
     """Runs the reference's caption decoding loop (main_task_caption.py:498-522) with the reference model on procedural
     weights and stores hypotheses / scores for two EOS settings: unreachable, and the token instance 0's top beam emits at
-    its second step (so one instance stops early)."""
+    its second step (so one instance stops early).  trace=True also stores, for every step and instance of both runs, the
+    n_bm (parent, token, score) triples Beam.advance kept and the (n_bm + 1)-th best candidate score."""
+    import time
+    t_start = time.time()
     cfg, rows, dseed = case_config(name)
     model = H.build_reference_model(_task_ns(cfg), vocab_size=cfg.vocab_size, zero_dropout=True)
     load_procedural_into_reference(model, cfg, seed=0)
@@ -339,7 +342,7 @@ def generate_beam(name="caption_small", n_inst=3, n_bm=5, max_len=5, bos=101):
             tup = (seq.repeat(1, n_bm, 1).view(n * n_bm, len_s, d_h), vis.repeat(1, n_bm, 1).view(n * n_bm, len_v, v_h),
                    input_ids.repeat(1, n_bm).view(n * n_bm, len_s), input_mask.repeat(1, n_bm).view(n * n_bm, len_s),
                    video_mask.repeat(1, n_bm).view(n * n_bm, len_v))
-            beams = [Beam(n_bm, device=dev, tokenizer=_Tok(eos)) for _ in range(n)]
+            beams = [(TracedBeam if trace else Beam)(n_bm, device=dev, tokenizer=_Tok(eos)) for _ in range(n)]
             active = list(range(n))
             pos = ns["get_inst_idx_to_tensor_position_map"](active)
             for len_dec_seq in range(1, steps + 1):
@@ -348,18 +351,130 @@ def generate_beam(name="caption_small", n_inst=3, n_bm=5, max_len=5, bos=101):
                     break
                 tup, pos = ns["collate_active_info"](tup, pos, active, n_bm, dev)
             hyp, scores = ns["collect_hypothesis_and_scores"](beams, 1)
-        return [h[0] for h in hyp], [float(s[0]) for s in scores]
+        return [h[0] for h in hyp], [float(s[0]) for s in scores], beams
+
+    class TracedBeam(Beam):
+        """Beam.advance unchanged; records what it keeps and the best candidate it drops."""
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            self.trace = []
+
+        def advance(self, word_prob, word_length=None):
+            beam_lk = word_prob + self.scores.unsqueeze(1).expand_as(word_prob) if self.prev_ks else word_prob[0]
+            best, best_id = beam_lk.reshape(-1).topk(self.size + 1, 0, True, True)
+            done = super().advance(word_prob, word_length)
+            assert torch.equal(self.scores, best[:self.size])
+            self.trace.append((self.prev_ks[-1].clone(), self.next_ys[-1].clone(), self.scores.clone(), float(best[self.size])))
+            return done
+
+    def traces(beams):
+        """[max_len, n, n_bm] parents / tokens / scores and [max_len, n] (n_bm + 1)-th scores; -1 / NaN after an instance stopped."""
+        par = np.full((max_len, n_inst, n_bm), -1, dtype=np.int64)
+        tok = np.full((max_len, n_inst, n_bm), -1, dtype=np.int64)
+        sco = np.full((max_len, n_inst, n_bm), np.nan, dtype=np.float32)
+        nxt = np.full((max_len, n_inst), np.nan, dtype=np.float32)
+        for i, b in enumerate(beams):
+            for t, (pk, ny, scs, s6) in enumerate(b.trace):
+                par[t, i], tok[t, i], sco[t, i], nxt[t, i] = pk.numpy(), ny.numpy(), scs.numpy(), s6
+        return par, tok, sco, nxt
 
     out = {}
-    hyp, sc = decode(-1, max_len)
-    short, _ = decode(-1, 2)
+    hyp, sc, beams1 = decode(-1, max_len)
+    short, _, _ = decode(-1, 2)
     eos = short[0][1]
-    hyp2, sc2 = decode(eos, max_len)
+    hyp2, sc2, beams2 = decode(eos, max_len)
     pad = lambda hs: np.array([h + [-1] * (max_len - len(h)) for h in hs], dtype=np.int64)
     out.update(n_inst=n_inst, n_bm=n_bm, max_len=max_len, bos=bos, eos2=eos, hyp=pad(hyp), scores=np.array(sc),
                hyp2=pad(hyp2), scores2=np.array(sc2), data_seed=dseed + 5)
-    np.savez(os.path.join(GOLDEN_DIR, "beam_" + name + ".npz"), **out)
-    print("[golden] beam_%s.npz: hyp %s | eos=%d -> lengths %s" % (name, hyp, eos, [len(h) for h in hyp2]))
+    if trace:
+        for sfx, bms in (("", beams1), ("2", beams2)):
+            par, tok, sco, nxt = traces(bms)
+            out.update({"parents" + sfx: par, "tokens" + sfx: tok, "step_scores" + sfx: sco, "next_score" + sfx: nxt})
+        out["config_json"] = np.array(json.dumps(cfg.to_dict()))
+    path = os.path.join(GOLDEN_DIR, (out_name or "beam_" + name) + ".npz")
+    if trace:
+        savez_reproducible(path, **out)
+    else:
+        np.savez(path, **out)
+    print("[golden] %s: hyp %s | eos=%d -> lengths %s | %.1f s" % (os.path.basename(path), hyp, eos, [len(h) for h in hyp2],
+                                                                  time.time() - t_start))
+
+
+# ------------------------------------------------------------------------------------------ goldens at the benchmark's sizes
+# bench.py --full times retrieval evaluation and beam decoding at full depth (bench.task_config / measure_caller); these fixtures
+# hold the reference's own results at those shapes, on ragged synthetic inputs.
+# name -> (CASES entry whose config is used, item counts of the eval batches, data seed of batch 0 (batch b uses seed + b))
+EVAL_CASES = {
+    # FT-Joint: 136 items in blocks of 64, 64 and 8 (a partial last block; three text blocks written into one matrix)
+    "eval_joint_full": ("joint_full", [64, 64, 8], 5101),
+    # FT-Align: 70 items in blocks of 64 and 6: 5-row cross-encoder chunks with 4-row (64 = 12 x 5 + 4) and 1-row tail chunks,
+    # and a 6-wide video block
+    "eval_align_full": ("align_full", [64, 6], 5201),
+}
+
+
+def _reference_function(script, fname, extra_ns):
+    """One top-level function of a reference script that cannot be imported, taken out of its syntax tree and executed here
+    (in this container only; nothing of it is stored in the repository)."""
+    import ast
+    tree = ast.parse(open(os.path.join(H.REFERENCE_ROOT, script)).read())
+    body = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == fname]
+    assert len(body) == 1, fname
+    ns = dict(extra_ns)
+    exec(compile(ast.Module(body=body, type_ignores=[]), "%s[%s]" % (script, fname), "exec"), ns)
+    return ns[fname]
+
+
+def savez_reproducible(path, **arrays):
+    """np.savez_compressed with a fixed member timestamp, so that a regenerated fixture is byte-identical."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for k, a in arrays.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def eval_batches(cfg, sizes, seed):
+    return [O.synthetic_batch(cfg, b, seed=seed + i) for i, b in enumerate(sizes)]
+
+
+def generate_eval(name):
+    """The reference's retrieval evaluation (main_task_retrieval.py:_run_on_single_gpu + eval_epoch's feature loop,
+    metrics.compute_metrics) over several 64-item blocks with a partial last one."""
+    import importlib
+    import time
+    base, sizes, seed = EVAL_CASES[name]
+    cfg, _, _ = case_config(base)
+    t0 = time.time()
+    model = H.build_reference_model(_task_ns(cfg), vocab_size=cfg.vocab_size, zero_dropout=True)
+    load_procedural_into_reference(model, cfg, seed=0)
+    model.eval()
+    run_on_single_gpu = _reference_function("main_task_retrieval.py", "_run_on_single_gpu", {"np": np, "torch": torch})
+    ref_metrics = importlib.import_module("metrics")          # the reference's metrics.py (on sys.path after _install_stubs)
+    batch_list, seqs, viss = [], [], []
+    with torch.no_grad():
+        for bt in eval_batches(cfg, sizes, seed):
+            seq, vis = model.get_sequence_visual_output(bt["input_ids"], bt["token_type_ids"], bt["attention_mask"], bt["video"],
+                                                        bt["video_mask"])
+            seqs.append(seq)
+            viss.append(vis)
+            batch_list.append((bt["input_ids"], bt["attention_mask"], bt["token_type_ids"], bt["video"], bt["video_mask"],
+                               None, None, None, None))
+        sim = run_on_single_gpu(model, batch_list, batch_list, seqs, viss)
+    sim = np.concatenate(tuple(sim), axis=0).astype(np.float32)
+    m = ref_metrics.compute_metrics(sim)
+    # per row: distance of the diagonal score to the nearest off-diagonal one (how far the row's rank is from a tie)
+    gap = np.where(np.eye(sim.shape[0], dtype=bool), np.inf, np.abs(sim - np.diag(sim)[:, None])).min(axis=1)
+    out = dict(sim_matrix=sim, metrics=np.array([m["R1"], m["R5"], m["R10"], m["MR"]], dtype=np.float64),
+               diag_gap=gap.astype(np.float32), sizes=np.array(sizes, dtype=np.int64),
+               data_seed=np.array(seed), config_json=np.array(json.dumps(cfg.to_dict())))
+    path = os.path.join(GOLDEN_DIR, name + ".npz")
+    savez_reproducible(path, **out)
+    print("[golden] %s: %d x %d, R1=%.4f R5=%.4f R10=%.4f MR=%s, min diag gap %.3e, %.1f s -> %s (%.0f KiB)" % (
+        name, sim.shape[0], sim.shape[1], m["R1"], m["R5"], m["R10"], m["MR"], float(gap.min()),
+        time.time() - t0, path, os.path.getsize(path) / 1024))
 
 
 def generate_metrics():
@@ -384,12 +499,18 @@ def generate_metrics():
 if __name__ == "__main__":
     assert H.reference_available(), "reference not mounted; golden vectors can only be made in the build container"
     torch.set_num_threads(os.cpu_count())
-    which = sys.argv[1:] or list(CASES) + ["beam", "metrics"] + [c + "_cot" for c in COT_CASES]
+    which = sys.argv[1:] or (list(CASES) + ["beam", "metrics"] + [c + "_cot" for c in COT_CASES] + list(EVAL_CASES)
+                             + ["beam_caption_full"])
     for nm in which:
         if nm.endswith("_cot"):
             generate_cotangent(nm[:-4])
         elif nm == "beam":
             generate_beam()
+        elif nm == "beam_caption_full":
+            # bench.py --measure decode: 16 instances x 5 beams, 32 positions, caption_full's 128 x 96 config
+            generate_beam("caption_full", n_inst=16, n_bm=5, max_len=32, out_name=nm, trace=True)
+        elif nm in EVAL_CASES:
+            generate_eval(nm)
         elif nm == "metrics":
             generate_metrics()
         else:

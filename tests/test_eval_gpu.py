@@ -104,3 +104,61 @@ def test_compute_metrics_matches_reference_golden(golden_dir):
     for n in (7, 60, 333):
         m = M.compute_metrics(torch.as_tensor(g["x%d" % n]).to(DEV))
         assert [m["R1"], m["R5"], m["R10"], float(m["MR"])] == list(g["m%d" % n])
+
+
+# bf16 similarity gates at the benchmark's sizes, error / max(1, max|ref|), set to ~1.3 x the value measured on the MI355X (never
+# looser than GATES[bf16]["sim"] = 1e-2): FT-Joint 8.34e-4 (fp32: 2.3e-7), FT-Align 3.81e-3 (fp32: 1.2e-6)
+EVAL_BF16_SIM = {"eval_joint_full": 1.1e-3, "eval_align_full": 5e-3}
+
+
+def _tie_aware_rank_bounds(ref, d):
+    """Per row: the lowest and highest 0-based rank of the diagonal that a matrix within d of `ref` can give it."""
+    diag = np.diag(ref)[:, None]
+    return (ref > diag + d).sum(axis=1), (ref >= diag - d).sum(axis=1) - 1
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name", ["eval_joint_full", "eval_align_full"])
+def test_eval_retrieval_matches_reference_at_bench_size(golden_dir, name, dtype):
+    """eval_retrieval at full depth and 48 x 48 in 64-item blocks (bench.py --measure eval_joint / eval_align) against the reference's
+    _run_on_single_gpu + metrics.compute_metrics (oracle/make_golden.py::generate_eval): several text blocks written into one matrix,
+    a partial last block, FT-Align's 5-row cross-encoder chunks with 4- and 1-row tails."""
+    import json
+    import os
+    from make_golden import EVAL_CASES, eval_batches
+    from test_model_gpu import GATES, _record
+    g = np.load(os.path.join(golden_dir, name + ".npz"))
+    base, sizes, seed = EVAL_CASES[name]
+    cfg, _, _ = case_config(base)
+    assert json.loads(str(g["config_json"])) == cfg.to_dict()
+    model, P = build(cfg, dtype)
+    model.eval()
+    batches = [(b["input_ids"], b["attention_mask"], b["token_type_ids"], b["video"], b["video_mask"])
+               for b in eval_batches(cfg, sizes, seed)]
+    metrics, sim = eval_retrieval(model, batches)
+    ref = g["sim_matrix"].astype(np.float64)
+    got = sim.cpu().double().numpy()
+    assert got.shape == ref.shape
+    scale = max(1.0, float(np.abs(ref).max()))
+    err = float(np.abs(got - ref).max()) / scale
+    gate = 1e-3 if dtype == torch.float32 else EVAL_BF16_SIM[name]
+    assert gate <= GATES[dtype]["sim"]
+    _record(name, dtype, sim=err)
+    print("[eval %s %s] sim err / max(1, max|ref|) = %.3e (gate %.1e)" % (name, dtype, err, gate))
+    assert err <= gate, (err, gate)
+    # ranks, tie-aware: every row's rank in the device matrix must be one the reference matrix allows within d
+    d = gate * scale
+    lo, hi = _tie_aware_rank_bounds(ref, d)
+    diag = np.diag(got)[:, None]
+    r_first, r_last = (got > diag).sum(axis=1), (got >= diag).sum(axis=1) - 1
+    bad = np.where((r_first < lo) | (r_last > hi))[0]
+    assert bad.size == 0, [(int(i), int(r_first[i]), int(lo[i]), int(hi[i])) for i in bad[:8]]
+    # the metrics follow from those ranks (metrics.py's semantics on the device matrix) ...
+    assert metrics == O.compute_metrics(got.astype(np.float32))
+    if not (r_first != r_last).any():
+        n = len(r_first)
+        assert [metrics["R1"], metrics["R5"], metrics["R10"]] == [float(np.sum(r_first < k)) / n for k in (1, 5, 10)]
+        assert float(metrics["MR"]) == float(np.median(r_first) + 1)
+    # ... and in fp32 they are the reference's own numbers unless a row's diagonal is within d of another score
+    if dtype == torch.float32 and float(g["diag_gap"].min()) > d:
+        assert [metrics["R1"], metrics["R5"], metrics["R10"], float(metrics["MR"])] == list(g["metrics"])

@@ -170,3 +170,83 @@ def test_oracle_matches_reference_cotangent_golden(golden_dir, name):
             rs = g["grad_samples_" + kind][i]
             gs = sample_exact(P[n].grad, 256)
             assert float(np.linalg.norm(gs - rs[:gs.size])) <= 5e-4 * float(np.linalg.norm(rs)) + 1e-6 * gmax, (kind, n)
+
+
+# ------------------------------------------------------------------------------------------ goldens at the benchmark's sizes
+_BENCH_KIND = {"eval_joint_full": "joint", "eval_align_full": "align", "beam_caption_full": "caption"}
+
+
+@pytest.mark.parametrize("name", list(_BENCH_KIND))
+def test_bench_size_golden_config_matches_bench(golden_dir, name):
+    """The golden's W, F, depth and branch are those bench.task_config times for the matching --measure kind."""
+    import argparse
+    import bench
+    g = _load(golden_dir, name)
+    cfg = json.loads(str(g["config_json"]))
+    tc = bench.task_config(argparse.Namespace(kind=_BENCH_KIND[name], batch=4, dropout=0.0, dtype="bf16"), 1)
+    for k in ("max_words", "max_frames", "text_num_hidden_layers", "visual_num_hidden_layers", "cross_num_hidden_layers",
+              "decoder_num_hidden_layers", "train_sim_after_cross", "stage_two", "task_type"):
+        assert cfg[k] == getattr(tc, k), (k, cfg[k], getattr(tc, k))
+
+
+@pytest.mark.parametrize("name,k", [("eval_joint_full", 8), ("eval_align_full", 6)])
+def test_oracle_matches_reference_eval_golden(golden_dir, name, k):
+    """Texts 0..k-1 x videos 0..k-1 of the reference's evaluation matrix (make_golden.generate_eval), from rows of the golden's
+    own first batch."""
+    from make_golden import EVAL_CASES, eval_batches
+    g = _load(golden_dir, name)
+    base, sizes, seed = EVAL_CASES[name]
+    cfg, _, _ = case_config(base)
+    assert json.loads(str(g["config_json"])) == cfg.to_dict()
+    assert list(g["sizes"]) == sizes and int(g["data_seed"]) == seed and g["sim_matrix"].shape == (sum(sizes), sum(sizes))
+    b = {key: t[:k] for key, t in eval_batches(cfg, sizes[:1], seed)[0].items()}
+    P = O.procedural_params(cfg, 0)
+    with torch.no_grad():
+        seq, vis = O.get_sequence_visual_output(P, cfg, b["input_ids"], b["token_type_ids"], b["attention_mask"], b["video"],
+                                                b["video_mask"], training=False)
+        v = lambda t: t.view(-1, t.shape[-1])
+        sim = O.similarity_logits(seq, vis, v(b["attention_mask"]), v(b["video_mask"]), P, cfg, False).numpy()
+    ref = g["sim_matrix"][:k, :k]
+    assert float(np.abs(sim - ref).max()) <= 1e-5 * max(1.0, float(np.abs(ref).max())), float(np.abs(sim - ref).max())
+    # the stored metrics and diagonal gaps are those of the stored matrix
+    assert [float(x) for x in g["metrics"]] == [float(x) for x in O.compute_metrics(g["sim_matrix"]).values()]
+    s = g["sim_matrix"]
+    gap = np.where(np.eye(len(s), dtype=bool), np.inf, np.abs(s - np.diag(s)[:, None])).min(axis=1)
+    np.testing.assert_array_equal(gap.astype(np.float32), g["diag_gap"])
+
+
+def _walk_back(parents, tokens, t, i, k=0):
+    """Hypothesis of beam k of instance i after step t, walked back through the recorded back-pointers (beam.py:108-116)."""
+    hyp = []
+    for j in range(t, -1, -1):
+        hyp.append(int(tokens[j, i, k]))
+        k = int(parents[j, i, k])
+    return hyp[::-1]
+
+
+def test_oracle_beam_search_matches_reference_full_golden(golden_dir):
+    """oracle.beam_search_caption on instances 0-1 of the golden's own 16-instance batch, 8 positions, against the first 8 steps the
+    reference's decode loop recorded (beam search is independent per instance).  Both EOS settings."""
+    g = _load(golden_dir, "beam_caption_full")
+    cfg, _, _ = case_config("caption_full")
+    assert json.loads(str(g["config_json"])) == cfg.to_dict()
+    n, nb, T, bos, eos = int(g["n_inst"]), int(g["n_bm"]), int(g["max_len"]), int(g["bos"]), int(g["eos2"])
+    assert (n, nb, T) == (16, 5, 32)
+    m, steps = 2, 8
+    P = O.procedural_params(cfg, 0)
+    b = {key: t[:m] for key, t in O.synthetic_batch(cfg, n, seed=int(g["data_seed"])).items()}
+    with torch.no_grad():
+        so, vo = O.get_sequence_visual_output(P, cfg, b["input_ids"], b["token_type_ids"], b["attention_mask"], b["video"],
+                                              b["video_mask"], training=False)
+        am, vm = b["attention_mask"].view(m, -1), b["video_mask"].view(m, -1)
+        hyp, sc = O.beam_search_caption(P, cfg, so, vo, am, vm, nb, steps, bos, -1)
+        hyp2, sc2 = O.beam_search_caption(P, cfg, so, vo, am, vm, nb, steps, bos, eos)
+    assert hyp == [_walk_back(g["parents"], g["tokens"], steps - 1, i) for i in range(m)]
+    np.testing.assert_allclose(sc, g["step_scores"][steps - 1, :m, 0], rtol=0, atol=2e-4)
+    # EOS run: instance 0 stops at its second step (the golden's full-length hypothesis says so too)
+    assert hyp2[0] == _golden_hyps(g["hyp2"])[0] and len(hyp2[0]) == 2
+    assert hyp2[1] == _walk_back(g["parents2"], g["tokens2"], steps - 1, 1)
+    np.testing.assert_allclose(sc2, [g["scores2"][0], g["step_scores2"][steps - 1, 1, 0]], rtol=0, atol=2e-4)
+    # the traces are consistent with the stored hypotheses of the full runs
+    assert _golden_hyps(g["hyp"]) == [_walk_back(g["parents"], g["tokens"], T - 1, i) for i in range(n)]
+    np.testing.assert_allclose(g["scores"], g["step_scores"][T - 1, :, 0], rtol=0, atol=0)
