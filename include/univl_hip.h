@@ -37,7 +37,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 const char* univl_last_error(void);
 int univl_version(void);
-/* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE) -- lets a
+/* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE, 8 BeamStep) -- lets a
  * foreign-language binding verify its struct mirrors at load time */
 int univl_struct_size(int which);
 /* number of CUs / name of the current device, for host-side launch heuristics; returns 0 or hipError_t */
@@ -362,6 +362,46 @@ int univl_gather_rows(const void* src, void* dst, const int32_t* idx, int32_t ro
 /* x[r, 0:n) <- log_softmax(x[r, 0:n)) in place, fp32 rows ld apart (torch.nn.functional.log_softmax of
  * main_task_caption.py:454 over the vocabulary) */
 int univl_log_softmax_rows(float* x, int32_t rows, int32_t n, int64_t ld, hipStream_t stream);
+/* ---------------------------------------------------------------------------------- caption beam search
+ * Beam.advance (modules/beam.py:63-87) for ALL instances of a batch at one position, entirely in device memory: two launches, no
+ * host involvement, capturable.  Per instance i that is not done:
+ *   candidate(b, v) = lp[i * n_bm + b, v] + scores[i, b]   (one fp32 addition; at the first step only b = 0 counts and nothing is
+ *                     added, beam.py:69), v < V -- columns V .. ld-1 of lp are padding and are never candidates;
+ *   the n_bm largest candidates, sorted descending.  TIE RULE: candidates of equal fp32 value are ordered by LOWER flat index
+ *   b * V + v first (torch.topk leaves this open; here it is part of the contract).  Behaviour on NaN values: unspecified;
+ *   parent = flat / V, token = flat % V;  scores[i, :] <- the kept values, tokens[i * n_bm + k] <- token (int64: the ids the next
+ *   position's univl_embed_text_fwd reads), src[i * n_bm + k] <- i * n_bm + parent (int32: the row index univl_gather_rows reads),
+ *   row t of the three history arrays [Tmax, n_inst, n_bm] <- parent / token / kept value;
+ *   length[i] += 1;  done[i] <- 1 if the TOP beam's token == eos (beam.py:84).
+ * An instance whose done[i] != 0 is FROZEN: scores, tokens, length and done stay as they are, src and the history's parents are
+ * the identity, and the history's tokens / scores repeat the state.
+ * Range: 1 <= n_bm <= UNIVL_BEAM_MAX, n_bm <= V <= ld, any n_inst >= 1, 0 <= t < Tmax; otherwise UNIVL_EINVAL. */
+#define UNIVL_BEAM_MAX 8
+#define UNIVL_BEAM_SLICES 8          /* most column slices a row is scanned in (sizes the workspace) */
+typedef struct {
+    const float* lp; int64_t ld;     /* [n_inst * n_bm, ld] fp32 log-probabilities (what univl_log_softmax_rows leaves)         */
+    int32_t n_inst, n_bm, V;
+    int32_t first_step;              /* != 0: only beam 0's row is read and no score is added                                     */
+    int32_t eos;                     /* token that ends an instance when its top beam emits it (-1: none)                         */
+    const int32_t* eos_dev;          /* optional device word read INSTEAD of eos: a captured hipGraph serves calls with different */
+                                     /* end tokens (the pattern of seed_dev above); NULL: eos                                     */
+    int32_t t, Tmax;                 /* history row written by this call, rows of the history arrays                              */
+    float* scores;                   /* [n_inst, n_bm]   read and written                                                         */
+    uint8_t* done;                   /* [n_inst]         read and written                                                         */
+    int32_t* length;                 /* [n_inst]         read and written                                                         */
+    int64_t* tokens;                 /* [n_inst * n_bm]  written (read for frozen instances)                                      */
+    int32_t* src;                    /* [n_inst * n_bm]  written                                                                  */
+    int32_t* hist_parents; int32_t* hist_tokens; float* hist_scores;     /* [Tmax, n_inst, n_bm] each; row t written             */
+    void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch of >= n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8 bytes          */
+} UnivlBeamStep;
+int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream);
+/* Beam.get_hypothesis (beam.py:108-116) for the n_best best beams of every instance (beams are sorted after univl_beam_step, so
+ * beam k is the k-th best): hyp[i, k, 0 .. length[i]) <- the tokens found by walking the history back from (row length[i] - 1,
+ * beam k) through the parents, the rest of hyp[i, k, :] (Tmax entries) <- -1;  hyp_scores[i, k] <- scores[i, k].
+ * 1 <= n_best <= n_bm <= UNIVL_BEAM_MAX, otherwise UNIVL_EINVAL. */
+int univl_beam_backtrack(const int32_t* hist_parents, const int32_t* hist_tokens, const float* scores, const int32_t* length,
+                         int32_t n_inst, int32_t n_bm, int32_t n_best, int32_t Tmax, int32_t* hyp, float* hyp_scores,
+                         hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

@@ -55,6 +55,7 @@ KEYS = {
     "vocab_dgrad_split": (1, "split-K of the vocabulary dgrad (caption / pretrain heads)"),
     "fused_sim": (1, "pooling + similarity + loss heads as fused launches up to 256 rows"),
     "dpos_gather_min": (32, "rows per position from which position-table gradients are gathered instead of scatter-added"),
+    "beam_step": (1, "caption decoding: Beam.advance as the device-side tail of each position's plan (univl_beam_step) -- CaptionBeamSearch's default beam_step='device'; 0: 'host', the ATen top-k / where path with one host read per position (the comparand)"),
     # ---- optimizer / step structure
     "adam_ride": ("1", "BertAdam chunks ride with the next forward's products; '0': side-stream form; 'force': one graph even with a captured exchange"),
     "tail_ride": (1, "chunks of cross layer 0 / decoder layer 0 ride in the last text / video layer's products; 0: launched in front of the forward"),

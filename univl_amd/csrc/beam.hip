@@ -1,0 +1,246 @@
+// Beam bookkeeping of caption decoding on the device (include/univl_hip.h: univl_beam_step, univl_beam_backtrack).
+//
+// univl_beam_step is Beam.advance (modules/beam.py:63-87) for every instance of a batch at one position, as two launches:
+//   phase 1  grid (rows, slices), 256 threads: a workgroup scans one slice of one row of the log-probabilities with 16-byte loads, each
+//            thread keeping a SORTED top-n_bm of value = lp + the row's accumulated score in registers; the workgroup then takes n_bm
+//            rounds of (value, index) arg-max over the threads' heads (wave shuffles + one LDS word pair per wave) and leaves its n_bm
+//            best (value, column) pairs in the workspace.  The score is added HERE, before any comparison, so that ties the fp32 sum
+//            creates between different log-probabilities of a row are seen by the tie rule like any other tie.
+//   phase 2  one wave per instance: the n_bm best of the (1 or n_bm) x slices x n_bm pairs, then parents / tokens / state / history.
+// Order of candidates everywhere: larger value first, equal values by LOWER flat index b * V + v first (`better` below).
+#include <limits.h>
+#include "common.h"
+#include "univl_hip.h"
+
+namespace {
+
+constexpr int BEAM_NONE = INT_MAX;           // index of an empty top-k slot; loses against every real candidate of any value
+
+__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
+
+__device__ __forceinline__ void wave_best(float& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float w = __shfl_xor(v, o, 64);
+        const int j = __shfl_xor(i, o, 64);
+        if (better(w, j, v, i)) { v = w; i = j; }
+    }
+}
+
+template <int NB>
+__device__ __forceinline__ void keep(float (&tv)[NB], int (&ti)[NB], float v, int i) {
+    if (!better(v, i, tv[NB - 1], ti[NB - 1])) return;
+    tv[NB - 1] = v; ti[NB - 1] = i;
+#pragma unroll
+    for (int j = NB - 1; j > 0; --j) {
+        if (better(tv[j], ti[j], tv[j - 1], ti[j - 1])) {
+            const float fv = tv[j]; tv[j] = tv[j - 1]; tv[j - 1] = fv;
+            const int fi = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = fi;
+        }
+    }
+}
+
+// ws_val / ws_idx: [rows][slices][NB]; idx is the COLUMN within the row (BEAM_NONE: empty)
+template <int NB>
+__global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict__ lp, long ld, int V, int first_step, const float* __restrict__ scores,
+                                                        const uint8_t* __restrict__ done, int chunk, int vec, float* __restrict__ ws_val,
+                                                        int* __restrict__ ws_idx) {
+    __shared__ float red_v[2][4];
+    __shared__ int red_i[2][4];
+    const int inst = first_step ? (int)blockIdx.x : (int)blockIdx.x / NB;
+    if (done[inst]) return;                                   // frozen instance: phase 2 does not read its slots
+    const int row = first_step ? inst * NB : (int)blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
+    const float add = first_step ? 0.f : scores[row];
+    const float* x = lp + (long)row * ld;
+    const int c0 = slice * chunk, c1 = min(V, c0 + chunk);    // chunk is a multiple of 4
+    float tv[NB];
+    int ti[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) { tv[k] = -INFINITY; ti[k] = BEAM_NONE; }
+    if (vec) {
+        // four 16-byte loads in flight per thread; columns >= V of the last word (padding up to ld) are never candidates
+        for (int c = c0 + 4 * tid; c < c1; c += 4 * 1024) {
+            f32x4_t q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int cu = c + u * 1024;
+                q[u] = cu < c1 ? *reinterpret_cast<const f32x4_t*>(x + cu) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int cu = c + u * 1024;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (cu + e < c1) keep<NB>(tv, ti, first_step ? q[u][e] : q[u][e] + add, cu + e);
+            }
+        }
+    } else {
+        for (int c = c0 + tid; c < c1; c += 256) keep<NB>(tv, ti, first_step ? x[c] : x[c] + add, c);
+    }
+    // NB rounds: the best head of the workgroup; its owner (columns are unique to a thread) moves on to its next entry
+    const int wave = tid >> 6;
+    float* out_v = ws_val + ((long)row * gridDim.y + slice) * NB;
+    int* out_i = ws_idx + ((long)row * gridDim.y + slice) * NB;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+        float v = tv[0];
+        int i = ti[0];
+        wave_best(v, i);
+        if ((tid & 63) == 0) { red_v[r & 1][wave] = v; red_i[r & 1][wave] = i; }
+        __syncthreads();                                      // the other buffer is rewritten only after the NEXT barrier
+        v = red_v[r & 1][0]; i = red_i[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (better(red_v[r & 1][w], red_i[r & 1][w], v, i)) { v = red_v[r & 1][w]; i = red_i[r & 1][w]; }
+        if (tid == 0) { out_v[r] = v; out_i[r] = i; }
+        if (i != BEAM_NONE && ti[0] == i) {
+#pragma unroll
+            for (int k = 0; k + 1 < NB; ++k) { tv[k] = tv[k + 1]; ti[k] = ti[k + 1]; }
+            tv[NB - 1] = -INFINITY; ti[NB - 1] = BEAM_NONE;
+        }
+    }
+}
+
+struct BeamOut {
+    float* scores; uint8_t* done; int32_t* length; int64_t* tokens; int32_t* src;
+    int32_t* hist_parents; int32_t* hist_tokens; float* hist_scores;
+};
+
+// one wave per instance; at most 8 x 8 x 8 = 512 pairs
+__global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx, int n_bm, int V, int slices,
+                                                         int first_step, int eos, const int32_t* __restrict__ eos_dev, long hist_row, BeamOut o) {
+    __shared__ float cv[512];
+    __shared__ int ci[512];
+    __shared__ float win_v[8];
+    __shared__ int win_i[8];
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    const long s0 = (long)inst * n_bm;                        // first row / state slot of the instance
+    if (o.done[inst]) {                                       // frozen: state untouched, the history row repeats it
+        if (lane < n_bm) {
+            o.src[s0 + lane] = (int32_t)(s0 + lane);
+            o.hist_parents[hist_row + s0 + lane] = lane;
+            o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
+            o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
+        }
+        return;
+    }
+    const int per_row = slices * n_bm, ncand = (first_step ? 1 : n_bm) * per_row;
+    for (int c = lane; c < ncand; c += 64) {
+        const int b = c / per_row, col = ws_idx[s0 * per_row + c];
+        cv[c] = ws_val[s0 * per_row + c];
+        ci[c] = col == BEAM_NONE ? BEAM_NONE : b * V + col;
+    }
+    __syncthreads();
+    for (int r = 0; r < n_bm; ++r) {
+        float v = -INFINITY;
+        int i = BEAM_NONE, at = -1;
+        for (int c = lane; c < ncand; c += 64)
+            if (better(cv[c], ci[c], v, i)) { v = cv[c]; i = ci[c]; at = c; }
+        const int mine = i;
+        wave_best(v, i);
+        if (i != BEAM_NONE && mine == i) { cv[at] = -INFINITY; ci[at] = BEAM_NONE; }      // flat indices are unique: one owner
+        if (lane == 0) { win_v[r] = v; win_i[r] = i; }
+        __syncthreads();
+    }
+    if (lane < n_bm) {
+        // fewer than n_bm comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
+        const int flat = win_i[lane] == BEAM_NONE ? lane * V : win_i[lane], parent = flat / V, token = flat % V;
+        o.scores[s0 + lane] = win_v[lane];
+        o.tokens[s0 + lane] = token;
+        o.src[s0 + lane] = (int32_t)(s0 + parent);
+        o.hist_parents[hist_row + s0 + lane] = parent;
+        o.hist_tokens[hist_row + s0 + lane] = token;
+        o.hist_scores[hist_row + s0 + lane] = win_v[lane];
+        if (lane == 0) {
+            o.length[inst] += 1;
+            if (token == (eos_dev ? *eos_dev : eos)) o.done[inst] = 1;               // beam.py:84: the TOP beam emitted EOS
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(const int32_t* __restrict__ hp, const int32_t* __restrict__ ht, const float* __restrict__ scores,
+                                                            const int32_t* __restrict__ length, int n_inst, int n_bm, int n_best, int Tmax,
+                                                            int32_t* __restrict__ hyp, float* __restrict__ hyp_scores) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n_inst * n_best) return;
+    const int inst = e / n_best, k = e % n_best;
+    int len = length[inst];
+    len = len < 0 ? 0 : (len > Tmax ? Tmax : len);
+    int32_t* out = hyp + (long)e * Tmax;
+    for (int j = len; j < Tmax; ++j) out[j] = -1;
+    int b = k;
+    for (int j = len - 1; j >= 0; --j) {
+        const long at = ((long)j * n_inst + inst) * n_bm + b;
+        out[j] = ht[at];
+        b = hp[at];
+        b = b < 0 ? 0 : (b >= n_bm ? n_bm - 1 : b);            // a corrupt history must not walk out of the arrays
+    }
+    hyp_scores[e] = scores[(long)inst * n_bm + k];
+}
+
+template <int NB>
+void launch_scan(const UnivlBeamStep* d, int slices, int chunk, int vec, float* ws_val, int* ws_idx, hipStream_t stream) {
+    const unsigned rows = d->first_step ? d->n_inst : d->n_inst * NB;
+    hipLaunchKernelGGL(beam_scan_kernel<NB>, dim3(rows, slices), dim3(256), 0, stream, d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores,
+                       d->done, chunk, vec, ws_val, ws_idx);
+}
+
+}  // namespace
+
+extern "C" int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_step: null descriptor");
+    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V &&
+                    d->V <= INT_MAX / UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
+                    "univl_beam_step: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", d->n_inst, d->n_bm, d->V,
+                    (long long)d->ld, UNIVL_BEAM_MAX);
+    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "univl_beam_step: history row t=%d of Tmax=%d", d->t, d->Tmax);
+    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
+                    d->ws, UNIVL_EINVAL, "univl_beam_step: null pointer");
+    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
+    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
+    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
+                    "univl_beam_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); got %lld",
+                    (long long)need, (long long)d->ws_bytes);
+    // slices: enough workgroups for the whole chip (~4 per CU at 80 rows), but at least 1024 columns each
+    const int64_t scanned = d->first_step ? d->n_inst : rows;
+    int slices = (int)((1024 + scanned - 1) / scanned);
+    const int by_len = (d->V + 1023) / 1024;
+    slices = slices > by_len ? by_len : slices;
+    slices = slices < 1 ? 1 : (slices > UNIVL_BEAM_SLICES ? UNIVL_BEAM_SLICES : slices);
+    const int chunk = ((d->V + 3) / 4 + slices - 1) / slices * 4;
+    const int vec = (aligned16(d->lp) && d->ld % 4 == 0) ? 1 : 0;      // then every row starts 16-byte aligned and ld >= roundup4(V)
+    float* ws_val = static_cast<float*>(d->ws);
+    int* ws_idx = reinterpret_cast<int*>(ws_val + rows * slices * d->n_bm);
+    switch (d->n_bm) {
+        case 1: launch_scan<1>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        case 2: launch_scan<2>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        case 3: launch_scan<3>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        case 4: launch_scan<4>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        case 5: launch_scan<5>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        case 6: launch_scan<6>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        case 7: launch_scan<7>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+        default: launch_scan<8>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
+    }
+    UNIVL_LAUNCH_CHECK();
+    BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
+    hipLaunchKernelGGL(beam_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->V, slices, d->first_step ? 1 : 0,
+                       d->eos, d->eos_dev, (long)d->t * rows, o);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_beam_backtrack(const int32_t* hist_parents, const int32_t* hist_tokens, const float* scores, const int32_t* length,
+                                    int32_t n_inst, int32_t n_bm, int32_t n_best, int32_t Tmax, int32_t* hyp, float* hyp_scores,
+                                    hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(hist_parents && hist_tokens && scores && length && hyp && hyp_scores, UNIVL_EINVAL, "univl_beam_backtrack: null pointer");
+    UNIVL_CHECK_ARG(n_inst >= 1 && n_bm >= 1 && n_bm <= UNIVL_BEAM_MAX && n_best >= 1 && n_best <= n_bm && Tmax >= 1 &&
+                    (int64_t)n_inst * n_best <= INT_MAX / 2, UNIVL_EINVAL,
+                    "univl_beam_backtrack: n_inst=%d n_bm=%d n_best=%d Tmax=%d (1 <= n_best <= n_bm <= %d)", n_inst, n_bm, n_best, Tmax, UNIVL_BEAM_MAX);
+    const int total = n_inst * n_best;
+    hipLaunchKernelGGL(beam_backtrack_kernel, dim3((total + 63) / 64), dim3(64), 0, stream, hist_parents, hist_tokens, scores, length, n_inst,
+                       n_bm, n_best, Tmax, hyp, hyp_scores);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}

@@ -31,6 +31,7 @@ extern "C" int univl_struct_size(int which) {
         case 5: return (int)sizeof(UnivlSeg);
         case 6: return (int)sizeof(UnivlAdam);
         case 7: return (int)sizeof(UnivlVocabCE);
+        case 8: return (int)sizeof(UnivlBeamStep);
         default: return -1;
     }
 }

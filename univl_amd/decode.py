@@ -12,20 +12,49 @@ of earlier inputs, so here:
   * the decoder keeps a key/value cache per beam: a step embeds one token per beam, projects q/k/v for that position
     only, attends over the cache (attention kernel with Sq = 1 and a cache batch stride), and the five beams of an
     instance share the instance's encoder K/V by running encoder attention as B = n_inst, Sq = n_beams;
-  * beam bookkeeping (Beam.advance, beam.py:63-87) stays on the device: top-k over the flattened (beam x vocab)
-    log-probabilities, back-pointers = id // vocab, tokens = id % vocab, the cache rows re-ordered by back-pointer with
-    one gather per layer; the host reads one "all instances done" flag per step.  Finished instances keep their slots
-    (static shapes) and are frozen, which is what removing them (collate_active_info, :404-416) amounts to.
+  * beam bookkeeping (Beam.advance, beam.py:63-87) is the LAST launch of each position's plan (univl_beam_step,
+    csrc/beam.hip): top-n_bm over the flattened (beam x vocab) candidates, back-pointers = id // vocab, tokens = id % vocab
+    written straight into the buffers the next position's embedding and cache gather read, plus one row of a device-side
+    history.  One position is one graph replay and nothing else: no ATen kernel, no host read.  The host looks at the
+    per-instance `done` bytes every `sync_every` positions only to stop early; finished instances keep their slots (static
+    shapes) and are frozen, which is what removing them (collate_active_info, :404-416) amounts to, so the result does
+    not depend on when the host looks.  Hypotheses are walked back on the device too (univl_beam_backtrack).
+  * `beam_step="host"` keeps the earlier bookkeeping (torch.topk / where on the device, one host read per position) as the
+    comparand of the tests and the A/B of the timing; it fills the same result object.
 
 Same results as the reference's procedure on the same logits: first step uses beam 0's distribution only (beam.py:69),
-an instance is done when its top beam emits EOS (beam.py:84), the reported hypothesis is the best-scored beam walked
-back through the back-pointers (beam.py:108-116, collect_hypothesis_and_scores n_best = 1).
+an instance is done when its top beam emits EOS (beam.py:84), the reported hypotheses are the n_best best-scored beams walked
+back through the back-pointers (beam.py:108-116, collect_hypothesis_and_scores).  Candidates of exactly equal fp32 value
+are ordered by lower flat index first in the device path (include/univl_hip.h); torch.topk leaves that order open.
 """
 import torch
 
-from . import ops
+from . import _ab, ops
 from .engine import Plan, _gemm_desc
 from .steps import Ctx, CrossRun, RowFeatures, VocabHead, H
+
+
+class BeamResult:
+    """What CaptionBeamSearch.decode returns -- DEVICE tensors only:
+      tokens  [n, n_best, Tmax] int32   the n_best best hypotheses of every instance, -1 padded
+      scores  [n, n_best] fp32          their accumulated log-probabilities (non-increasing in k)
+      lengths [n] int32                 generated tokens per instance (all n_best hypotheses of an instance share it)
+      parents / step_tokens / step_scores  [steps_run, n, n_bm]   the history; steps_run is the max_len of the call, rows at or
+                                        past an instance's length are frozen rows (identity parents, state repeated)."""
+
+    def __init__(self, tokens, scores, lengths, parents, step_tokens, step_scores):
+        self.tokens, self.scores, self.lengths = tokens, scores, lengths
+        self.parents, self.step_tokens, self.step_scores = parents, step_tokens, step_scores
+
+    @property
+    def steps_run(self):
+        return self.parents.shape[0]
+
+    def hypotheses(self):
+        """[n][n_best] token lists, as collect_hypothesis_and_scores(inst_dec_beams, n_best) gives them -- the one place that
+        copies to the host."""
+        tok, lens = self.tokens.cpu().tolist(), self.lengths.cpu().tolist()
+        return [[row[:lens[i]] for row in inst] for i, inst in enumerate(tok)]
 
 
 class CaptionBeamSearch:
@@ -33,9 +62,16 @@ class CaptionBeamSearch:
 
     NH, I = 12, 3072
 
-    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True):
+    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None):
+        """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
+        None: the UNIVL_AB key `beam_step` (default device)."""
         if model.decoder is None:
             raise RuntimeError("CaptionBeamSearch: this model was built without a decoder (stage one)")
+        if beam_step is None:
+            beam_step = "device" if _ab.get("beam_step") else "host"
+        if beam_step not in ("device", "host"):
+            raise ValueError("CaptionBeamSearch: beam_step must be 'device' or 'host', got %r" % (beam_step,))
+        self.beam_step = beam_step
         self.model, self.n_inst, self.W, self.F, self.n_bm = model, n_inst, W, F, n_bm
         self.use_graphs = bool(use_graphs)     # each step plan (one per position) is captured once into a hipGraph
         self.Tmax = Tmax = int(max_len or model.task_config.max_words)
@@ -78,10 +114,27 @@ class CaptionBeamSearch:
         self.src = e(R, dtype=torch.int32)               # cache row each beam continues from
         self.steps = {}
         self.base = torch.arange(n_inst, device=cx.dev, dtype=torch.int64)[:, None] * n_bm
+        # ---- beam state and history (read and written by univl_beam_step; the host path fills the same buffers)
+        dev = cx.dev
+        self.scores = torch.zeros(n_inst, n_bm, device=dev)
+        self.done = torch.zeros(n_inst, dtype=torch.uint8, device=dev)
+        self.length = torch.zeros(n_inst, dtype=torch.int32, device=dev)
+        self.hist_par = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
+        self.hist_tok = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
+        self.hist_sc = torch.zeros(Tmax, n_inst, n_bm, device=dev)
+        self.eos_dev = torch.full((1,), -1, dtype=torch.int32, device=dev)     # a device word: the captured plans serve any eos
+        self.ident = torch.arange(R, device=dev, dtype=torch.int32)
+        self.ident_nb = torch.arange(n_bm, device=dev, dtype=torch.int32).expand(n_inst, n_bm)
+        self.done_host = torch.zeros(n_inst, dtype=torch.uint8).pin_memory()
+        self.done_event = torch.cuda.Event()
+        self.beam_ws = ops.beam_ws(n_inst, n_bm, dev) if beam_step == "device" else None
 
     # ------------------------------------------------------------------------------------------ step plans
-    def _step_plan(self, t):
-        pl = self.steps.get(t)
+    def _step_plan(self, t, beam=False):
+        """The plan of position t.  beam=False: embedding .. log-probabilities (what step_logprobs replays; it neither reads nor
+        advances the beam state).  beam=True: a second captured form of the same launches with univl_beam_step as its last entry
+        (t, the history row and first_step are baked into that position's descriptor)."""
+        pl = self.steps.get((t, beam))
         if pl is not None:
             return pl
         cx, fl, dt, R, Tmax, S = self.cx, self.cx.fl, self.cx.dt, self.R, self.Tmax, self.S
@@ -134,8 +187,13 @@ class CaptionBeamSearch:
             x32, x16 = ws["o32"], ws["o16"]
         self.head.build_forward(pl, x16, with_loss=False)
         pl.add_callable(lambda: ops.log_softmax_rows(self.head.logits, self.V))
+        if beam:
+            pl.add("univl_beam_step", ops.beam_step_desc(
+                self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done, length=self.length,
+                tokens=self.ids, src=self.src, hist_parents=self.hist_par, hist_tokens=self.hist_tok, hist_scores=self.hist_sc,
+                ws=self.beam_ws, eos_dev=self.eos_dev))
         pl.keepalive = (pos,)
-        self.steps[t] = pl
+        self.steps[(t, beam)] = pl
         return pl
 
     # ------------------------------------------------------------------------------------------------- run
@@ -160,19 +218,62 @@ class CaptionBeamSearch:
                         input_mask.reshape(-1, input_mask.shape[-1]), video_mask.reshape(-1, video_mask.shape[-1]))
         self.setup.run()
 
+    def _all_done(self):
+        """The n done bytes through a pinned buffer and an event wait (the only host read of the device path's loop)."""
+        self.done_host.copy_(self.done, non_blocking=True)
+        self.done_event.record()
+        self.done_event.synchronize()
+        return bool(self.done_host.all())
+
     @torch.no_grad()
-    def __call__(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None):
-        """Returns (hypotheses: list of n_inst token lists, as collect_hypothesis_and_scores(n_best=1) gives them,
-        scores: [n_inst] fp32 tensor of the best beams' accumulated log-probabilities)."""
-        n, nb, V, dev = self.n_inst, self.n_bm, self.V, self.cx.dev
+    def decode(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None, n_best=1, sync_every=8):
+        """Beam search over at most max_len positions; returns a BeamResult (device tensors).  n_best <= n_bm hypotheses per
+        instance.  sync_every: the host reads the done flags every that many positions to stop early (0: never, run to max_len);
+        finished instances are frozen, so the result does not depend on it."""
+        n, nb = self.n_inst, self.n_bm
         max_len = min(int(max_len or self.Tmax), self.Tmax)
+        if not 1 <= int(n_best) <= nb:
+            raise ValueError("CaptionBeamSearch.decode: n_best=%r, expected 1 .. n_bm=%d" % (n_best, nb))
         self.encode(sequence_output, visual_output, input_mask, video_mask)
+        # state reset (outside the position loop)
+        self.scores.zero_()
+        self.done.zero_()
+        self.length.zero_()
+        self.ids.fill_(int(bos))
+        self.src.copy_(self.ident)
+        self.eos_dev.fill_(int(eos))
+        ran = max_len
+        if self.beam_step == "device":
+            for t in range(max_len):
+                pl = self._step_plan(t, beam=True)
+                if self.use_graphs and not torch.cuda.is_current_stream_capturing():
+                    pl.run_graphed()
+                else:
+                    pl.run()
+                if sync_every and (t + 1) % sync_every == 0 and t + 1 < max_len and self._all_done():
+                    ran = t + 1
+                    break
+        else:
+            ran = self._host_steps(max_len, int(eos))
+        if ran < max_len:            # every instance is done: the rows not run are the frozen rows the kernel would have written
+            self.hist_par[ran:max_len] = self.ident_nb
+            self.hist_tok[ran:max_len] = self.hist_tok[ran - 1]
+            self.hist_sc[ran:max_len] = self.hist_sc[ran - 1]
+        tokens, scores = ops.beam_backtrack(self.hist_par, self.hist_tok, self.scores, self.length, int(n_best))
+        return BeamResult(tokens, scores, self.length.clone(), self.hist_par[:max_len].clone(), self.hist_tok[:max_len].clone(),
+                          self.hist_sc[:max_len].clone())
+
+    def _host_steps(self, max_len, eos):
+        """beam_step="host": the bookkeeping as ATen calls on the device with one host read per position -- the arithmetic of the
+        path this class had before univl_beam_step, kept as the comparand; it leaves state and history in the same buffers."""
+        n, nb, V, dev = self.n_inst, self.n_bm, self.V, self.cx.dev
         scores = torch.zeros(n, nb, device=dev)
         done = torch.zeros(n, dtype=torch.bool, device=dev)
         length = torch.zeros(n, dtype=torch.int64, device=dev)
-        tokens = torch.full((n, nb), int(bos), dtype=torch.int64, device=dev)
-        parents = torch.arange(nb, device=dev, dtype=torch.int64).expand(n, nb).contiguous()
-        prev_ks, next_ys = [], []
+        tokens = self.ids.view(n, nb).clone()
+        ident = torch.arange(nb, device=dev).expand(n, nb)
+        parents = ident.contiguous()
+        ran = max_len
         for t in range(max_len):
             lp = self.step_logprobs(t, tokens, (self.base + parents) if t > 0 else None).view(n, nb, V)
             if t == 0:
@@ -182,22 +283,26 @@ class CaptionBeamSearch:
             pk, ny = ids // V, ids % V
             act = ~done
             scores = torch.where(act[:, None], best, scores)
-            parents = torch.where(act[:, None], pk, torch.arange(nb, device=dev).expand(n, nb))
+            parents = torch.where(act[:, None], pk, ident)
             tokens = torch.where(act[:, None], ny, tokens)
-            prev_ks.append(pk)
-            next_ys.append(ny)
+            self.hist_par[t].copy_(parents)
+            self.hist_tok[t].copy_(tokens)
+            self.hist_sc[t].copy_(scores)
             length += act.to(torch.int64)
-            done = done | (act & (ny[:, 0] == int(eos)))                                      # beam.py:84
+            done = done | (act & (ny[:, 0] == eos))                                           # beam.py:84
             if bool(done.all()):
+                ran = t + 1
                 break
-        # hypotheses: best beam (index 0 after the sorted top-k) walked back through the back-pointers (beam.py:108-116)
-        pks, nys = torch.stack(prev_ks).cpu(), torch.stack(next_ys).cpu()
-        lens = length.cpu().tolist()
-        hyps = []
-        for i in range(n):
-            k, hyp = 0, []
-            for j in range(lens[i] - 1, -1, -1):
-                hyp.append(int(nys[j, i, k]))
-                k = int(pks[j, i, k])
-            hyps.append(hyp[::-1])
-        return hyps, scores[:, 0].clone()
+        self.scores.copy_(scores)
+        self.done.copy_(done)
+        self.length.copy_(length)
+        self.ids.copy_(tokens.reshape(-1))
+        self.src.copy_((self.base + parents).reshape(-1))
+        return ran
+
+    @torch.no_grad()
+    def __call__(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None):
+        """Returns (hypotheses: list of n_inst token lists, as collect_hypothesis_and_scores(n_best=1) gives them,
+        scores: [n_inst] fp32 tensor of the best beams' accumulated log-probabilities)."""
+        res = self.decode(sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=max_len, n_best=1)
+        return [h[0] for h in res.hypotheses()], res.scores[:, 0].clone()

@@ -351,6 +351,55 @@ def log_softmax_rows(x, n):
     _lib.check(_lib.lib().univl_log_softmax_rows(_p(x), x.shape[0], n, x.stride(0), _stream()), "log_softmax_rows")
 
 
+def beam_ws(n_inst, n_bm, device):
+    """Scratch of univl_beam_step for n_inst x n_bm beams (include/univl_hip.h: UnivlBeamStep.ws)."""
+    return torch.empty(n_inst * n_bm * _lib.BEAM_SLICES * n_bm * 2, dtype=torch.float32, device=device)
+
+
+def beam_step_desc(lp, V, n_inst, n_bm, t, *, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos=-1,
+                   eos_dev=None, first_step=None):
+    """lp: [n_inst * n_bm, ld] fp32 view (row stride ld >= V); state / outputs as in include/univl_hip.h: UnivlBeamStep.  first_step
+    defaults to t == 0.  Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
+    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev)
+    R = n_inst * n_bm
+    assert lp.dtype == torch.float32 and lp.dim() == 2 and lp.stride(1) == 1 and lp.shape[0] >= R
+    assert scores.dtype == torch.float32 and scores.numel() == R and scores.is_contiguous()
+    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == n_inst
+    assert length.dtype == torch.int32 and length.numel() == n_inst
+    assert tokens.dtype == torch.int64 and tokens.numel() == R and src.dtype == torch.int32 and src.numel() == R
+    Tmax = hist_parents.shape[0]
+    for h, dt_ in ((hist_parents, torch.int32), (hist_tokens, torch.int32), (hist_scores, torch.float32)):
+        assert h.dtype == dt_ and h.is_contiguous() and h.shape[0] == Tmax and h.numel() == Tmax * R
+    assert eos_dev is None or eos_dev.dtype == torch.int32
+    d = _lib.BeamStep()
+    d.lp, d.ld, d.n_inst, d.n_bm, d.V = _p(lp), lp.stride(0), n_inst, n_bm, V
+    d.first_step, d.eos, d.eos_dev, d.t, d.Tmax = int(t == 0 if first_step is None else first_step), int(eos), _p(eos_dev), t, Tmax
+    d.scores, d.done, d.length, d.tokens, d.src = _p(scores), _p(done), _p(length), _p(tokens), _p(src)
+    d.hist_parents, d.hist_tokens, d.hist_scores = _p(hist_parents), _p(hist_tokens), _p(hist_scores)
+    d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
+    return d
+
+
+def beam_step(*a, **kw):
+    d = beam_step_desc(*a, **kw)
+    _lib.check(_lib.lib().univl_beam_step(_BYREF(d), _stream()), "beam_step")
+
+
+def beam_backtrack(hist_parents, hist_tokens, scores, length, n_best):
+    """Walk the n_best best beams of every instance back through the history (include/univl_hip.h: univl_beam_backtrack).
+    Returns (hyp [n, n_best, Tmax] int32, -1 padded; hyp_scores [n, n_best] fp32)."""
+    _require_gpu(hist_parents, hist_tokens, scores, length)
+    Tmax, n, n_bm = hist_parents.shape
+    assert hist_parents.dtype == torch.int32 and hist_tokens.dtype == torch.int32 and hist_tokens.shape == hist_parents.shape
+    assert hist_parents.is_contiguous() and hist_tokens.is_contiguous() and scores.is_contiguous()
+    assert scores.dtype == torch.float32 and scores.shape == (n, n_bm) and length.dtype == torch.int32 and length.numel() == n
+    hyp = torch.empty(n, n_best, Tmax, dtype=torch.int32, device=scores.device)
+    hs = torch.empty(n, n_best, dtype=torch.float32, device=scores.device)
+    _lib.check(_lib.lib().univl_beam_backtrack(_p(hist_parents), _p(hist_tokens), _p(scores), _p(length), n, n_bm, int(n_best), Tmax,
+                                               _p(hyp), _p(hs), _stream()), "beam_backtrack")
+    return hyp, hs
+
+
 def rank_counts(sim):
     """sim: [n, n] fp32 device tensor (row stride >= n).  Returns (gt, eq) int32 [n]."""
     _require_gpu(sim)
