@@ -402,6 +402,15 @@ int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream);
 int univl_beam_backtrack(const int32_t* hist_parents, const int32_t* hist_tokens, const float* scores, const int32_t* length,
                          int32_t n_inst, int32_t n_bm, int32_t n_best, int32_t Tmax, int32_t* hyp, float* hyp_scores,
                          hipStream_t stream);
+/* The caption cut of main_task_caption.py:555-560 (first "[SEP]", then first "[PAD]") on the rows univl_beam_backtrack writes:
+ * for row r = i * n_best + k of hyp [n_inst * n_best, Tmax], with len = length[i] clamped to [0, Tmax],
+ *   cap_len[r] <- the smallest j < len with hyp[r, j] == eos or hyp[r, j] == pad, else len (the reference's two successive cuts);
+ *   cap_tokens[r, 0 .. cap_len[r]) <- hyp[r, 0 .. cap_len[r]), the rest of cap_tokens[r, :] (Tmax entries) <- -1.
+ * eos / pad: a negative id means "none".  eos_dev: optional device word read INSTEAD of eos (as UnivlBeamStep.eos_dev; NULL: eos).
+ * cap_tokens MAY ALIAS hyp (the cut in place); otherwise the buffers must not overlap.  One launch, capturable.
+ * 1 <= n_best <= UNIVL_BEAM_MAX, n_inst >= 1, Tmax >= 1, otherwise UNIVL_EINVAL. */
+int univl_beam_captions(const int32_t* hyp, const int32_t* length, int32_t n_inst, int32_t n_best, int32_t Tmax, int32_t eos, int32_t pad,
+                        const int32_t* eos_dev, int32_t* cap_tokens, int32_t* cap_len, hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

@@ -134,6 +134,8 @@ def lib():
     L.univl_log_softmax_rows.argtypes = [vp, i32, i32, i64, vp]
     L.univl_beam_backtrack.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.univl_beam_backtrack.restype = i32
+    L.univl_beam_captions.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.univl_beam_captions.restype = i32
     L.univl_rank_counts.argtypes = [vp, i32, i64, vp, vp, vp]
     L.univl_scale_by_device_scalar.argtypes = [vp, i64, vp, vp]
     L.univl_pair_concat_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
@@ -186,7 +188,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_dev
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_backtrack", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

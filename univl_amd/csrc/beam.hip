@@ -1,4 +1,4 @@
-// Beam bookkeeping of caption decoding on the device (include/univl_hip.h: univl_beam_step, univl_beam_backtrack).
+// Beam bookkeeping of caption decoding on the device (include/univl_hip.h: univl_beam_step, univl_beam_backtrack, univl_beam_captions).
 //
 // univl_beam_step is Beam.advance (modules/beam.py:63-87) for every instance of a batch at one position, as two launches:
 //   phase 1  grid (rows, slices), 256 threads: a workgroup scans one slice of one row of the log-probabilities with 16-byte loads, each
@@ -178,6 +178,34 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(const int32_t* __res
     hyp_scores[e] = scores[(long)inst * n_bm + k];
 }
 
+// The cut of main_task_caption.py:555-560 on the rows the walk-back wrote: one wave per hypothesis row, four rows per workgroup.
+// Pass 1 reads 64 tokens at a time and takes the first matching lane from a ballot; pass 2 rewrites the row.  hyp and cap_tokens
+// may be the same buffer (no __restrict__): every lane reads the word it is about to write, and a row belongs to one wave.
+__global__ __launch_bounds__(256) void beam_captions_kernel(const int32_t* hyp, const int32_t* __restrict__ length, int rows, int n_best, int Tmax,
+                                                            int eos, int pad, const int32_t* __restrict__ eos_dev, int32_t* cap_tokens,
+                                                            int32_t* __restrict__ cap_len) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;                                  // whole waves leave: the ballots below see full rows only
+    int len = length[row / n_best];
+    len = len < 0 ? 0 : (len > Tmax ? Tmax : len);
+    const int end = eos_dev ? *eos_dev : eos;
+    const int32_t* in = hyp + (long)row * Tmax;
+    int32_t* out = cap_tokens + (long)row * Tmax;
+    int cut = len;
+    for (int j0 = 0; j0 < len; j0 += 64) {
+        const int j = j0 + lane;
+        const int tok = j < len ? in[j] : -1;
+        const bool hit = j < len && ((end >= 0 && tok == end) || (pad >= 0 && tok == pad));
+        const unsigned long long m = __ballot(hit);
+        if (m) { cut = j0 + __ffsll(m) - 1; break; }          // m is wave-uniform: all lanes leave together
+    }
+    for (int j = lane; j < Tmax; j += 64) {
+        const int tok = j < cut ? in[j] : -1;
+        out[j] = tok;
+    }
+    if (lane == 0) cap_len[row] = cut;
+}
+
 template <int NB>
 void launch_scan(const UnivlBeamStep* d, int slices, int chunk, int vec, float* ws_val, int* ws_idx, hipStream_t stream) {
     const unsigned rows = d->first_step ? d->n_inst : d->n_inst * NB;
@@ -241,6 +269,19 @@ extern "C" int univl_beam_backtrack(const int32_t* hist_parents, const int32_t* 
     const int total = n_inst * n_best;
     hipLaunchKernelGGL(beam_backtrack_kernel, dim3((total + 63) / 64), dim3(64), 0, stream, hist_parents, hist_tokens, scores, length, n_inst,
                        n_bm, n_best, Tmax, hyp, hyp_scores);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_beam_captions(const int32_t* hyp, const int32_t* length, int32_t n_inst, int32_t n_best, int32_t Tmax, int32_t eos,
+                                   int32_t pad, const int32_t* eos_dev, int32_t* cap_tokens, int32_t* cap_len, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(hyp && length && cap_tokens && cap_len, UNIVL_EINVAL, "univl_beam_captions: null pointer");
+    UNIVL_CHECK_ARG(n_inst >= 1 && n_best >= 1 && n_best <= UNIVL_BEAM_MAX && Tmax >= 1 && (int64_t)n_inst * n_best <= INT_MAX / 2, UNIVL_EINVAL,
+                    "univl_beam_captions: n_inst=%d n_best=%d Tmax=%d (1 <= n_best <= %d, Tmax >= 1)", n_inst, n_best, Tmax, UNIVL_BEAM_MAX);
+    const int rows = n_inst * n_best;
+    hipLaunchKernelGGL(beam_captions_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, hyp, length, rows, n_best, Tmax, eos, pad, eos_dev,
+                       cap_tokens, cap_len);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

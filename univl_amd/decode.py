@@ -50,6 +50,13 @@ class BeamResult:
     def steps_run(self):
         return self.parents.shape[0]
 
+    def captions(self, eos, pad, eos_dev=None):
+        """The reference's cut of every hypothesis at the first eos ("[SEP]"), then at the first pad ("[PAD]")
+        (main_task_caption.py:555-560), on the device (ops.beam_captions): (cap_tokens [n, n_best, Tmax] int32, -1 past the cut;
+        cap_len [n, n_best] int32), device tensors.  eos / pad: token ids, negative for none; eos_dev: a device word read instead
+        of eos.  `tokens` is left as it is."""
+        return ops.beam_captions(self.tokens, self.lengths, eos, pad, eos_dev=eos_dev)
+
     def hypotheses(self):
         """[n][n_best] token lists, as collect_hypothesis_and_scores(inst_dec_beams, n_best) gives them -- the one place that
         copies to the host."""
@@ -58,7 +65,17 @@ class BeamResult:
 
 
 class CaptionBeamSearch:
-    """Compiled decoding session for a fixed (n_inst, max_words W, max_frames F, beam size, max_len)."""
+    """Compiled decoding session for a fixed (n_inst, max_words W, max_frames F, beam size, max_len).
+
+    Partial batches: encode() / decode() / __call__ take n_active (None: n_inst), the number of instances the call carries; the
+    feature and mask tensors then have n_active rows.  Slots [0, n_active) carry the batch, slots [n_active, n_inst) are IDLE: their
+    `done` byte is preset to 1 and their `length` to 0 before position 0, so the beam scan skips them and the select kernel writes
+    frozen rows for them, as both do for an instance that has finished.  The launch shapes do not change, so a loader's short last
+    batch replays the plans and hipGraphs of the full ones: no second session, no new capture.  The decoder plans still run over
+    the idle rows, so what they read there must be defined and finite: the feature and mask slots are zero-filled once at
+    construction, and after that an idle slot simply keeps what an earlier batch left in it.  No launch reduces across instances
+    (DESIGN.md section 7), so the active instances' results do not depend on it.  The BeamResult holds the first n_active
+    instances only."""
 
     NH, I = 12, 3072
 
@@ -85,6 +102,8 @@ class CaptionBeamSearch:
         rows = list(range(n_inst))
         # ---- once per batch: cross encoder per instance + encoder K/V of every decoder layer
         self.feats = RowFeatures(cx, n_inst, n_inst, W, F)
+        for buf in (self.feats.seq_out, self.feats.vis_out, self.feats.amask, self.feats.vmask):
+            buf.zero_()                                  # idle slots of a partial first batch read these (class docstring)
         self.run = run = CrossRun(cx, self.feats, rows, rows)
         self.S = S = run.S
         self.setup = Plan()
@@ -212,10 +231,22 @@ class CaptionBeamSearch:
         return self.head.logits[:, :self.V]
 
     @torch.no_grad()
-    def encode(self, sequence_output, visual_output, input_mask, video_mask):
+    def _active(self, n_active):
+        if n_active is None:
+            return self.n_inst
+        if not 1 <= int(n_active) <= self.n_inst:
+            raise ValueError("CaptionBeamSearch: n_active=%r, expected 1 .. n_inst=%d" % (n_active, self.n_inst))
+        return int(n_active)
+
+    @torch.no_grad()
+    def encode(self, sequence_output, visual_output, input_mask, video_mask, n_active=None):
+        m = self._active(n_active)
+        if sequence_output.shape[0] != m or visual_output.shape[0] != m:
+            raise ValueError("CaptionBeamSearch.encode: features of %d / %d instances, expected %d"
+                             % (sequence_output.shape[0], visual_output.shape[0], m))
         self.model.flat.refresh_shadow()
         self.feats.load(sequence_output.to(torch.float32), visual_output.to(torch.float32),
-                        input_mask.reshape(-1, input_mask.shape[-1]), video_mask.reshape(-1, video_mask.shape[-1]))
+                        input_mask.reshape(-1, input_mask.shape[-1]), video_mask.reshape(-1, video_mask.shape[-1]), rows=m)
         self.setup.run()
 
     def _all_done(self):
@@ -226,19 +257,24 @@ class CaptionBeamSearch:
         return bool(self.done_host.all())
 
     @torch.no_grad()
-    def decode(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None, n_best=1, sync_every=8):
+    def decode(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None, n_best=1, sync_every=8,
+               n_active=None):
         """Beam search over at most max_len positions; returns a BeamResult (device tensors).  n_best <= n_bm hypotheses per
         instance.  sync_every: the host reads the done flags every that many positions to stop early (0: never, run to max_len);
-        finished instances are frozen, so the result does not depend on it."""
+        finished instances are frozen, so the result does not depend on it.  n_active: instances in this batch (class docstring);
+        the result then has n_active instances."""
         n, nb = self.n_inst, self.n_bm
+        m = self._active(n_active)
         max_len = min(int(max_len or self.Tmax), self.Tmax)
         if not 1 <= int(n_best) <= nb:
             raise ValueError("CaptionBeamSearch.decode: n_best=%r, expected 1 .. n_bm=%d" % (n_best, nb))
-        self.encode(sequence_output, visual_output, input_mask, video_mask)
+        self.encode(sequence_output, visual_output, input_mask, video_mask, n_active=n_active)
         # state reset (outside the position loop)
         self.scores.zero_()
         self.done.zero_()
         self.length.zero_()
+        if m < n:
+            self.done[m:].fill_(1)           # idle slots: done from the start, length 0
         self.ids.fill_(int(bos))
         self.src.copy_(self.ident)
         self.eos_dev.fill_(int(eos))
@@ -260,15 +296,15 @@ class CaptionBeamSearch:
             self.hist_tok[ran:max_len] = self.hist_tok[ran - 1]
             self.hist_sc[ran:max_len] = self.hist_sc[ran - 1]
         tokens, scores = ops.beam_backtrack(self.hist_par, self.hist_tok, self.scores, self.length, int(n_best))
-        return BeamResult(tokens, scores, self.length.clone(), self.hist_par[:max_len].clone(), self.hist_tok[:max_len].clone(),
-                          self.hist_sc[:max_len].clone())
+        return BeamResult(tokens[:m], scores[:m], self.length[:m].clone(), self.hist_par[:max_len, :m].clone(),
+                          self.hist_tok[:max_len, :m].clone(), self.hist_sc[:max_len, :m].clone())
 
     def _host_steps(self, max_len, eos):
         """beam_step="host": the bookkeeping as ATen calls on the device with one host read per position -- the arithmetic of the
         path this class had before univl_beam_step, kept as the comparand; it leaves state and history in the same buffers."""
         n, nb, V, dev = self.n_inst, self.n_bm, self.V, self.cx.dev
         scores = torch.zeros(n, nb, device=dev)
-        done = torch.zeros(n, dtype=torch.bool, device=dev)
+        done = self.done.bool()                # zeros, but for the idle slots of a partial batch
         length = torch.zeros(n, dtype=torch.int64, device=dev)
         tokens = self.ids.view(n, nb).clone()
         ident = torch.arange(nb, device=dev).expand(n, nb)
@@ -301,8 +337,9 @@ class CaptionBeamSearch:
         return ran
 
     @torch.no_grad()
-    def __call__(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None):
-        """Returns (hypotheses: list of n_inst token lists, as collect_hypothesis_and_scores(n_best=1) gives them,
-        scores: [n_inst] fp32 tensor of the best beams' accumulated log-probabilities)."""
-        res = self.decode(sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=max_len, n_best=1)
+    def __call__(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None, n_active=None):
+        """Returns (hypotheses: list of n_inst (n_active) token lists, as collect_hypothesis_and_scores(n_best=1) gives them,
+        scores: [n_inst] ([n_active]) fp32 tensor of the best beams' accumulated log-probabilities)."""
+        res = self.decode(sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=max_len, n_best=1,
+                          n_active=n_active)
         return [h[0] for h in res.hypotheses()], res.scores[:, 0].clone()

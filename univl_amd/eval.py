@@ -1,8 +1,17 @@
-"""Retrieval evaluation helpers: the device-resident equivalent of main_task_retrieval.py:367-450 (`_run_on_single_gpu`,
+"""Evaluation entry points for callers that can be edited: eval_retrieval and eval_caption (below).
+
+Retrieval: the device-resident equivalent of main_task_retrieval.py:367-450 (`_run_on_single_gpu`,
 `eval_epoch`) for callers that can be edited.  The unchanged script keeps working through UniVL.get_* and
 nn.parallel.replicate (tests/test_eval_gpu.py); these helpers avoid its per-block D2H copies and numpy concatenations:
 all blocks of the N_t x N_v similarity matrix are written into one device tensor and the metrics need 2 N integers
-from the GPU (univl_amd.metrics)."""
+from the GPU (univl_amd.metrics).
+
+Caption: eval_caption is the body of main_task_caption.py:490-618 (`eval_epoch`) around ONE decoding session
+(univl_amd.decode.CaptionBeamSearch) that every batch of the loader reuses, the short last one included (n_active); the
+reference's cut of each hypothesis at "[SEP]" / "[PAD]" runs on the device (univl_beam_captions) and each batch is copied to the
+host once."""
+import os
+
 import torch
 
 from .metrics import compute_metrics
@@ -43,3 +52,90 @@ def eval_retrieval(model, batches, device="cuda"):
     sim = similarity_matrix(model, masks_t, masks_v, seqs, viss)
     model.train(was_training)
     return compute_metrics(sim), sim
+
+
+def ids_to_caption(tokenizer, ids):
+    """Token ids -> caption text, exactly as main_task_caption.py:554-562 (hypotheses) and :566-574 (ground truth) do it: cut at
+    the first "[SEP]", then at the first "[PAD]", join with ' ', glue "##" pieces.  (`.strip("##")` strips the CHARACTER '#' from
+    both ends, as the reference does.)"""
+    toks = tokenizer.convert_ids_to_tokens([int(i) for i in ids])
+    if "[SEP]" in toks:
+        toks = toks[:toks.index("[SEP]")]
+    if "[PAD]" in toks:
+        toks = toks[:toks.index("[PAD]")]
+    return ' '.join(toks).replace(" ##", "").strip("##").strip()
+
+
+class CaptionEvalResult:
+    """What eval_caption returns.  Items are in loader order.
+      hyps     list[str]             the best hypothesis of every item (what the reference writes to hyp.txt)
+      refs     list[str]             pairs_output_caption_ids through the same id-to-text rule: the SINGLE-reference list.  The
+                                     MSRVTT regrouping of main_task_caption.py:599-607 needs the dataset object and is the caller's.
+      hyp_ids  list[list[list[int]]] [item][k] token ids of the k-th best hypothesis after the "[SEP]" / "[PAD]" cut, k < n_best
+      scores   [items, n_best] fp32  accumulated log-probabilities, non-increasing in k (host tensor)
+      lengths  [items] int32         generated tokens per item, before the cut (host tensor)
+      metrics  nlg_eval.compute_metrics(ref_list=[refs], hyp_list=hyps), or None without nlg_eval
+      session  the CaptionBeamSearch that decoded every batch (None for a stage-one model)
+    float(result) is metrics["Bleu_4"] (the reference's return value), 0.0 without metrics."""
+
+    def __init__(self, hyps, refs, hyp_ids, scores, lengths, metrics, session):
+        self.hyps, self.refs, self.hyp_ids, self.scores, self.lengths = hyps, refs, hyp_ids, scores, lengths
+        self.metrics, self.session = metrics, session
+
+    def __float__(self):
+        return float(self.metrics["Bleu_4"]) if self.metrics else 0.0
+
+
+@torch.no_grad()
+def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, session=None, output_dir=None, nlg_eval=None,
+                 device="cuda"):
+    """Caption evaluation over a loader (main_task_caption.py:490-618).  batches: the reference loader's 12-tuples (:504-506);
+    tokenizer: any object with vocab["[CLS]"], vocab["[SEP]"], vocab["[PAD]"] and convert_ids_to_tokens.  One CaptionBeamSearch,
+    sized by the first batch (or the `session` passed in), decodes every batch; a smaller batch runs with n_active, a larger one is
+    a ValueError.  max_len: positions decoded per batch (default: the model's max_words, the reference's bound).  output_dir:
+    hyp.txt and ref.txt are written there as :588-597 writes them.  nlg_eval: optional metric object (NLGEval).
+    Returns a CaptionEvalResult; for a stage-one model an empty one (float() == 0.0, :495) without decoding anything."""
+    from .decode import CaptionBeamSearch
+    if model._stage_one:
+        return CaptionEvalResult([], [], [], torch.zeros(0, n_best), torch.zeros(0, dtype=torch.int32), None, None)
+    bos, eos, pad = tokenizer.vocab["[CLS]"], tokenizer.vocab["[SEP]"], tokenizer.vocab["[PAD]"]
+    was_training = model.training
+    model.eval()
+    hyps, refs, hyp_ids, scores, lengths = [], [], [], [], []
+    try:
+        for batch in batches:
+            input_ids, input_mask, segment_ids, video, video_mask = [t.to(device, non_blocking=True) for t in batch[:5]]
+            so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
+            n = int(so.shape[0])
+            if session is None:
+                session = CaptionBeamSearch(model, n, so.shape[1], vo.shape[1], n_bm=n_bm, max_len=max_len)
+            if n > session.n_inst:
+                raise ValueError("eval_caption: a batch of %d items does not fit the decoding session's %d instances"
+                                 % (n, session.n_inst))
+            res = session.decode(so, vo, input_mask, video_mask, bos, eos, max_len=max_len, n_best=n_best,
+                                 n_active=None if n == session.n_inst else n)
+            cap, cap_len = res.captions(eos, pad)
+            # the one host copy of the batch: tokens, cut lengths, scores and lengths
+            cap, cap_len, sc, ln = cap.cpu().tolist(), cap_len.cpu().tolist(), res.scores.cpu(), res.lengths.cpu()
+            for i in range(n):
+                ids = [cap[i][k][:cap_len[i][k]] for k in range(n_best)]
+                hyp_ids.append(ids)
+                hyps.append(ids_to_caption(tokenizer, ids[0]))
+            scores.append(sc)
+            lengths.append(ln)
+            truth = batch[11]
+            for row in truth.reshape(-1, truth.shape[-1]).cpu().tolist():
+                refs.append(ids_to_caption(tokenizer, row))
+    finally:
+        model.train(was_training)
+    if output_dir is not None:
+        with open(os.path.join(output_dir, "hyp.txt"), "w", encoding="utf-8") as writer:
+            for txt in hyps:
+                writer.write(txt + "\n")
+        with open(os.path.join(output_dir, "ref.txt"), "w", encoding="utf-8") as writer:
+            for txt in refs:
+                writer.write(txt + "\n")
+    metrics = nlg_eval.compute_metrics(ref_list=[refs], hyp_list=hyps) if nlg_eval is not None else None
+    scores = torch.cat(scores) if scores else torch.zeros(0, n_best)
+    lengths = torch.cat(lengths) if lengths else torch.zeros(0, dtype=torch.int32)
+    return CaptionEvalResult(hyps, refs, hyp_ids, scores, lengths, metrics, session)

@@ -400,6 +400,24 @@ def beam_backtrack(hist_parents, hist_tokens, scores, length, n_best):
     return hyp, hs
 
 
+def beam_captions(hyp, length, eos, pad, *, eos_dev=None, out=None):
+    """The reference's caption cut on the device (include/univl_hip.h: univl_beam_captions).  hyp: [n, n_best, Tmax] int32 as
+    beam_backtrack returns it, length: [n] int32; eos / pad: token ids, negative for none; eos_dev: optional int32 device word read
+    instead of eos; out: the cap_tokens buffer (hyp itself for the cut in place; default a new tensor).
+    Returns (cap_tokens [n, n_best, Tmax] int32, -1 past the cut; cap_len [n, n_best] int32)."""
+    _require_gpu(hyp, length, eos_dev, out)
+    assert hyp.dtype == torch.int32 and hyp.dim() == 3 and hyp.is_contiguous()
+    n, n_best, Tmax = hyp.shape
+    assert length.dtype == torch.int32 and length.numel() == n and length.is_contiguous()
+    assert eos_dev is None or eos_dev.dtype == torch.int32
+    cap = torch.empty_like(hyp) if out is None else out
+    assert cap.dtype == torch.int32 and cap.shape == hyp.shape and cap.is_contiguous()
+    cap_len = torch.empty(n, n_best, dtype=torch.int32, device=hyp.device)
+    _lib.check(_lib.lib().univl_beam_captions(_p(hyp), _p(length), n, n_best, Tmax, int(eos), int(pad), _p(eos_dev), _p(cap), _p(cap_len),
+                                              _stream()), "beam_captions")
+    return cap, cap_len
+
+
 def rank_counts(sim):
     """sim: [n, n] fp32 device tensor (row stride >= n).  Returns (gt, eq) int32 [n]."""
     _require_gpu(sim)

@@ -539,11 +539,16 @@ class RowFeatures:
         self.amask, self.vmask = e(Bt, W, dtype=torch.int64), e(Bv, F, dtype=torch.int64)
         self.dseq, self.dvis = None, None
 
-    def load(self, seq, vis, amask, vmask):
-        self.seq_out.copy_(seq.reshape(self.seq_out.shape), non_blocking=True)
-        self.vis_out.copy_(vis.reshape(self.vis_out.shape), non_blocking=True)
-        self.amask.copy_(amask.reshape(self.amask.shape), non_blocking=True)
-        self.vmask.copy_(vmask.reshape(self.vmask.shape), non_blocking=True)
+    def load(self, seq, vis, amask, vmask, rows=None):
+        """rows: fill the first `rows` text and video slots only (a partial batch; the other slots keep their contents)."""
+        if rows is None:
+            so, vo, am, vm = self.seq_out, self.vis_out, self.amask, self.vmask
+        else:
+            so, vo, am, vm = self.seq_out[:rows * self.W], self.vis_out[:rows * self.F], self.amask[:rows], self.vmask[:rows]
+        so.copy_(seq.reshape(so.shape), non_blocking=True)
+        vo.copy_(vis.reshape(vo.shape), non_blocking=True)
+        am.copy_(amask.reshape(am.shape), non_blocking=True)
+        vm.copy_(vmask.reshape(vm.shape), non_blocking=True)
 
 
 class DecoderRun:
