@@ -37,7 +37,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 const char* univl_last_error(void);
 int univl_version(void);
-/* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE, 8 BeamStep) -- lets a
+/* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE, 8 BeamStep, 9 SimTopk) -- lets a
  * foreign-language binding verify its struct mirrors at load time */
 int univl_struct_size(int which);
 /* number of CUs / name of the current device, for host-side launch heuristics; returns 0 or hipError_t */
@@ -411,6 +411,48 @@ int univl_beam_backtrack(const int32_t* hist_parents, const int32_t* hist_tokens
  * 1 <= n_best <= UNIVL_BEAM_MAX, n_inst >= 1, Tmax >= 1, otherwise UNIVL_EINVAL. */
 int univl_beam_captions(const int32_t* hyp, const int32_t* length, int32_t n_inst, int32_t n_best, int32_t Tmax, int32_t eos, int32_t pad,
                         const int32_t* eos_dev, int32_t* cap_tokens, int32_t* cap_len, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- retrieval search
+ * The k best gallery rows of every query row by inner product -- torch.matmul(text, video.t()) of modeling.py:389 followed by a
+ * row-wise top-k -- WITHOUT the [Nq, Ng] score matrix: the 768-deep product's epilogue keeps a running top-k per query and never
+ * writes the tile (the pattern of univl_vocab_ce_fwd).  Two launches, no host read, capturable:
+ *   scan   grid (query tiles of 16 / 32 rows, gallery slices), 512 threads: the query tile stays in LDS, gallery tiles of 128 rows are
+ *          streamed from global memory into f32 MFMA operands (fp32 accumulate); every score is tested against the query's current
+ *          k-th entry before any insert; a slice's sorted k best and its partial counts go to the workspace;
+ *   merge  one wave per query row over the slices' lists.
+ * Outputs, per query row i:  idx[i, 0..k) / score[i, 0..k) = the k best gallery rows, sorted by DESCENDING score.  TIE RULE (the one
+ * univl_beam_step fixes, part of the contract): equal fp32 scores are ordered by LOWER gallery index first.  With Ng < k the entries
+ * Ng .. k-1 are idx = -1, score = -inf.  Behaviour on NaN values: unspecified.
+ * Rank counts (optional): with target ([Nq] int32, each in [0, Ng); a value outside is not refused -- the device cannot report it --
+ * but CLAMPED to that range, so the counts are then those of row 0 or Ng - 1 and nothing is read outside the gallery) also
+ *   gt[i] = #{j : s(i, j) > s(i, target[i])},   eq[i] = #{j : s(i, j) == s(i, target[i])}  (>= 1: the target itself)
+ * -- the two counts of univl_rank_counts for an ARBITRARY ground-truth column, so several queries may share a gallery row and
+ * Nq != Ng is allowed.  k = 0 produces the counts only (idx / score may be NULL) and needs target.
+ * SCORE CONTRACT: s(i, j) is a pure function of the 768 values of q_i and g_j -- one fixed fp32 accumulation chain.  Its bits do not
+ * depend on Nq, Ng, the row's position in a tile, the slice count or deterministic mode; there are no float atomics and no
+ * order-dependent reduction across workgroups.  Equality of scores is therefore meaningful (tie rule, eq), and a gallery searched in
+ * pieces merges exactly: sort the pieces' results by (score descending, global index ascending).
+ * Range: H == 768 (as univl_pool_fwd), Nq >= 1, Ng >= 1, 0 <= k <= UNIVL_TOPK_MAX, ldq / ldg >= H, 0 <= slices <=
+ * UNIVL_TOPK_SLICES_MAX; otherwise, for a NULL pointer, for k == 0 without target or for a workspace that is too small, UNIVL_EINVAL.
+ * Rows of q and g (base and leading dimension) and the workspace must be 16-byte aligned (UNIVL_EALIGN).
+ * WORKSPACE: Nq * S * (8 * k + 8) bytes, S = the number of slices the call uses:  with T = ceil(Ng / 128) gallery tiles and
+ * QT = ceil(Nq / (Nq <= 16 ? 16 : 32)) query tiles,  want = slices ? slices : ceil(256 / QT)  (query tiles x slices fills the 256
+ * compute units once),  want = min(want, UNIVL_TOPK_SLICES_MAX, T),  S = ceil(T / ceil(T / want)).  univl_sim_topk_workspace
+ * evaluates this on the host (no device work; < 0 for arguments univl_sim_topk would refuse). */
+#define UNIVL_TOPK_MAX 64
+#define UNIVL_TOPK_SLICES_MAX 256
+typedef struct UnivlSimTopk {
+    const float* q; int64_t ldq;     /* [Nq, ldq] fp32 queries                                                                    */
+    const float* g; int64_t ldg;     /* [Ng, ldg] fp32 gallery                                                                    */
+    int32_t Nq, Ng, H, k;            /* H must be 768; k = 0: rank counts only                                                    */
+    int32_t slices;                  /* 0: the library chooses; 1 .. UNIVL_TOPK_SLICES_MAX: forced (capped at the tile count)     */
+    int32_t reserved;                /* 0                                                                                          */
+    int32_t* idx; float* score;      /* [Nq, k] each, written (k > 0)                                                             */
+    const int32_t* target;           /* optional [Nq]: the ground-truth gallery row of every query                                */
+    int32_t* gt; int32_t* eq;        /* [Nq] each, written when target is given                                                   */
+    void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch, see WORKSPACE                                                    */
+} UnivlSimTopk;
+int univl_sim_topk(const UnivlSimTopk* d, hipStream_t stream);
+int64_t univl_sim_topk_workspace(int32_t Nq, int32_t Ng, int32_t k, int32_t slices);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

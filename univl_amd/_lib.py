@@ -76,9 +76,15 @@ class BeamStep(C.Structure):
                 ("hist_tokens", vp), ("hist_scores", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
-BEAM_MAX, BEAM_SLICES = 8, 8       # include/univl_hip.h: UNIVL_BEAM_MAX, UNIVL_BEAM_SLICES
+class SimTopk(C.Structure):
+    _fields_ = [("q", vp), ("ldq", i64), ("g", vp), ("ldg", i64), ("Nq", i32), ("Ng", i32), ("H", i32), ("k", i32), ("slices", i32),
+                ("reserved", i32), ("idx", vp), ("score", vp), ("target", vp), ("gt", vp), ("eq", vp), ("ws", vp), ("ws_bytes", i64)]
 
-_STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep]
+
+BEAM_MAX, BEAM_SLICES = 8, 8       # include/univl_hip.h: UNIVL_BEAM_MAX, UNIVL_BEAM_SLICES
+TOPK_MAX, TOPK_SLICES_MAX = 64, 256   # include/univl_hip.h: UNIVL_TOPK_MAX, UNIVL_TOPK_SLICES_MAX
+
+_STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk]
 _lib = None
 
 
@@ -103,7 +109,7 @@ def lib():
             raise RuntimeError("ABI mismatch for %s: library %d bytes, ctypes %d" % (st.__name__, n, C.sizeof(st)))
     for name in ("univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_gemm", "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd",
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
-                 "univl_pool_bwd", "univl_bert_adam", "univl_beam_step"):
+                 "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_pool_pair_fwd.argtypes = [vp, vp, vp]
@@ -137,6 +143,8 @@ def lib():
     L.univl_beam_captions.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     L.univl_beam_captions.restype = i32
     L.univl_rank_counts.argtypes = [vp, i32, i64, vp, vp, vp]
+    L.univl_sim_topk_workspace.argtypes = [i32, i32, i32, i32]
+    L.univl_sim_topk_workspace.restype = i64
     L.univl_scale_by_device_scalar.argtypes = [vp, i64, vp, vp]
     L.univl_pair_concat_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.univl_pair_concat_bwd.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
@@ -188,7 +196,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_dev
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

@@ -32,6 +32,7 @@ extern "C" int univl_struct_size(int which) {
         case 6: return (int)sizeof(UnivlAdam);
         case 7: return (int)sizeof(UnivlVocabCE);
         case 8: return (int)sizeof(UnivlBeamStep);
+        case 9: return (int)sizeof(UnivlSimTopk);
         default: return -1;
     }
 }

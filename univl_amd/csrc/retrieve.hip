@@ -1,0 +1,301 @@
+// Retrieval search on the device (include/univl_hip.h: univl_sim_topk): the k best gallery rows of every query row by inner product,
+// and optionally the two rank counts of univl_rank_counts against an arbitrary target column, without the [Nq, Ng] score matrix.
+//
+// Two launches, no host read, capturable:
+//   scan   grid (query tiles, gallery slices), 512 threads = 8 waves.  The query tile (16 or 32 rows x 768 fp32, pitch 772) is staged into
+//          LDS once; the workgroup then walks its slice of the gallery in tiles of 128 rows.  Wave w owns gallery rows 16 w .. 16 w + 15 of
+//          the tile and reads them STRAIGHT from global memory into MFMA operand fragments (lane (i, g) reads 16 bytes of row i at
+//          k = 16 c + 4 g: a 64-byte piece per row and instruction, eight chunks = 512 contiguous bytes per row in flight, double buffered
+//          in registers), the query fragments come from LDS.  One tile's scores go through a [queries][128] LDS buffer (two of them, so
+//          that one barrier per tile is enough) to the wave that owns the query: waves keep 2 or 4 queries each, a query's running top-64
+//          list is ONE ENTRY PER LANE of that wave, sorted.  Every score is compared with the query's current k-th entry first; the few
+//          that pass are inserted one by one (ballot -> position, one shuffle to shift the tail).  The slice's k best and its counts go to
+//          the workspace.
+//   merge  one wave per query: the same insert over the slices' lists, then idx / score / gt / eq.
+//
+// SCORE CONTRACT.  s(i, j) is one accumulator chain: 48 chunks of 16 contraction indices in ascending order, 4 x v_mfma_f32_16x16x4_f32
+// per chunk, starting from zero.  Neither the tile position of the row, the slice, the number of query blocks (16 / 32 row tiles run the
+// same chain) nor deterministic mode enters it, and the target's score is computed by the same chain on gathered rows -- so equality of
+// scores is meaningful (tie rule, eq) and pieces of a gallery searched separately merge exactly.  No float atomics anywhere.
+// Order everywhere: larger score first, equal scores by LOWER gallery index first (`better`).
+#include <limits.h>
+#include "common.h"
+#include "univl_hip.h"
+
+namespace {
+
+constexpr int RT_H = 768;                   // contraction width (the pooled hidden size)
+constexpr int RT_PITCH = RT_H + 4;          // LDS pitch of a query row: the 16 rows of a fragment read land in distinct banks
+constexpr int RT_TILE = 128;                // gallery rows per tile = 8 waves x 16
+constexpr int RT_SCP = RT_TILE + 4;         // pitch of the score buffer
+constexpr int RT_NONE = INT_MAX;            // index of an empty list slot; loses against every real entry of any value
+constexpr int RT_WGS = 256;                 // workgroups the automatic slice count aims for (one per compute unit)
+
+__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
+
+// (lv, li): this lane's entry of a wave-wide list sorted best first.  Inserts the wave-uniform candidate; the last entry falls off.
+__device__ __forceinline__ void list_insert(float& lv, int& li, float cv, int ci, int lane) {
+    const int pos = __popcll(__ballot(better(lv, li, cv, ci)));      // the entries that stay in front of it are a prefix
+    const float uv = __shfl_up(lv, 1, 64);
+    const int ui = __shfl_up(li, 1, 64);
+    if (lane == pos) { lv = cv; li = ci; }
+    else if (lane > pos) { lv = uv; li = ui; }
+}
+
+// Offers every lane's (v, base + lane) with ok != 0 to the list: tested against the k-th entry BEFORE any insert, and again when its turn comes.
+__device__ __forceinline__ void list_offer(float& lv, int& li, int k, float v, int base, bool ok, int lane) {
+    float kv = __shfl(lv, k - 1, 64);
+    int ki = __shfl(li, k - 1, 64);
+    unsigned long long m = __ballot(ok && better(v, base + lane, kv, ki));
+    while (m) {                                                       // wave-uniform
+        const int b = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const float cv = __shfl(v, b, 64);
+        const int ci = base + b;
+        if (better(cv, ci, kv, ki)) {
+            list_insert(lv, li, cv, ci, lane);
+            kv = __shfl(lv, k - 1, 64);
+            ki = __shfl(li, k - 1, 64);
+        }
+    }
+}
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct ScanArgs {
+    const float* q; long ldq;
+    const float* g; long ldg;
+    int Nq, Ng, k, tiles, tps, S;          // tiles of the gallery, tiles per slice, slices
+    const int32_t* target;
+    float* ws_val; int32_t* ws_idx; int32_t* ws_cnt;     // [Nq][S][k], [Nq][S][k], [Nq][S][2]
+};
+
+__device__ __forceinline__ void load8(f32x4_t (&f)[8], const float* p) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) f[c] = *reinterpret_cast<const f32x4_t*>(p + 16 * c);
+}
+
+// NQB: blocks of 16 queries per workgroup
+template <int NQB>
+__global__ __launch_bounds__(512) void sim_topk_scan_kernel(ScanArgs a) {
+    constexpr int QT = 16 * NQB, NQW = QT / 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char rt_smem[];
+    float* qs = reinterpret_cast<float*>(rt_smem);                   // [QT][RT_PITCH]
+    float* sc = qs + QT * RT_PITCH;                                   // [2][QT][RT_SCP]
+    float* tsc = sc + 2 * QT * RT_SCP;                                // [QT] target scores
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, gg = lane >> 4;
+    const int q0 = blockIdx.x * QT, slice = blockIdx.y;
+
+    for (int e = tid; e < QT * (RT_H / 4); e += 512) {
+        const int r = e / (RT_H / 4), c4 = e % (RT_H / 4);
+        f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+        if (q0 + r < a.Nq) v = *reinterpret_cast<const f32x4_t*>(a.q + (long)(q0 + r) * a.ldq + 4 * c4);
+        *reinterpret_cast<f32x4_t*>(qs + r * RT_PITCH + 4 * c4) = v;
+    }
+    __syncthreads();
+
+    // s(query, target[query]) by the chain of the main loop: wave w takes query block w against the gathered target rows; the
+    // diagonal of its 16 x 16 tile sits in lane i + 16 (i / 4), register i % 4
+    if (a.target != nullptr) {
+        if (wave < NQB) {
+            const int tq = q0 + 16 * wave + i;
+            int tr = tq < a.Nq ? a.target[tq] : 0;
+            tr = tr < 0 ? 0 : (tr >= a.Ng ? a.Ng - 1 : tr);          // a target out of range must not read outside the gallery
+            const float* gp = a.g + (long)tr * a.ldg + 4 * gg;
+            const float* qp = qs + (16 * wave + i) * RT_PITCH + 4 * gg;
+            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < RT_H / 16; ++c)
+                acc = Mma<float>::mma(*reinterpret_cast<const f32x4_t*>(gp + 16 * c), *reinterpret_cast<const f32x4_t*>(qp + 16 * c), acc);
+            if (gg == (i >> 2)) {
+                const int r = i & 3;
+                tsc[16 * wave + i] = r == 0 ? acc[0] : (r == 1 ? acc[1] : (r == 2 ? acc[2] : acc[3]));
+            }
+        }
+        __syncthreads();
+    }
+
+    float lv[NQW], tv[NQW];
+    int li[NQW], cgt[NQW], ceq[NQW];
+#pragma unroll
+    for (int u = 0; u < NQW; ++u) {
+        lv[u] = -INFINITY; li[u] = RT_NONE; cgt[u] = 0; ceq[u] = 0;
+        tv[u] = a.target != nullptr ? tsc[wave * NQW + u] : 0.f;
+    }
+
+    const int t0 = slice * a.tps, t1 = min(a.tiles, t0 + a.tps);
+    const long last = a.Ng - 1;
+    // rows past the gallery's end read its last row (a valid address); their scores are never offered or counted
+    const float* gp = a.g + min((long)t0 * RT_TILE + 16 * wave + i, last) * a.ldg + 4 * gg;
+    f32x4_t cur[8], nxt[8];
+    load8(cur, gp);
+    for (int t = t0; t < t1; ++t) {
+        const float* gpn = a.g + min((long)(t + 1) * RT_TILE + 16 * wave + i, last) * a.ldg + 4 * gg;
+        f32x4_t acc[NQB];
+#pragma unroll
+        for (int b = 0; b < NQB; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kg = 0; kg < RT_H / 128; ++kg) {
+            load8(nxt, kg + 1 < RT_H / 128 ? gp + 128 * (kg + 1) : gpn);       // the next 8 chunks (of the next tile after the last group)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+#pragma unroll
+                for (int b = 0; b < NQB; ++b) {
+                    const f32x4_t qf = *reinterpret_cast<const f32x4_t*>(qs + (16 * b + i) * RT_PITCH + 128 * kg + 16 * c + 4 * gg);
+                    acc[b] = Mma<float>::mma(cur[c], qf, acc[b]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) cur[c] = nxt[c];
+        }
+        gp = gpn;
+        // accumulator (lane (i, g), register r) = gallery row 16 w + 4 g + r of the tile, query 16 b + i
+        float* scb = sc + (t & 1) * QT * RT_SCP;
+#pragma unroll
+        for (int b = 0; b < NQB; ++b) *reinterpret_cast<f32x4_t*>(scb + (16 * b + i) * RT_SCP + 16 * wave + 4 * gg) = acc[b];
+        __syncthreads();             // the other buffer is rewritten only after the NEXT barrier
+        const int j0 = t * RT_TILE;
+#pragma unroll
+        for (int u = 0; u < NQW; ++u) {
+            const float* row = scb + (wave * NQW + u) * RT_SCP;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float s = row[64 * h + lane];
+                const bool ok = j0 + 64 * h + lane < a.Ng;
+                if (a.target != nullptr) {
+                    cgt[u] += (ok && s > tv[u]) ? 1 : 0;
+                    ceq[u] += (ok && s == tv[u]) ? 1 : 0;
+                }
+                if (a.k > 0) list_offer(lv[u], li[u], a.k, s, j0 + 64 * h, ok, lane);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int u = 0; u < NQW; ++u) {
+        const int qrow = q0 + wave * NQW + u;
+        if (qrow >= a.Nq) continue;                                   // wave-uniform
+        const long slot = (long)qrow * a.S + slice;
+        if (lane < a.k) { a.ws_val[slot * a.k + lane] = lv[u]; a.ws_idx[slot * a.k + lane] = li[u]; }
+        if (a.target != nullptr) {
+            const int ngt = wave_sum_i(cgt[u]), neq = wave_sum_i(ceq[u]);
+            if (lane == 0) { a.ws_cnt[slot * 2] = ngt; a.ws_cnt[slot * 2 + 1] = neq; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void sim_topk_merge_kernel(const float* __restrict__ ws_val, const int32_t* __restrict__ ws_idx,
+                                                            const int32_t* __restrict__ ws_cnt, int S, int k, int counts,
+                                                            int32_t* __restrict__ idx, float* __restrict__ score, int32_t* __restrict__ gt,
+                                                            int32_t* __restrict__ eq) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    if (k > 0) {
+        float lv = -INFINITY;
+        int li = RT_NONE;
+        for (int s = 0; s < S; ++s) {
+            const long at = ((long)row * S + s) * k + lane;
+            const float v = lane < k ? ws_val[at] : -INFINITY;
+            const int j = lane < k ? ws_idx[at] : RT_NONE;
+            // list_offer numbers its candidates base + lane; here every lane brings its own index, so the loop is spelled out
+            float kv = __shfl(lv, k - 1, 64);
+            int ki = __shfl(li, k - 1, 64);
+            unsigned long long m = __ballot(j != RT_NONE && better(v, j, kv, ki));
+            while (m) {
+                const int b = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const float cv = __shfl(v, b, 64);
+                const int ci = __shfl(j, b, 64);
+                if (better(cv, ci, kv, ki)) {
+                    list_insert(lv, li, cv, ci, lane);
+                    kv = __shfl(lv, k - 1, 64);
+                    ki = __shfl(li, k - 1, 64);
+                }
+            }
+        }
+        if (lane < k) {
+            idx[(long)row * k + lane] = li == RT_NONE ? -1 : li;
+            score[(long)row * k + lane] = li == RT_NONE ? -INFINITY : lv;
+        }
+    }
+    if (counts) {
+        int ngt = 0, neq = 0;
+        for (int s = lane; s < S; s += 64) { ngt += ws_cnt[((long)row * S + s) * 2]; neq += ws_cnt[((long)row * S + s) * 2 + 1]; }
+        ngt = wave_sum_i(ngt); neq = wave_sum_i(neq);
+        if (lane == 0) { gt[row] = ngt; eq[row] = neq; }
+    }
+}
+
+struct Plan { int nqb, qtiles, tiles, tps, S; };
+
+Plan make_plan(int Nq, int Ng, int slices) {
+    Plan p;
+    p.nqb = Nq <= 16 ? 1 : 2;
+    p.qtiles = (Nq + 16 * p.nqb - 1) / (16 * p.nqb);
+    p.tiles = (Ng + RT_TILE - 1) / RT_TILE;
+    // automatic: query tiles x slices fills the chip once -- a workgroup owns a compute unit's LDS, so a second round would only queue
+    int want = slices > 0 ? slices : (RT_WGS + p.qtiles - 1) / p.qtiles;
+    want = want > UNIVL_TOPK_SLICES_MAX ? UNIVL_TOPK_SLICES_MAX : want;
+    want = want > p.tiles ? p.tiles : want;
+    p.tps = (p.tiles + want - 1) / want;
+    p.S = (p.tiles + p.tps - 1) / p.tps;                              // no empty slice
+    return p;
+}
+
+template <int NQB>
+void launch_scan(const ScanArgs& a, const Plan& p, hipStream_t stream) {
+    constexpr size_t smem = ((size_t)16 * NQB * RT_PITCH + (size_t)2 * 16 * NQB * RT_SCP + 16 * NQB) * sizeof(float);
+    static bool done[UNIVL_MAX_DEVICES] = {};
+    univl_allow_lds(sim_topk_scan_kernel<NQB>, smem, done);
+    hipLaunchKernelGGL(sim_topk_scan_kernel<NQB>, dim3(p.qtiles, p.S), dim3(512), smem, stream, a);
+}
+
+}  // namespace
+
+extern "C" int64_t univl_sim_topk_workspace(int32_t Nq, int32_t Ng, int32_t k, int32_t slices) {
+    if (Nq < 1 || Ng < 1 || k < 0 || k > UNIVL_TOPK_MAX || slices < 0 || slices > UNIVL_TOPK_SLICES_MAX || Ng > INT_MAX - 2 * RT_TILE) {
+        univl_set_error("univl_sim_topk_workspace: Nq=%d Ng=%d k=%d slices=%d", Nq, Ng, k, slices);
+        return UNIVL_EINVAL;
+    }
+    const Plan p = make_plan(Nq, Ng, slices);
+    return (int64_t)Nq * p.S * (8 * (int64_t)k + 8);
+}
+
+extern "C" int univl_sim_topk(const UnivlSimTopk* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_sim_topk: null descriptor");
+    UNIVL_CHECK_ARG(d->H == RT_H, UNIVL_EINVAL, "univl_sim_topk: H=%d (must be 768)", d->H);
+    UNIVL_CHECK_ARG(d->Nq >= 1 && d->Ng >= 1 && d->Ng <= INT_MAX - 2 * RT_TILE, UNIVL_EINVAL, "univl_sim_topk: Nq=%d Ng=%d (both >= 1)", d->Nq, d->Ng);
+    UNIVL_CHECK_ARG(d->k >= 0 && d->k <= UNIVL_TOPK_MAX, UNIVL_EINVAL, "univl_sim_topk: k=%d (0 <= k <= %d)", d->k, UNIVL_TOPK_MAX);
+    UNIVL_CHECK_ARG(d->k > 0 || d->target != nullptr, UNIVL_EINVAL, "univl_sim_topk: k = 0 asks for the rank counts only and needs target");
+    UNIVL_CHECK_ARG(d->slices >= 0 && d->slices <= UNIVL_TOPK_SLICES_MAX, UNIVL_EINVAL, "univl_sim_topk: slices=%d (0 = automatic, at most %d)",
+                    d->slices, UNIVL_TOPK_SLICES_MAX);
+    UNIVL_CHECK_ARG(d->q && d->g && d->ws, UNIVL_EINVAL, "univl_sim_topk: null pointer (q, g, ws)");
+    UNIVL_CHECK_ARG(d->k == 0 || (d->idx && d->score), UNIVL_EINVAL, "univl_sim_topk: null pointer (idx, score)");
+    UNIVL_CHECK_ARG(d->target == nullptr || (d->gt && d->eq), UNIVL_EINVAL, "univl_sim_topk: null pointer (gt, eq with target)");
+    UNIVL_CHECK_ARG(d->ldq >= RT_H && d->ldg >= RT_H, UNIVL_EINVAL, "univl_sim_topk: ldq=%lld ldg=%lld (both >= 768)", (long long)d->ldq,
+                    (long long)d->ldg);
+    UNIVL_CHECK_ARG(aligned16(d->q) && aligned16(d->g) && d->ldq % 4 == 0 && d->ldg % 4 == 0 && aligned16(d->ws), UNIVL_EALIGN,
+                    "univl_sim_topk: rows of q and g and the workspace must be 16-byte aligned");
+    const Plan p = make_plan(d->Nq, d->Ng, d->slices);
+    const int64_t need = (int64_t)d->Nq * p.S * (8 * (int64_t)d->k + 8);
+    UNIVL_CHECK_ARG(d->ws_bytes >= need, UNIVL_EINVAL, "univl_sim_topk: workspace of %lld bytes needed (univl_sim_topk_workspace), got %lld",
+                    (long long)need, (long long)d->ws_bytes);
+    ScanArgs a;
+    a.q = d->q; a.ldq = (long)d->ldq; a.g = d->g; a.ldg = (long)d->ldg;
+    a.Nq = d->Nq; a.Ng = d->Ng; a.k = d->k; a.tiles = p.tiles; a.tps = p.tps; a.S = p.S;
+    a.target = d->target;
+    const int64_t slots = (int64_t)d->Nq * p.S;
+    a.ws_val = static_cast<float*>(d->ws);
+    a.ws_idx = reinterpret_cast<int32_t*>(a.ws_val + slots * d->k);
+    a.ws_cnt = a.ws_idx + slots * d->k;
+    if (p.nqb == 1) launch_scan<1>(a, p, stream);
+    else launch_scan<2>(a, p, stream);
+    UNIVL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sim_topk_merge_kernel, dim3(d->Nq), dim3(64), 0, stream, a.ws_val, a.ws_idx, a.ws_cnt, p.S, d->k, d->target != nullptr ? 1 : 0,
+                       d->idx, d->score, d->gt, d->eq);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}

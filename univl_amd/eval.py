@@ -1,4 +1,4 @@
-"""Evaluation entry points for callers that can be edited: eval_retrieval and eval_caption (below).
+"""Evaluation entry points for callers that can be edited: eval_retrieval, eval_retrieval_streamed and eval_caption (below).
 
 Retrieval: the device-resident equivalent of main_task_retrieval.py:367-450 (`_run_on_single_gpu`,
 `eval_epoch`) for callers that can be edited.  The unchanged script keeps working through UniVL.get_* and
@@ -52,6 +52,42 @@ def eval_retrieval(model, batches, device="cuda"):
     sim = similarity_matrix(model, masks_t, masks_v, seqs, viss)
     model.train(was_training)
     return compute_metrics(sim), sim
+
+
+@torch.no_grad()
+def eval_retrieval_streamed(model, text_batches, video_batches, targets, device="cuda", capacity=1024):
+    """Retrieval metrics without the N_t x N_v matrix and without a paired test set.  video_batches: iterable of (video, video_mask);
+    text_batches: iterable of (input_ids, input_mask, segment_ids), the loader's order (main_task_retrieval.py:396); targets: for
+    every text row, in order, the gallery row (= position among all videos added) that is its ground truth -- several texts may name
+    one video, and the number of texts need not be the number of videos.  The videos go into a retrieval.VideoIndex, every text batch
+    is searched for its two rank counts only (univl_sim_topk with k = 0), and R@1 / R@5 / R@10 / MR come from the counts through
+    metrics.compute_metrics.  Joint-head similarity only (what VideoIndex holds).  Returns (metrics dict, (gt, eq) host arrays)."""
+    from .retrieval import VideoIndex
+    was_training = model.training
+    model.eval()
+    try:
+        index = VideoIndex(model, capacity=capacity)
+        for video, video_mask in video_batches:
+            index.add(video.to(device), video_mask.to(device))
+        targets = torch.as_tensor(targets).reshape(-1).to(device=device, dtype=torch.int32)
+        if targets.numel() and (int(targets.min()) < 0 or int(targets.max()) >= len(index)):
+            raise ValueError("eval_retrieval_streamed: targets must lie in [0, %d)" % len(index))
+        gts, eqs, row = [], [], 0
+        for batch in text_batches:
+            input_ids, input_mask, segment_ids = [t.to(device) for t in batch[:3]]
+            n = input_ids.numel() // input_ids.shape[-1]
+            if row + n > targets.numel():
+                raise ValueError("eval_retrieval_streamed: more text rows than targets (%d)" % targets.numel())
+            gt, eq = index.search(input_ids, segment_ids, input_mask, k=0, targets=targets[row:row + n])
+            gts.append(gt)
+            eqs.append(eq)
+            row += n
+        if row != targets.numel():
+            raise ValueError("eval_retrieval_streamed: %d text rows for %d targets" % (row, targets.numel()))
+    finally:
+        model.train(was_training)
+    gt, eq = torch.cat(gts).cpu().numpy(), torch.cat(eqs).cpu().numpy()
+    return compute_metrics((gt, eq)), (gt, eq)
 
 
 def ids_to_caption(tokenizer, ids):

@@ -11,18 +11,26 @@ import torch
 from . import ops
 
 
+def positions_from_counts(gt, eq):
+    """`ind` from the two counts per row (univl_rank_counts / univl_sim_topk): the diagonal -- or target -- score of row i sits at
+    positions range(gt[i], gt[i] + eq[i]) of the descending-sorted row.  gt / eq: integer arrays or tensors of one length."""
+    gt, eq = (np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t).astype(np.int64).reshape(-1) for t in (gt, eq))
+    if int(eq.max()) == 1:
+        return gt
+    return np.concatenate([np.arange(g, g + e) for g, e in zip(gt, eq)])
+
+
 def rank_positions(x):
-    """The reference's `ind` array (metrics.py:9-14), ties included, as a sorted-by-row int64 numpy array."""
+    """The reference's `ind` array (metrics.py:9-14), ties included, as a sorted-by-row int64 numpy array.  x: the similarity
+    matrix, or a (gt, eq) tuple of counts that something else already took (eval.eval_retrieval_streamed: no matrix exists)."""
+    if isinstance(x, tuple) and len(x) == 2:
+        return positions_from_counts(*x)
     if not isinstance(x, torch.Tensor):
         x = torch.as_tensor(np.ascontiguousarray(x))
     if not x.is_cuda:
         x = x.to("cuda")
     x = x.to(torch.float32).contiguous()
-    gt, eq = ops.rank_counts(x)
-    gt, eq = gt.cpu().numpy().astype(np.int64), eq.cpu().numpy().astype(np.int64)
-    if int(eq.max()) == 1:
-        return gt
-    return np.concatenate([np.arange(g, g + e) for g, e in zip(gt, eq)])
+    return positions_from_counts(*ops.rank_counts(x))
 
 
 def compute_metrics(x):

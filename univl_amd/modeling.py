@@ -903,6 +903,39 @@ class UniVL(UniVLPreTrainedModel):
         st.fwd.run(upto=st.fwd_encoders_len)
         return st.enc.seq_out.view(B, W, -1).clone(), st.enc.vis_out.view(B, F, -1).clone()
 
+    def _single_branch_step(self, kind, B, W, F):
+        """Flushes a pending optimizer update and refreshes the shadow exactly as get_sequence_visual_output does, then hands
+        out the eval-mode plan that builds ONE encoder stack (steps.EncoderPass(branches=...))."""
+        self._flush_pending()
+        self.flat.refresh_shadow()
+        was = self.training
+        self.training = False
+        try:
+            return self._get_step(kind, B, W, F)
+        finally:
+            self.training = was
+
+    def get_visual_output(self, video, video_mask, shaped=False):
+        """The video half of get_sequence_visual_output (modeling.py:299-313) alone: NormalizeVideo + VisualModel, the text stack
+        is neither built nor run.  Eval-only; `shaped` as there.  Returns [B, F, 768] fp32."""
+        F = video_mask.shape[-1]
+        B = video_mask.numel() // F
+        st = self._single_branch_step("features_vis_shaped" if shaped else "features_vis", B, 0, F)
+        st.enc.load_video(video, video_mask)
+        st.fwd.run(upto=st.fwd_encoders_len)
+        return st.enc.vis_out.view(B, F, -1).clone()
+
+    def get_sequence_output(self, input_ids, token_type_ids, attention_mask, shaped=False):
+        """The text half of get_sequence_visual_output alone: BertModel, the video stack is neither built nor run.  Eval-only;
+        `shaped` only says that the pair dimension is already flattened, which the reshape below does not need to know.
+        Returns [B, W, 768] fp32."""
+        W = input_ids.shape[-1]
+        B = input_ids.numel() // W
+        st = self._single_branch_step("features_text", B, W, 0)
+        st.enc.load_text(input_ids, token_type_ids, attention_mask)
+        st.fwd.run(upto=st.fwd_encoders_len)
+        return st.enc.seq_out.view(B, W, -1).clone()
+
     def get_similarity_logits(self, sequence_output, visual_output, attention_mask, video_mask, shaped=False,
                               _pretrain_joint=False):
         """modeling.py:377-391: cross-encoder similarity when stage two / train_sim_after_cross, else masked means,

@@ -429,6 +429,39 @@ def rank_counts(sim):
     return gt, eq
 
 
+def sim_topk(q, g, k, *, target=None, slices=0):
+    """The k best rows of g for every row of q by inner product, without the [Nq, Ng] matrix (include/univl_hip.h: univl_sim_topk).
+    q: [Nq, 768], g: [Ng, 768] fp32 row-major views (row stride >= 768, rows 16-byte aligned); 0 <= k <= TOPK_MAX; target: optional
+    [Nq] int32 gallery rows; slices: 0 = the library chooses.  Returns (scores [Nq, k] fp32 descending, indices [Nq, k] int32; equal
+    scores by lower index first, -inf / -1 past the gallery's end), followed by (gt, eq) int32 [Nq] -- the rank counts against
+    target -- when target is given.  k = 0: only (gt, eq)."""
+    _require_gpu(q, g, target)
+    assert q.dtype == torch.float32 and g.dtype == torch.float32 and q.dim() == 2 and g.dim() == 2
+    d = _lib.SimTopk()
+    d.q, d.ldq, d.g, d.ldg = _p(q), _ld(q), _p(g), _ld(g)
+    d.Nq, d.Ng, d.H, d.k, d.slices = q.shape[0], g.shape[0], q.shape[1], int(k), int(slices)
+    if g.shape[1] != q.shape[1]:
+        raise RuntimeError("sim_topk: q is %d wide, g %d" % (q.shape[1], g.shape[1]))
+    dev = q.device
+    need = _lib.lib().univl_sim_topk_workspace(d.Nq, d.Ng, d.k, d.slices)
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+    d.ws, d.ws_bytes = _p(ws), ws.numel()
+    idx = score = gt = eq = None
+    if d.k > 0:
+        idx = torch.empty(d.Nq, d.k, dtype=torch.int32, device=dev)
+        score = torch.empty(d.Nq, d.k, dtype=torch.float32, device=dev)
+        d.idx, d.score = _p(idx), _p(score)
+    if target is not None:
+        assert target.dtype == torch.int32 and target.numel() == d.Nq and target.is_contiguous()
+        gt = torch.empty(d.Nq, dtype=torch.int32, device=dev)
+        eq = torch.empty(d.Nq, dtype=torch.int32, device=dev)
+        d.target, d.gt, d.eq = _p(target), _p(gt), _p(eq)
+    _lib.check(_lib.lib().univl_sim_topk(_BYREF(d), _stream()), "sim_topk")     # refuses what the workspace query refused, with its message
+    if d.k == 0:
+        return gt, eq
+    return (score, idx) if target is None else (score, idx, gt, eq)
+
+
 def cast_bf16(src, dst):
     _lib.check(_lib.lib().univl_cast_bf16(_p(src), _p(dst), src.numel(), _stream()), "cast_bf16")
 

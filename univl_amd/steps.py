@@ -88,10 +88,17 @@ def stage_inputs(pairs):
 
 
 class EncoderPass:
-    """NormalizeVideo + BertModel + VisualModel for one set of inputs (modeling.py:196-202, 299-313)."""
+    """NormalizeVideo + BertModel + VisualModel for one set of inputs (modeling.py:196-202, 299-313).
+    branches: ("text", "vis") builds both stacks on two streams; ("text",) or ("vis",) builds and runs that stack alone on s_text
+    (UniVL.get_sequence_output / get_visual_output: forward only, the other stack's buffers and attributes are None)."""
 
-    def __init__(self, cx, B, W, F, s_text=0, s_vis=2, normalized_input=False):
+    def __init__(self, cx, B, W, F, s_text=0, s_vis=2, normalized_input=False, branches=("text", "vis")):
         self.cx, self.B, self.W, self.F = cx, B, W, F
+        self.branches = tuple(branches)
+        assert self.branches in (("text", "vis"), ("text",), ("vis",)), branches
+        if self.branches != ("text", "vis"):
+            self._init_single(cx, B, W, F, s_text, bool(normalized_input))
+            return
         self.normalized_input = bool(normalized_input)     # get_sequence_visual_output(shaped=True): video arrives normalised
         e, ct, bf, fl = cx.e, cx.ct, cx.bf, cx.fl
         D = cx.tc.video_dim
@@ -125,6 +132,44 @@ class EncoderPass:
         self.seq_out, self.seq_out16 = self.text.output()
         self.vis_out, self.vis_out16 = self.vis.output()
 
+    def _init_single(self, cx, B, W, F, stream, normalized_input):
+        """One stack, one stream, forward buffers only."""
+        self.normalized_input = normalized_input
+        e, ct, bf, fl, m = cx.e, cx.ct, cx.bf, cx.fl, cx.model
+        D = cx.tc.video_dim
+        self.D, self.Tt, self.Tv = D, B * W, B * F
+        self.ST = self.SV = stream
+        i64 = torch.int64
+        self.text = self.vis = self.seq_out = self.seq_out16 = self.vis_out = self.vis_out16 = None
+        self.t0_lo = self.v0_lo = self.vn_lo = None
+        if self.branches == ("text",):
+            self.ids, self.type_ids, self.amask = e(B, W, dtype=i64), e(B, W, dtype=i64), e(B, W, dtype=i64)
+            self.te, self.test, self.t0_32 = e(self.Tt, H), e(self.Tt, 2), e(self.Tt, H)
+            self.t0_16 = e(self.Tt, H, dtype=ct) if bf else self.t0_32
+            self.text = EncoderStack(fl, "bert", m.bert_config.num_hidden_layers, B, W, self.amask, cx.p, cx.seed_dev, cx.sites,
+                                     s_main=stream, s_side=stream)
+            self.off_t = cx.sites.next()
+            self.t0_lo = e(self.Tt, H, dtype=ct) if self.text.pair_x else None
+            self.seq_out, self.seq_out16 = self.text.output()
+        else:
+            self.video, self.vmask = e(B * F, D, dtype=torch.float64), e(B, F, dtype=i64)
+            self.vy, self.vst, self.vn32 = e(self.Tv, D), e(self.Tv, 2), e(self.Tv, D)
+            self.vn_op = e(self.Tv, D, dtype=ct) if bf else self.vn32
+            self.ve, self.vest, self.v0_32 = e(self.Tv, H), e(self.Tv, 2), e(self.Tv, H)
+            self.v0_16 = e(self.Tv, H, dtype=ct) if bf else self.v0_32
+            self.vis = EncoderStack(fl, "visual", m.visual_config.num_hidden_layers, B, F, self.vmask, cx.p, cx.seed_dev, cx.sites,
+                                    s_main=stream, s_side=stream)
+            self.off_v = cx.sites.next()
+            self.v0_lo = e(self.Tv, H, dtype=ct) if self.vis.pair_x else None
+            self.vn_lo = e(self.Tv, D, dtype=ct) if (self.vis.pair_x and not normalized_input) else None
+            self.vis_out, self.vis_out16 = self.vis.output()
+
+    def load_text(self, input_ids, token_type_ids, attention_mask):
+        stage_inputs([(self.ids, input_ids), (self.type_ids, token_type_ids), (self.amask, attention_mask)])
+
+    def load_video(self, video, video_mask):
+        stage_inputs([(self.vn32 if self.normalized_input else self.video, video), (self.vmask, video_mask)])
+
     N = dict(nv_g="normalize_video.visual_norm2d.weight", nv_b="normalize_video.visual_norm2d.bias",
              vw="visual.embeddings.word_embeddings.weight", vb="visual.embeddings.word_embeddings.bias",
              vpos="visual.embeddings.position_embeddings.weight", vlg="visual.embeddings.LayerNorm.weight",
@@ -141,37 +186,43 @@ class EncoderPass:
         cx, n, fl, dt, bf = self.cx, self.N, self.cx.fl, self.cx.dt, self.cx.bf
         W32, p, B, W, F, D, Tv = fl.w32, cx.p, self.B, self.W, self.F, self.D, self.Tv
         ST, SV = self.ST, self.SV
+        both, stacks = self.branches == ("text", "vis"), [st for st in (self.text, self.vis) if st is not None]
         # split-K accumulation targets; and the arrival counters of the LayerNorm folds (every launch leaves them zero: clearing them with
         # the arenas, in the same launch, only makes a step self-healing after a launch that did not complete)
-        fwd.add_zeros([st.yarena for st in (self.text, self.vis) if st.zero_y] +
-                      [st.ln_ctr for st in (self.text, self.vis) if st.ln_ctr is not None], ST)
-        cx.stamp(fwd, "f_fork", ST)
-        fwd.fork(ST, SV)           # the video encoder runs concurrently with the text encoder
-        cx.stamp(fwd, "f_vis_start", SV)
-        if self.normalized_input:
-            if bf:
-                fwd.add_callable(lambda: ops.cast_bf16(self.vn32, self.vn_op), SV)
-        else:
+        fwd.add_zeros([st.yarena for st in stacks if st.zero_y] + [st.ln_ctr for st in stacks if st.ln_ctr is not None], ST)
+        if both:
+            cx.stamp(fwd, "f_fork", ST)
+            fwd.fork(ST, SV)           # the video encoder runs concurrently with the text encoder
+            cx.stamp(fwd, "f_vis_start", SV)
+        if self.vis is not None:
+            if self.normalized_input:
+                if bf:
+                    fwd.add_callable(lambda: ops.cast_bf16(self.vn32, self.vn_op), SV)
+            else:
+                fwd.add("univl_layernorm_fwd", ops.layernorm_desc(
+                    dt, Tv, D, x=self.video, x_f64=True, gamma=W32(n["nv_g"]), beta=W32(n["nv_b"]), y=self.vy, stats=self.vst,
+                    out32=self.vn32, out16=self.vn_op if bf else None, out16_lo=self.vn_lo), SV)
+            fwd.add("univl_gemm", _gemm_desc(dt, self.vn_op, D, fl.wop(n["vw"]), D, Tv, H, D, out32=self.ve, ldc=H, bias=W32(n["vb"]),
+                                             a_lo=self.vn_lo, b_lo=fl.wlo(n["vw"]) if self.vis.pair_w else None), SV)
             fwd.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, Tv, D, x=self.video, x_f64=True, gamma=W32(n["nv_g"]), beta=W32(n["nv_b"]), y=self.vy, stats=self.vst,
-                out32=self.vn32, out16=self.vn_op if bf else None, out16_lo=self.vn_lo), SV)
-        fwd.add("univl_gemm", _gemm_desc(dt, self.vn_op, D, fl.wop(n["vw"]), D, Tv, H, D, out32=self.ve, ldc=H, bias=W32(n["vb"]),
-                                         a_lo=self.vn_lo, b_lo=fl.wlo(n["vw"]) if self.vis.pair_w else None), SV)
-        fwd.add("univl_layernorm_fwd", ops.layernorm_desc(
-            dt, Tv, H, x=self.ve, pos=W32(n["vpos"]), pos_period=F, gamma=W32(n["vlg"]), beta=W32(n["vlb"]), y=self.ve,
-            stats=self.vest, out32=self.v0_32, out16=self.v0_16 if bf else None, p_post=p, seed=cx.seed, off_post=self.off_v,
-            seed_dev=cx.seed_dev, out16_lo=self.v0_lo), SV)
-        cx.stamp(fwd, "f_text_start", ST)
-        fwd.add("univl_embed_text_fwd", ops.embed_text_desc(
-            dt, B, W, self.ids, W32(n["bw"]), W32(n["bp"]), W32(n["blg"]), W32(n["blb"]), type_ids=self.type_ids,
-            type_emb=W32(n["bt"]), y=self.te, stats=self.test, out32=self.t0_32, out16=self.t0_16 if bf else None, p_post=p,
-            seed=cx.seed, off_post=self.off_t, seed_dev=cx.seed_dev, out16_lo=self.t0_lo), ST)
-        self.vis.build_forward(fwd, self.v0_32, self.v0_16, cx.training, zero_arena=False, x16_lo=self.v0_lo)
-        cx.stamp(fwd, "f_vis_end", SV)
-        self.text.build_forward(fwd, self.t0_32, self.t0_16, cx.training, zero_arena=False, x16_lo=self.t0_lo)
-        cx.stamp(fwd, "f_text_end", ST)
-        fwd.join(SV, ST)
-        cx.stamp(fwd, "f_join", ST)
+                dt, Tv, H, x=self.ve, pos=W32(n["vpos"]), pos_period=F, gamma=W32(n["vlg"]), beta=W32(n["vlb"]), y=self.ve,
+                stats=self.vest, out32=self.v0_32, out16=self.v0_16 if bf else None, p_post=p, seed=cx.seed, off_post=self.off_v,
+                seed_dev=cx.seed_dev, out16_lo=self.v0_lo), SV)
+        if self.text is not None:
+            cx.stamp(fwd, "f_text_start", ST)
+            fwd.add("univl_embed_text_fwd", ops.embed_text_desc(
+                dt, B, W, self.ids, W32(n["bw"]), W32(n["bp"]), W32(n["blg"]), W32(n["blb"]), type_ids=self.type_ids,
+                type_emb=W32(n["bt"]), y=self.te, stats=self.test, out32=self.t0_32, out16=self.t0_16 if bf else None, p_post=p,
+                seed=cx.seed, off_post=self.off_t, seed_dev=cx.seed_dev, out16_lo=self.t0_lo), ST)
+        if self.vis is not None:
+            self.vis.build_forward(fwd, self.v0_32, self.v0_16, cx.training, zero_arena=False, x16_lo=self.v0_lo)
+            cx.stamp(fwd, "f_vis_end", SV)
+        if self.text is not None:
+            self.text.build_forward(fwd, self.t0_32, self.t0_16, cx.training, zero_arena=False, x16_lo=self.t0_lo)
+            cx.stamp(fwd, "f_text_end", ST)
+        if both:
+            fwd.join(SV, ST)
+            cx.stamp(fwd, "f_join", ST)
 
     def zero_list(self):
         """Accumulation buffers a backward clears before anything adds into them."""
@@ -765,7 +816,8 @@ def build_step(model, kind, B, W, F, training):
     cx.stamp(fwd, "f_begin")
     if cx.p > 0:
         fwd.add_callable(lambda: ops.bump_counter(cx.seed_dev))
-    st.enc = enc = EncoderPass(cx, B, W, F, normalized_input=(kind == "features_shaped"))
+    branches = {"features_text": ("text",), "features_vis": ("vis",), "features_vis_shaped": ("vis",)}.get(kind, ("text", "vis"))
+    st.enc = enc = EncoderPass(cx, B, W, F, normalized_input=kind in ("features_shaped", "features_vis_shaped"), branches=branches)
     # Round 5: the first layer of the cross encoder / the decoder is read after both encoder stacks; while an update rides, its chunks go
     # with the products of the text / video stack's LAST layer (which carry nothing otherwise) instead of a launch in front of the forward
     if _ab.get("tail_ride"):
@@ -819,8 +871,8 @@ def build_step(model, kind, B, W, F, training):
         st.pooler = PoolerSim(cx, st.run_pairs, B, B, loss_kind)
         st.pooler.build_forward(fwd)
         st.loss_terms.append(st.pooler.loss)
-    elif kind in ("features", "features_shaped"):
-        pass                                   # encoders only (get_sequence_visual_output on a stage-two model)
+    elif kind in ("features", "features_shaped", "features_text", "features_vis", "features_vis_shaped"):
+        pass                                   # encoders only (get_sequence_visual_output on a stage-two model), or one of them alone
     else:
         raise ValueError(kind)
     cx.stamp(fwd, "f_end")
