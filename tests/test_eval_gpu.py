@@ -162,3 +162,46 @@ def test_eval_retrieval_matches_reference_at_bench_size(golden_dir, name, dtype)
     # ... and in fp32 they are the reference's own numbers unless a row's diagonal is within d of another score
     if dtype == torch.float32 and float(g["diag_gap"].min()) > d:
         assert [metrics["R1"], metrics["R5"], metrics["R10"], float(metrics["MR"])] == list(g["metrics"])
+
+
+def test_evaluation_sessions_are_cached_named_objects():
+    """get_similarity_logits (cross-encoder branch), decoder_caption and VideoIndex.search(rerank=True) keep their compiled plans in
+    model._steps as steps.EvalSession objects: a repeated call with the same shapes builds nothing and gives the same bits (fixed-order
+    sums: the library's deterministic mode), and no session can be mistaken for a training Step by the filters over model._steps
+    (bench.py: `getattr(v, "kind", None) in (...) and v.cx.training`).  7 texts x 3 videos, 8 words, 6 frames: 7 text rows in chunks of
+    5 are sessions of 5 and of 2 rows."""
+    import univl_amd
+    from univl_amd.retrieval import VideoIndex
+    from univl_amd.steps import EvalSession, Step
+    cfg = O.OracleConfig(batch_size=2, text_num_hidden_layers=1, visual_num_hidden_layers=1, cross_num_hidden_layers=1,
+                         decoder_num_hidden_layers=2, stage_two=True, task_type="caption", max_words=8, max_frames=6)
+    was = univl_amd.deterministic()
+    univl_amd.set_deterministic(True)
+    try:
+        model, _ = build(cfg, torch.float32)
+        model.eval()
+        t = {k: v.to(DEV) for k, v in O.synthetic_batch(cfg, 7, seed=11).items()}
+        v = {k: x.to(DEV) for k, x in O.synthetic_batch(cfg, 3, seed=12).items()}
+        with torch.no_grad():
+            so = model.get_sequence_output(t["input_ids"], t["token_type_ids"], t["attention_mask"])
+            vo = model.get_visual_output(v["video"], v["video_mask"])
+            am, vm = t["attention_mask"].view(7, -1), v["video_mask"].view(3, -1)
+            first = model.get_similarity_logits(so, vo, am, vm)
+            n_steps = len(model._steps)
+            assert {k[:2] for k in model._steps if k[0] == "xsim"} == {("xsim", 5), ("xsim", 2)}
+            second = model.get_similarity_logits(so, vo, am, vm)
+            assert len(model._steps) == n_steps
+            assert first.shape == (7, 3) and torch.equal(first, second)
+            model.decoder_caption(so[:3], vo, t["input_ids"][:3], am[:3], vm, t["input_caption_ids"][:3], t["decoder_mask"][:3])
+            index = VideoIndex(model, capacity=4, keep_frames=True)
+            index.add(v["video"], v["video_mask"])
+            index.search(t["input_ids"], t["token_type_ids"], t["attention_mask"], k=2, rerank=True)
+        assert {k[0] for k in model._steps} >= {"xsim", "caption_eval", "rerank"}
+        sessions = [s for s in model._steps.values() if not isinstance(s, Step)]
+        assert len(sessions) >= 5                                   # xsim 5 + 2, caption_eval, rerank 5 + 2
+        for s in sessions:
+            assert type(s) is EvalSession and not isinstance(s, tuple)
+            assert getattr(s, "kind", None) not in ("joint", "align", "caption", "pretrain")
+            assert s.cx.training is False and not hasattr(s, "fwd")
+    finally:
+        univl_amd.set_deterministic(was)

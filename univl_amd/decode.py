@@ -30,8 +30,8 @@ are ordered by lower flat index first in the device path (include/univl_hip.h); 
 import torch
 
 from . import _ab, ops
-from .engine import Plan, _gemm_desc
-from .steps import Ctx, CrossRun, RowFeatures, VocabHead, H
+from .engine import DecoderLayer, DecoderStack, Plan, _gemm_desc
+from .steps import EvalSession, VocabHead, H
 
 
 class BeamResult:
@@ -77,7 +77,7 @@ class CaptionBeamSearch:
     (DESIGN.md section 7), so the active instances' results do not depend on it.  The BeamResult holds the first n_active
     instances only."""
 
-    NH, I = 12, 3072
+    NH = 12
 
     def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None):
         """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
@@ -94,41 +94,28 @@ class CaptionBeamSearch:
         self.Tmax = Tmax = int(max_len or model.task_config.max_words)
         assert Tmax <= model.decoder_config.max_target_embeddings
         model.flat.refresh_shadow()
-        cx = self.cx = Ctx(model, False)
-        e, ct, bf, fl, dt = cx.e, cx.ct, cx.bf, cx.fl, cx.dt
         self.R = R = n_inst * n_bm
         self.V = V = model.bert_config.vocab_size
         self.L = L = model.decoder_config.num_decoder_layers
         rows = list(range(n_inst))
         # ---- once per batch: cross encoder per instance + encoder K/V of every decoder layer
-        self.feats = RowFeatures(cx, n_inst, n_inst, W, F)
+        ses = EvalSession(model, n_inst, n_inst, W, F, rows, rows)
+        cx, self.feats, self.run, self.setup = ses.cx, ses.feats, ses.run, ses.plan
+        self.cx, e, ct, bf, fl, dt = cx, cx.e, cx.ct, cx.bf, cx.fl, cx.dt
         for buf in (self.feats.seq_out, self.feats.vis_out, self.feats.amask, self.feats.vmask):
             buf.zero_()                                  # idle slots of a partial first batch read these (class docstring)
-        self.run = run = CrossRun(cx, self.feats, rows, rows)
-        self.S = S = run.S
-        self.setup = Plan()
-        run.build_forward(self.setup)
-        from .engine import DecoderStack
-        names = DecoderStack._names
-        self.nm = [names(None, l) for l in range(L)]
+        self.S = S = self.run.S
         self.kv2 = [e(n_inst * S, 2 * H, dtype=ct) for _ in range(L)]
         for l in range(L):
-            nm = self.nm[l]
-            self.setup.add("univl_gemm", _gemm_desc(dt, run.out16, H, fl.wop_fused(nm["c_kv_w"]), H, n_inst * S, 2 * H, H,
+            nm = DecoderStack._names(l)
+            self.setup.add("univl_gemm", _gemm_desc(dt, self.run.out16, H, fl.wop_fused(nm["c_kv_w"]), H, n_inst * S, 2 * H, H,
                                                     out16=self.kv2[l], ldc=2 * H, bias=fl.w32_fused(nm["c_kv_b"])))
         # ---- per step buffers (R rows)
         self.ids = e(R, dtype=torch.int64)
         self.ey, self.est, self.e32 = e(R, H), e(R, 2), e(R, H)
         self.e16 = e(R, H, dtype=ct) if bf else self.e32
         self.cache = [[torch.zeros(R, Tmax, 2 * H, device=cx.dev, dtype=ct) for _ in range(2)] for _ in range(L)]
-        self.ws = []
-        for l in range(L):
-            w = dict(q1=e(R, H, dtype=ct), ctx1=e(R, H, dtype=ct), lse1=e(R * self.NH), y1=e(R, H), st1=e(R, 2), a32=e(R, H),
-                     q2=e(R, H, dtype=ct), ctx2=e(R, H, dtype=ct), lse2=e(R * self.NH), y2=e(R, H), st2=e(R, 2), d32=e(R, H),
-                     u=e(R, self.I, dtype=ct), f=e(R, self.I, dtype=ct), y3=e(R, H), st3=e(R, 2), o32=e(R, H))
-            for k in ("a", "d", "o"):
-                w[k + "16"] = e(R, H, dtype=ct) if bf else w[k + "32"]
-            self.ws.append(w)
+        self.ws = [dict(DecoderStack.layer_workspace(e, ct, R), q1=e(R, H, dtype=ct)) for _ in range(L)]
         self.head = VocabHead(cx, "decoder.classifier.cls.predictions", R)
         self.src = e(R, dtype=torch.int32)               # cache row each beam continues from
         self.steps = {}
@@ -168,7 +155,9 @@ class CaptionBeamSearch:
             out16=self.e16 if cx.bf else None))
         x32, x16 = self.e32, self.e16
         for l in range(self.L):
-            nm, ws = self.nm[l], self.ws[l]
+            ws = self.ws[l]
+            lay = DecoderLayer(pl, fl, l, ws, R)
+            nm = lay.nm
             cache = self.cache[l][cur]
             if t > 0:        # beams continue from re-ordered parents: gather positions [0, t) of the parent rows
                 src_c, n_rows, stride, nbytes = self.cache[l][prev], R, Tmax * 2 * H * es, t * 2 * H * es
@@ -180,29 +169,11 @@ class CaptionBeamSearch:
             pl.add("univl_attention_fwd", ops.attention_desc(
                 dt, R, self.NH, 1, t + 1, ws["q1"], H, (cache, 0), 2 * H, (cache, H), 2 * H, ws["ctx1"], H, ws["lse1"],
                 bsk=Tmax * 2 * H, bsv=Tmax * 2 * H))
-            pl.add("univl_gemm", _gemm_desc(dt, ws["ctx1"], H, fl.wop(nm["s_o_w"]), H, R, H, H, out32=ws["y1"], ldc=H,
-                                            bias=W32(nm["s_o_b"])))
-            pl.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, R, H, x=ws["y1"], residual=x32, gamma=W32(nm["s_ln_g"]), beta=W32(nm["s_ln_b"]), y=ws["y1"], stats=ws["st1"],
-                out32=ws["a32"], out16=ws["a16"] if cx.bf else None))
-            pl.add("univl_gemm", _gemm_desc(dt, ws["a16"], H, fl.wop(nm["c_q_w"]), H, R, H, H, out16=ws["q2"], ldc=H,
-                                            bias=W32(nm["c_q_b"])))
-            kv = self.kv2[l]
-            pl.add("univl_attention_fwd", ops.attention_desc(
-                dt, self.n_inst, self.NH, self.n_bm, S, ws["q2"], H, (kv, 0), 2 * H, (kv, H), 2 * H, ws["ctx2"], H, ws["lse2"],
-                key_mask=self.run.cmask))
-            pl.add("univl_gemm", _gemm_desc(dt, ws["ctx2"], H, fl.wop(nm["c_o_w"]), H, R, H, H, out32=ws["y2"], ldc=H,
-                                            bias=W32(nm["c_o_b"])))
-            pl.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, R, H, x=ws["y2"], residual=ws["a32"], gamma=W32(nm["c_ln_g"]), beta=W32(nm["c_ln_b"]), y=ws["y2"],
-                stats=ws["st2"], out32=ws["d32"], out16=ws["d16"] if cx.bf else None))
-            pl.add("univl_gemm", _gemm_desc(dt, ws["d16"], H, fl.wop(nm["w1"]), H, R, self.I, H, out16=ws["f"], ldc=self.I,
-                                            bias=W32(nm["b1"]), aux=ws["u"], ldaux=self.I, gelu="fwd"))
-            pl.add("univl_gemm", _gemm_desc(dt, ws["f"], self.I, fl.wop(nm["w2"]), self.I, R, H, self.I, out32=ws["y3"], ldc=H,
-                                            bias=W32(nm["b2"])))
-            pl.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, R, H, x=ws["y3"], residual=ws["d32"], gamma=W32(nm["ln_g"]), beta=W32(nm["ln_b"]), y=ws["y3"], stats=ws["st3"],
-                out32=ws["o32"], out16=ws["o16"] if cx.bf else None))
+            lay.attn_output("s_", x32)
+            lay.enc_query()
+            lay.enc_attention(self.n_inst, self.n_bm, S, self.kv2[l], self.run.cmask)
+            lay.attn_output("c_", ws["a32"])
+            lay.ffn()
             x32, x16 = ws["o32"], ws["o16"]
         self.head.build_forward(pl, x16, with_loss=False)
         pl.add_callable(lambda: ops.log_softmax_rows(self.head.logits, self.V))

@@ -1166,6 +1166,58 @@ class EncoderStack:
         self.bwd_out = gin
 
 
+class DecoderLayer:
+    """What training (DecoderStack.build_forward) and cached decoding (decode.CaptionBeamSearch._step_plan) share of a decoder layer
+    (module_decoder.py:268-320), stated once: emitters over one layer's workspace of T rows (DecoderStack.layer_workspace).  The
+    self-attention core stays with each caller.  p / off / seed_dev: dropout probability, the layer's five stream offsets, the seed word."""
+
+    H, NH, I = 768, 12, 3072
+    BLOCK = {"s_": ("1", "a", 1), "c_": ("2", "d", 3)}     # name prefix -> workspace suffix, output buffer, dropout offset
+
+    def __init__(self, plan, flat, l, ws, T, p=0.0, off=(0, 0, 0, 0, 0), seed_dev=None, stream=0):
+        self.plan, self.fl, self.nm, self.ws, self.T = plan, flat, DecoderStack._names(l), ws, T
+        self.p, self.off, self.seed_dev, self.sm = p, off, seed_dev, stream
+
+    def _gemm(self, desc):
+        self.plan.add("univl_gemm", desc, self.sm)
+
+    def _res_ln(self, sfx, residual, g, b, out, off):
+        fl, ws, nm = self.fl, self.ws, self.nm
+        self.plan.add("univl_layernorm_fwd", ops.layernorm_desc(
+            fl.dt, self.T, self.H, x=ws["y" + sfx], residual=residual, gamma=fl.w32(nm[g]), beta=fl.w32(nm[b]), y=ws["y" + sfx],
+            stats=ws["st" + sfx], out32=ws[out + "32"], out16=ws[out + "16"] if fl.compute_dtype == torch.bfloat16 else None,
+            p_pre=self.p, off_pre=off, seed_dev=self.seed_dev), self.sm)
+
+    def attn_output(self, pre, x32):
+        """output dense + residual LayerNorm of the self-attention ("s_") or encoder-attention ("c_") block; x32: the block's input"""
+        fl, ws, nm, H = self.fl, self.ws, self.nm, self.H
+        sfx, out, oi = self.BLOCK[pre]
+        self._gemm(_gemm_desc(fl.dt, ws["ctx" + sfx], H, fl.wop(nm[pre + "o_w"]), H, self.T, H, H, out32=ws["y" + sfx], ldc=H,
+                              bias=fl.w32(nm[pre + "o_b"])))
+        self._res_ln(sfx, x32, pre + "ln_g", pre + "ln_b", out, self.off[oi])
+
+    def enc_query(self):
+        fl, ws, nm, H = self.fl, self.ws, self.nm, self.H
+        self._gemm(_gemm_desc(fl.dt, ws["a16"], H, fl.wop_fused(nm["c_q_w"]), H, self.T, H, H, out16=ws["q2"], ldc=H,
+                              bias=fl.w32_fused(nm["c_q_b"])))
+
+    def enc_attention(self, B, Sq, Sk, kv, key_mask):
+        """B x Sq query rows (= T) over the Sk encoder positions of their instance; kv: [B * Sk, 2H] keys | values"""
+        ws, H = self.ws, self.H
+        self.plan.add("univl_attention_fwd", ops.attention_desc(
+            self.fl.dt, B, self.NH, Sq, Sk, ws["q2"], H, (kv, 0), 2 * H, (kv, H), 2 * H, ws["ctx2"], H, ws["lse2"],
+            key_mask=key_mask, p_drop=self.p, offset=self.off[2], seed_dev=self.seed_dev), self.sm)
+
+    def ffn(self, big=None):
+        """FFN1 + GELU, FFN2, residual LayerNorm; big: how the caller adds the two products (None: plainly)"""
+        fl, ws, nm, H, I = self.fl, self.ws, self.nm, self.H, self.I
+        add = big or self._gemm
+        add(_gemm_desc(fl.dt, ws["d16"], H, fl.wop(nm["w1"]), H, self.T, I, H, out16=ws["f"], ldc=I, bias=fl.w32(nm["b1"]),
+                       aux=ws["u"], ldaux=I, gelu="fwd"))
+        add(_gemm_desc(fl.dt, ws["f"], I, fl.wop(nm["w2"]), I, self.T, H, I, out32=ws["y3"], ldc=H, bias=fl.w32(nm["b2"])))
+        self._res_ln("3", ws["d32"], "ln_g", "ln_b", "o", self.off[4])
+
+
 class DecoderStack:
     """Decoder of module_decoder.py:322-340: L layers of {causal self-attention, encoder attention over the cross
     encoder output, FFN}, each followed by the BertSelfOutput / BertOutput residual + LayerNorm blocks
@@ -1180,17 +1232,11 @@ class DecoderStack:
         self.p, self.seed_dev, self.sm = float(p_drop), seed_dev, stream
         dev, H, I, Tq, Tkv = flat.device, self.H, self.I, self.Tq, self.Tkv
         ct = flat.compute_dtype
-        self.bf = ct == torch.bfloat16
         e = _workspace(dev)
         self.layers = []
         for l in range(n_layers):
-            ws = dict(qkv=e(Tq, 3 * H, dtype=ct), lse1=e(B, self.NH, Wd), ctx1=e(Tq, H, dtype=ct), y1=e(Tq, H), st1=e(Tq, 2),
-                      a32=e(Tq, H), q2=e(Tq, H, dtype=ct), kv2=e(Tkv, 2 * H, dtype=ct), lse2=e(B, self.NH, Wd),
-                      ctx2=e(Tq, H, dtype=ct), y2=e(Tq, H), st2=e(Tq, 2), d32=e(Tq, H), u=e(Tq, I, dtype=ct),
-                      f=e(Tq, I, dtype=ct), y3=e(Tq, H), st3=e(Tq, 2), o32=e(Tq, H))
-            for k in ("a", "d", "o"):
-                ws[k + "16"] = e(Tq, H, dtype=ct) if self.bf else ws[k + "32"]
-            ws["off"] = [sites.next() for _ in range(5)]
+            ws = self.layer_workspace(e, ct, Tq)
+            ws.update(qkv=e(Tq, 3 * H, dtype=ct), kv2=e(Tkv, 2 * H, dtype=ct), off=[sites.next() for _ in range(5)])
             self.layers.append(ws)
         self.g1, self.g2 = e(Tq, H), e(Tq, H)
         self.dxd = e(Tq, H, dtype=ct)
@@ -1200,14 +1246,26 @@ class DecoderStack:
         self.dq2 = e(Tq, H, dtype=ct)
         self.dkv2 = e(Tkv, 2 * H, dtype=ct)
 
-    def _names(self, l):
+    @classmethod
+    def layer_workspace(cls, e, ct, T):
+        """One layer's buffers for T decoder rows from the caller's allocator e (this class adds qkv, kv2, off; decoding adds q1)."""
+        H, I = cls.H, cls.I
+        ws = dict(ctx1=e(T, H, dtype=ct), lse1=e(T * cls.NH), y1=e(T, H), st1=e(T, 2), a32=e(T, H),
+                  q2=e(T, H, dtype=ct), ctx2=e(T, H, dtype=ct), lse2=e(T * cls.NH), y2=e(T, H), st2=e(T, 2), d32=e(T, H),
+                  u=e(T, I, dtype=ct), f=e(T, I, dtype=ct), y3=e(T, H), st3=e(T, 2), o32=e(T, H))
+        for k in ("a", "d", "o"):
+            ws[k + "16"] = e(T, H, dtype=ct) if ct == torch.bfloat16 else ws[k + "32"]
+        return ws
+
+    @staticmethod
+    def _names(l):
         p = "decoder.decoder.layer.%d" % l
         s, c = p + ".slf_attn", p + ".enc_attn"
         qkv = lambda a, names, suf: [a + ".att." + n + suf for n in names]
         return dict(s_qkv_w=qkv(s, ("query", "key", "value"), ".weight"), s_qkv_b=qkv(s, ("query", "key", "value"), ".bias"),
                     s_o_w=s + ".output.dense.weight", s_o_b=s + ".output.dense.bias",
                     s_ln_g=s + ".output.LayerNorm.weight", s_ln_b=s + ".output.LayerNorm.bias",
-                    c_q_w=c + ".att.query.weight", c_q_b=c + ".att.query.bias",
+                    c_q_w=qkv(c, ("query",), ".weight"), c_q_b=qkv(c, ("query",), ".bias"),
                     c_kv_w=qkv(c, ("key", "value"), ".weight"), c_kv_b=qkv(c, ("key", "value"), ".bias"),
                     c_o_w=c + ".output.dense.weight", c_o_b=c + ".output.dense.bias",
                     c_ln_g=c + ".output.LayerNorm.weight", c_ln_b=c + ".output.LayerNorm.bias",
@@ -1219,13 +1277,11 @@ class DecoderStack:
         return self.layers[-1]["o32"], self.layers[-1]["o16"]
 
     def build_forward(self, plan, x32, x16, enc16, training):
-        fl, dt, H, I, B, Wd, Sk, Tq, Tkv, sm = self.flat, self.flat.dt, self.H, self.I, self.B, self.Wd, self.Sk, self.Tq, self.Tkv, self.sm
+        fl, dt, H, B, Wd, Sk, Tq, Tkv, sm = self.flat, self.flat.dt, self.H, self.B, self.Wd, self.Sk, self.Tq, self.Tkv, self.sm
         p = self.p if training else 0.0
         adam_ride = (getattr(fl, "adam_ride", False)
                      and fl.compute_dtype == torch.bfloat16 and training)
         for l, ws in enumerate(self.layers):
-            nm = self._names(l)
-            off = ws["off"]
             plan.wait_point(("layer", "decoder", l), sm)
             slot = [0]
 
@@ -1238,40 +1294,19 @@ class DecoderStack:
                 else:
                     plan.add("univl_gemm", desc, sm)
 
-            big(_gemm_desc(dt, x16, H, fl.wop_fused(nm["s_qkv_w"]), H, Tq, 3 * H, H, out16=ws["qkv"], ldc=3 * H,
+            lay = DecoderLayer(plan, fl, l, ws, Tq, p, ws["off"], self.seed_dev, sm)
+            nm, qkv, kv = lay.nm, ws["qkv"], ws["kv2"]
+            big(_gemm_desc(dt, x16, H, fl.wop_fused(nm["s_qkv_w"]), H, Tq, 3 * H, H, out16=qkv, ldc=3 * H,
                            bias=fl.w32_fused(nm["s_qkv_b"])))
-            qkv = ws["qkv"]
             plan.add("univl_attention_fwd", ops.attention_desc(
                 dt, B, self.NH, Wd, Wd, (qkv, 0), 3 * H, (qkv, H), 3 * H, (qkv, 2 * H), 3 * H, ws["ctx1"], H, ws["lse1"],
-                key_mask=self.dec_mask, causal=True, p_drop=p, offset=off[0], seed_dev=self.seed_dev), sm)
-            plan.add("univl_gemm", _gemm_desc(dt, ws["ctx1"], H, fl.wop(nm["s_o_w"]), H, Tq, H, H, out32=ws["y1"], ldc=H,
-                                              bias=fl.w32(nm["s_o_b"])), sm)
-            plan.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, Tq, H, x=ws["y1"], residual=x32, gamma=fl.w32(nm["s_ln_g"]), beta=fl.w32(nm["s_ln_b"]), y=ws["y1"],
-                stats=ws["st1"], out32=ws["a32"], out16=ws["a16"] if self.bf else None, p_pre=p, off_pre=off[1],
-                seed_dev=self.seed_dev), sm)
-            plan.add("univl_gemm", _gemm_desc(dt, ws["a16"], H, fl.wop(nm["c_q_w"]), H, Tq, H, H, out16=ws["q2"], ldc=H,
-                                              bias=fl.w32(nm["c_q_b"])), sm)
-            big(_gemm_desc(dt, enc16, H, fl.wop_fused(nm["c_kv_w"]), H, Tkv, 2 * H, H, out16=ws["kv2"],
-                           ldc=2 * H, bias=fl.w32_fused(nm["c_kv_b"])))
-            kv = ws["kv2"]
-            plan.add("univl_attention_fwd", ops.attention_desc(
-                dt, B, self.NH, Wd, Sk, ws["q2"], H, (kv, 0), 2 * H, (kv, H), 2 * H, ws["ctx2"], H, ws["lse2"],
-                key_mask=self.enc_mask, p_drop=p, offset=off[2], seed_dev=self.seed_dev), sm)
-            plan.add("univl_gemm", _gemm_desc(dt, ws["ctx2"], H, fl.wop(nm["c_o_w"]), H, Tq, H, H, out32=ws["y2"], ldc=H,
-                                              bias=fl.w32(nm["c_o_b"])), sm)
-            plan.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, Tq, H, x=ws["y2"], residual=ws["a32"], gamma=fl.w32(nm["c_ln_g"]), beta=fl.w32(nm["c_ln_b"]), y=ws["y2"],
-                stats=ws["st2"], out32=ws["d32"], out16=ws["d16"] if self.bf else None, p_pre=p, off_pre=off[3],
-                seed_dev=self.seed_dev), sm)
-            big(_gemm_desc(dt, ws["d16"], H, fl.wop(nm["w1"]), H, Tq, I, H, out16=ws["f"], ldc=I,
-                           bias=fl.w32(nm["b1"]), aux=ws["u"], ldaux=I, gelu="fwd"))
-            big(_gemm_desc(dt, ws["f"], I, fl.wop(nm["w2"]), I, Tq, H, I, out32=ws["y3"], ldc=H,
-                           bias=fl.w32(nm["b2"])))
-            plan.add("univl_layernorm_fwd", ops.layernorm_desc(
-                dt, Tq, H, x=ws["y3"], residual=ws["d32"], gamma=fl.w32(nm["ln_g"]), beta=fl.w32(nm["ln_b"]), y=ws["y3"],
-                stats=ws["st3"], out32=ws["o32"], out16=ws["o16"] if self.bf else None, p_pre=p, off_pre=off[4],
-                seed_dev=self.seed_dev), sm)
+                key_mask=self.dec_mask, causal=True, p_drop=p, offset=ws["off"][0], seed_dev=self.seed_dev), sm)
+            lay.attn_output("s_", x32)
+            lay.enc_query()
+            big(_gemm_desc(dt, enc16, H, fl.wop_fused(nm["c_kv_w"]), H, Tkv, 2 * H, H, out16=kv, ldc=2 * H, bias=fl.w32_fused(nm["c_kv_b"])))
+            lay.enc_attention(B, Wd, Sk, kv, self.enc_mask)
+            lay.attn_output("c_", ws["a32"])
+            lay.ffn(big)
             x32, x16 = ws["o32"], ws["o16"]
 
     def build_backward(self, plan, gin, x0_32, x0_16, enc16, denc32, gs, training):
@@ -1294,10 +1329,37 @@ class DecoderStack:
                 plan.add("univl_gemm", wgrad, sm)
                 plan.add("univl_gemm", dgrad, sm)
 
+        def proj_pair(dy, x16, wn, bn, rows, out32, **kw):
+            """wgrad + dgrad pair of y = x16 . W^T + b given dy [rows, N]; wn / bn: weight / bias names; kw: how the dgrad lands in out32"""
+            N = dy.shape[1]
+            emit(_gemm_desc(dt, dy, N, x16, H, N, H, rows, trans_a=1, trans_b=1, out32=fl.g_fused(wn), ldc=H,
+                            accumulate=gs.acc(wn[0]), dbias=fl.g_fused(bn)),
+                 _gemm_desc(dt, dy, N, fl.wop_fused(wn), H, rows, H, N, trans_b=1, out32=out32, ldc=H, **kw))
+
         for l in range(self.L - 1, -1, -1):
             ws, nm = self.layers[l], self._names(l)
             off = ws["off"]
-            xin32, xin16 = (x0_32, x0_16) if l == 0 else (self.layers[l - 1]["o32"], self.layers[l - 1]["o16"])
+            xin16 = x0_16 if l == 0 else self.layers[l - 1]["o16"]
+
+            def attn_block(pre, dout, attn, dq, x16, kv=None):
+                """The self- ("s_") / encoder-attention ("c_") block's backward given dout: LayerNorm, output projection, attention
+                (attn: its descriptor), then the input projections -- the encoder K/V one (kv = (dkv, enc16), accumulated into denc32)
+                and dq against the block input x16 plus the LayerNorm's dx (residual path).  Returns the gradient wrt x16's block input."""
+                sfx, _, oi = DecoderLayer.BLOCK[pre]
+                plan.add("univl_layernorm_bwd", ops.layernorm_desc(
+                    dt, Tq, H, gamma=fl.w32(nm[pre + "ln_g"]), y=ws["y" + sfx], stats=ws["st" + sfx], dout=dout, dx32=self.g1,
+                    dxd16=self.dxd, dgamma=G(nm[pre + "ln_g"]), dbeta=G(nm[pre + "ln_b"]), dbias=G(nm[pre + "o_b"]), p_pre=p,
+                    off_pre=off[oi], seed_dev=self.seed_dev), sm)
+                emit(_gemm_desc(dt, self.dxd, H, ws["ctx" + sfx], H, H, H, Tq, trans_a=1, trans_b=1, out32=G(nm[pre + "o_w"]),
+                                ldc=H, accumulate=gs.acc(nm[pre + "o_w"])),
+                     _gemm_desc(dt, self.dxd, H, fl.wop(nm[pre + "o_w"]), H, Tq, H, H, trans_b=1, out16=self.dctx, ldc=H))
+                plan.add("univl_attention_bwd", attn, sm)
+                if kv is not None:
+                    proj_pair(kv[0], kv[1], nm["c_kv_w"], nm["c_kv_b"], Tkv, denc32, accumulate=True)
+                qn = "c_q" if kv is not None else "s_qkv"
+                proj_pair(dq, x16, nm[qn + "_w"], nm[qn + "_b"], Tq, self.g2, residual=self.g1, ldr=H)
+                return self.g2
+
             # FFN block
             dz = self.g1
             plan.add("univl_layernorm_bwd", ops.layernorm_desc(
@@ -1308,51 +1370,14 @@ class DecoderStack:
                  _gemm_desc(dt, self.dxd, H, fl.wop(nm["w2"]), I, Tq, I, H, trans_b=1, out16=self.du, ldc=I,
                             aux=ws["u"], ldaux=I, gelu="bwd"))
             dd = self.g2
-            emit(_gemm_desc(dt, self.du, I, ws["d16"], H, I, H, Tq, trans_a=1, trans_b=1, out32=G(nm["w1"]), ldc=H,
-                            accumulate=gs.acc(nm["w1"]), dbias=G(nm["b1"])),
-                 _gemm_desc(dt, self.du, I, fl.wop(nm["w1"]), H, Tq, H, I, trans_b=1, out32=dd, ldc=H,
-                            residual=dz, ldr=H))
-            # encoder-attention block
-            dy2 = self.g1
-            plan.add("univl_layernorm_bwd", ops.layernorm_desc(
-                dt, Tq, H, gamma=fl.w32(nm["c_ln_g"]), y=ws["y2"], stats=ws["st2"], dout=dd, dx32=dy2, dxd16=self.dxd,
-                dgamma=G(nm["c_ln_g"]), dbeta=G(nm["c_ln_b"]), dbias=G(nm["c_o_b"]), p_pre=p, off_pre=off[3], seed_dev=self.seed_dev), sm)
-            emit(_gemm_desc(dt, self.dxd, H, ws["ctx2"], H, H, H, Tq, trans_a=1, trans_b=1, out32=G(nm["c_o_w"]),
-                            ldc=H, accumulate=gs.acc(nm["c_o_w"])),
-                 _gemm_desc(dt, self.dxd, H, fl.wop(nm["c_o_w"]), H, Tq, H, H, trans_b=1, out16=self.dctx, ldc=H))
-            kv, dkv = ws["kv2"], self.dkv2
-            plan.add("univl_attention_bwd", ops.attention_desc(
+            proj_pair(self.du, ws["d16"], [nm["w1"]], [nm["b1"]], Tq, dd, residual=dz, ldr=H)
+            kv, dkv, qkv, dqkv = ws["kv2"], self.dkv2, ws["qkv"], self.dqkv
+            da = attn_block("c_", dd, ops.attention_desc(
                 dt, B, self.NH, Wd, Sk, ws["q2"], H, (kv, 0), 2 * H, (kv, H), 2 * H, ws["ctx2"], H, ws["lse2"],
                 key_mask=self.enc_mask, p_drop=p, offset=off[2], seed_dev=self.seed_dev, dout=self.dctx, lddo=H,
-                dq=self.dq2, lddq=H, dk=(dkv, 0), lddk=2 * H, dv=(dkv, H), lddv=2 * H), sm)
-            emit(_gemm_desc(dt, dkv, 2 * H, enc16, H, 2 * H, H, Tkv, trans_a=1, trans_b=1,
-                            out32=fl.g_fused(nm["c_kv_w"]), ldc=H, accumulate=gs.acc(nm["c_kv_w"][0]),
-                            dbias=fl.g_fused(nm["c_kv_b"])),
-                 _gemm_desc(dt, dkv, 2 * H, fl.wop_fused(nm["c_kv_w"]), H, Tkv, H, 2 * H, trans_b=1,
-                            out32=denc32, ldc=H, accumulate=True))
-            da = self.g2
-            emit(_gemm_desc(dt, self.dq2, H, ws["a16"], H, H, H, Tq, trans_a=1, trans_b=1, out32=G(nm["c_q_w"]),
-                            ldc=H, accumulate=gs.acc(nm["c_q_w"]), dbias=G(nm["c_q_b"])),
-                 _gemm_desc(dt, self.dq2, H, fl.wop(nm["c_q_w"]), H, Tq, H, H, trans_b=1, out32=da, ldc=H,
-                            residual=dy2, ldr=H))
-            # causal self-attention block
-            dy1 = self.g1
-            plan.add("univl_layernorm_bwd", ops.layernorm_desc(
-                dt, Tq, H, gamma=fl.w32(nm["s_ln_g"]), y=ws["y1"], stats=ws["st1"], dout=da, dx32=dy1, dxd16=self.dxd,
-                dgamma=G(nm["s_ln_g"]), dbeta=G(nm["s_ln_b"]), dbias=G(nm["s_o_b"]), p_pre=p, off_pre=off[1], seed_dev=self.seed_dev), sm)
-            emit(_gemm_desc(dt, self.dxd, H, ws["ctx1"], H, H, H, Tq, trans_a=1, trans_b=1, out32=G(nm["s_o_w"]),
-                            ldc=H, accumulate=gs.acc(nm["s_o_w"])),
-                 _gemm_desc(dt, self.dxd, H, fl.wop(nm["s_o_w"]), H, Tq, H, H, trans_b=1, out16=self.dctx, ldc=H))
-            qkv, dqkv = ws["qkv"], self.dqkv
-            plan.add("univl_attention_bwd", ops.attention_desc(
+                dq=self.dq2, lddq=H, dk=(dkv, 0), lddk=2 * H, dv=(dkv, H), lddv=2 * H), self.dq2, ws["a16"], kv=(dkv, enc16))
+            gin = attn_block("s_", da, ops.attention_desc(
                 dt, B, self.NH, Wd, Wd, (qkv, 0), 3 * H, (qkv, H), 3 * H, (qkv, 2 * H), 3 * H, ws["ctx1"], H, ws["lse1"],
                 key_mask=self.dec_mask, causal=True, p_drop=p, offset=off[0], seed_dev=self.seed_dev, dout=self.dctx, lddo=H,
-                dq=(dqkv, 0), lddq=3 * H, dk=(dqkv, H), lddk=3 * H, dv=(dqkv, 2 * H), lddv=3 * H), sm)
-            dx = self.g2
-            emit(_gemm_desc(dt, dqkv, 3 * H, xin16, H, 3 * H, H, Tq, trans_a=1, trans_b=1,
-                            out32=fl.g_fused(nm["s_qkv_w"]), ldc=H, accumulate=gs.acc(nm["s_qkv_w"][0]),
-                            dbias=fl.g_fused(nm["s_qkv_b"])),
-                 _gemm_desc(dt, dqkv, 3 * H, fl.wop_fused(nm["s_qkv_w"]), H, Tq, H, 3 * H, trans_b=1, out32=dx,
-                            ldc=H, residual=dy1, ldr=H))
-            gin = dx
+                dq=(dqkv, 0), lddq=3 * H, dk=(dqkv, H), lddk=3 * H, dv=(dqkv, 2 * H), lddv=3 * H), dqkv, xin16)
         return gin

@@ -964,34 +964,30 @@ class UniVL(UniVLPreTrainedModel):
         ops.gemm(tn, vn, Bt, Bv, Hd, out32=sim)
         return sim
 
+    def _eval_session(self, key, build):
+        """The steps.EvalSession cached under `key` in self._steps (build() makes it on first use), behind the flush of a pending optimizer
+        update and the shadow refresh that every reader of the parameters starts with."""
+        self._flush_pending()
+        self.flat.refresh_shadow()
+        ses = self._steps.get(key)
+        if ses is None:
+            ses = self._steps[key] = build()
+        return ses
+
     def _cross_similarity_eval(self, seq, vis, am, vm, chunk_rows=5):
         """_cross_similarity (modeling.py:341-375) for cached features: every (text, video) pair through the cross
         encoder, `chunk_rows` text rows at a time (the reference's step_size = 5)."""
-        from .steps import Ctx, CrossRun, PoolerSim, RowFeatures
-        from .engine import Plan
+        from .steps import EvalSession, PoolerSim
         Bt, W, _ = seq.shape
         Bv, F, _ = vis.shape
-        self._flush_pending()
-        self.flat.refresh_shadow()
         out = torch.empty(Bt, Bv, device=seq.device)
         for lo in range(0, Bt, chunk_rows):
             n = min(chunk_rows, Bt - lo)
-            key = ("xsim", n, Bv, W, F)
-            ev = self._steps.get(key)
-            if ev is None:
-                cx = Ctx(self, False)
-                feats = RowFeatures(cx, n, Bv, W, F)
-                pairs = [(i, j) for i in range(n) for j in range(Bv)]
-                run = CrossRun(cx, feats, [a for a, _ in pairs], [b for _, b in pairs])
-                plan = Plan()
-                run.build_forward(plan)
-                pooler = PoolerSim(cx, run, n, Bv, None)
-                pooler.build_forward(plan)
-                ev = self._steps[key] = (feats, run, pooler, plan)
-            feats, run, pooler, plan = ev
-            feats.load(seq[lo:lo + n], vis, am[lo:lo + n], vm)
-            plan.run()
-            out[lo:lo + n].copy_(pooler.sim.view(n, Bv))
+            ses = self._eval_session(("xsim", n, Bv, W, F), lambda: EvalSession(
+                self, n, Bv, W, F, [i for i in range(n) for _ in range(Bv)], list(range(Bv)) * n, PoolerSim, n, Bv, None))
+            ses.feats.load(seq[lo:lo + n], vis, am[lo:lo + n], vm)
+            ses.plan.run()
+            out[lo:lo + n].copy_(ses.head.sim.view(n, Bv))
         return out
 
     def decoder_caption(self, sequence_output, visual_output, input_ids, attention_mask, video_mask, input_caption_ids,
@@ -1000,8 +996,7 @@ class UniVL(UniVLPreTrainedModel):
         their argmax."""
         if self.decoder is None:
             raise RuntimeError("decoder_caption: this model was built without a decoder (stage one)")
-        from .steps import Ctx, CrossRun, DecoderRun, RowFeatures
-        from .engine import Plan
+        from .steps import DecoderRun, EvalSession
         attention_mask = attention_mask.reshape(-1, attention_mask.shape[-1])
         video_mask = video_mask.reshape(-1, video_mask.shape[-1])
         input_caption_ids = input_caption_ids.reshape(-1, input_caption_ids.shape[-1])
@@ -1010,23 +1005,12 @@ class UniVL(UniVLPreTrainedModel):
         F, Wd = visual_output.shape[1], input_caption_ids.shape[-1]
         if sequence_output.device.type != "cuda":
             raise RuntimeError("univl_amd.UniVL.decoder_caption needs HIP device tensors; no CPU fallback")
-        self._flush_pending()
-        self.flat.refresh_shadow()
-        key = ("caption_eval", B, W, F, Wd)
-        ev = self._steps.get(key)
-        if ev is None:
-            cx = Ctx(self, False)
-            feats = RowFeatures(cx, B, B, W, F)
-            run = CrossRun(cx, feats, list(range(B)), list(range(B)))
-            plan = Plan()
-            run.build_forward(plan)
-            dec = DecoderRun(cx, run, Wd, with_loss=False)
-            dec.build_forward(plan)
-            ev = self._steps[key] = (feats, run, dec, plan)
-        feats, run, dec, plan = ev
-        feats.load(sequence_output.to(torch.float32), visual_output.to(torch.float32), attention_mask, video_mask)
+        ses = self._eval_session(("caption_eval", B, W, F, Wd), lambda: EvalSession(
+            self, B, B, W, F, list(range(B)), list(range(B)), DecoderRun, Wd, False))
+        dec = ses.head
+        ses.feats.load(sequence_output.to(torch.float32), visual_output.to(torch.float32), attention_mask, video_mask)
         dec.load(input_caption_ids, decoder_mask)
-        plan.run()
+        ses.plan.run()
         V = self.bert_config.vocab_size
         scores = dec.head.logits.view(B, Wd, -1)[:, :, :V]
         if get_logits:

@@ -130,8 +130,7 @@ class VideoIndex:
         return ops.sim_topk(q, self.vectors, int(k), target=targets)
 
     def _rerank(self, q, so, am, K, chunk_rows):
-        from .engine import Plan
-        from .steps import Ctx, CrossRun, PoolerSim, RowFeatures
+        from .steps import EvalSession, PoolerSim
         model = self.model
         if model.cross is None:
             raise ValueError("VideoIndex.search(rerank=True): this model has no cross encoder")
@@ -145,25 +144,16 @@ class VideoIndex:
         cross = torch.empty(Nq, K, device=q.device, dtype=torch.float32)
         for lo in range(0, Nq, chunk_rows):
             n = min(chunk_rows, Nq - lo)
-            key = ("rerank", n, K, W, F)
-            ev = model._steps.get(key)
-            if ev is None:
-                cx = Ctx(model, False)
-                feats = RowFeatures(cx, n, n * K, W, F)
-                run = CrossRun(cx, feats, [i for i in range(n) for _ in range(K)], list(range(n * K)))     # explicit tidx / vidx
-                plan = Plan()
-                run.build_forward(plan)
-                pooler = PoolerSim(cx, run, n, K, None)
-                pooler.build_forward(plan)
-                ev = model._steps[key] = (feats, run, pooler, plan)
-            feats, run, pooler, plan = ev
+            ses = model._eval_session(("rerank", n, K, W, F), lambda: EvalSession(
+                model, n, n * K, W, F, [i for i in range(n) for _ in range(K)], list(range(n * K)), PoolerSim, n, K, None))
+            feats = ses.feats
             cand = idx[lo:lo + n].reshape(-1).contiguous()
             ops.gather_rows(self._frames, feats.vis_out, cand, n * K, F * H * 4, F * H * 4)
             feats.vmask.copy_(self._fmask.index_select(0, cand.long()))
             feats.seq_out.copy_(so[lo:lo + n].reshape(n * W, H))
             feats.amask.copy_(am[lo:lo + n])
-            plan.run()
-            cross[lo:lo + n].copy_(pooler.sim.view(n, K))
+            ses.plan.run()
+            cross[lo:lo + n].copy_(ses.head.sim.view(n, K))
         # each row by descending cross score, equal scores by lower row id first: ids ascending, then a stable sort by score
         ids, perm = torch.sort(idx.long(), dim=1, stable=True)
         sc, perm2 = torch.sort(cross.gather(1, perm), dim=1, descending=True, stable=True)

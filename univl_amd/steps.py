@@ -96,79 +96,73 @@ class EncoderPass:
         self.cx, self.B, self.W, self.F = cx, B, W, F
         self.branches = tuple(branches)
         assert self.branches in (("text", "vis"), ("text",), ("vis",)), branches
-        if self.branches != ("text", "vis"):
-            self._init_single(cx, B, W, F, s_text, bool(normalized_input))
-            return
+        both = self.branches == ("text", "vis")
         self.normalized_input = bool(normalized_input)     # get_sequence_visual_output(shaped=True): video arrives normalised
-        e, ct, bf, fl = cx.e, cx.ct, cx.bf, cx.fl
         D = cx.tc.video_dim
         self.D, self.Tt, self.Tv = D, B * W, B * F
         # (Round 4, measured and removed: the video stack BEHIND the text stack on one stream where every product fills the chip by
         # itself -- 13.40 / 13.40 vs 11.99 / 12.11 ms at 128 pairs, 12.03 vs 9.25 at 64, 6.60 vs 5.30 at 32, profiles/r04m_ab_serial_branches.txt:
         # two streams also overlap one branch's tails and non-GEMM kernels with the other's products.)
-        self.ST, self.SV = s_text, s_vis
-        i64 = torch.int64
-        self.ids, self.type_ids, self.amask = e(B, W, dtype=i64), e(B, W, dtype=i64), e(B, W, dtype=i64)
-        self.video, self.vmask = e(B * F, D, dtype=torch.float64), e(B, F, dtype=i64)
-        self.vy, self.vst, self.vn32 = e(self.Tv, D), e(self.Tv, 2), e(self.Tv, D)
-        self.vn_op = e(self.Tv, D, dtype=ct) if bf else self.vn32
-        self.ve, self.vest, self.v0_32 = e(self.Tv, H), e(self.Tv, 2), e(self.Tv, H)
-        self.v0_16 = e(self.Tv, H, dtype=ct) if bf else self.v0_32
-        self.te, self.test, self.t0_32 = e(self.Tt, H), e(self.Tt, 2), e(self.Tt, H)
-        self.t0_16 = e(self.Tt, H, dtype=ct) if bf else self.t0_32
-        self.dseq, self.dvis = e(self.Tt, H), e(self.Tv, H)
-        self.de_op = e(self.Tv, H, dtype=ct)
-        self.dvnorm = e(self.Tv, D)            # grad wrt the normalised video (accumulated: encoder + MFM loss)
-        m = cx.model
-        self.text = EncoderStack(fl, "bert", m.bert_config.num_hidden_layers, B, W, self.amask, cx.p, cx.seed_dev, cx.sites,
-                                 s_main=s_text, s_side=s_text)
-        self.vis = EncoderStack(fl, "visual", m.visual_config.num_hidden_layers, B, F, self.vmask, cx.p, cx.seed_dev, cx.sites,
-                                s_main=s_vis, s_side=s_vis)
-        self.off_t, self.off_v = cx.sites.next(), cx.sites.next()
-        # lo halves of the stacks' input pairs (EncoderStack.pair_x) and of the normalised video (A operand of the video embedding product)
-        self.t0_lo = e(self.Tt, H, dtype=ct) if self.text.pair_x else None
-        self.v0_lo = e(self.Tv, H, dtype=ct) if self.vis.pair_x else None
-        self.vn_lo = e(self.Tv, D, dtype=ct) if (self.vis.pair_x and not self.normalized_input) else None
-        self.seq_out, self.seq_out16 = self.text.output()
-        self.vis_out, self.vis_out16 = self.vis.output()
-
-    def _init_single(self, cx, B, W, F, stream, normalized_input):
-        """One stack, one stream, forward buffers only."""
-        self.normalized_input = normalized_input
-        e, ct, bf, fl, m = cx.e, cx.ct, cx.bf, cx.fl, cx.model
-        D = cx.tc.video_dim
-        self.D, self.Tt, self.Tv = D, B * W, B * F
-        self.ST = self.SV = stream
-        i64 = torch.int64
+        self.ST, self.SV = s_text, (s_vis if both else s_text)
         self.text = self.vis = self.seq_out = self.seq_out16 = self.vis_out = self.vis_out16 = None
         self.t0_lo = self.v0_lo = self.vn_lo = None
-        if self.branches == ("text",):
-            self.ids, self.type_ids, self.amask = e(B, W, dtype=i64), e(B, W, dtype=i64), e(B, W, dtype=i64)
-            self.te, self.test, self.t0_32 = e(self.Tt, H), e(self.Tt, 2), e(self.Tt, H)
-            self.t0_16 = e(self.Tt, H, dtype=ct) if bf else self.t0_32
-            self.text = EncoderStack(fl, "bert", m.bert_config.num_hidden_layers, B, W, self.amask, cx.p, cx.seed_dev, cx.sites,
-                                     s_main=stream, s_side=stream)
+        # the dropout sites in their fixed order: all of the text stack's, all of the video stack's, then the two embedding sites
+        if "text" in self.branches:
+            self._alloc_text(self.ST)
+        if "vis" in self.branches:
+            self._alloc_vis(self.SV)
+        if self.text is not None:
             self.off_t = cx.sites.next()
-            self.t0_lo = e(self.Tt, H, dtype=ct) if self.text.pair_x else None
-            self.seq_out, self.seq_out16 = self.text.output()
-        else:
-            self.video, self.vmask = e(B * F, D, dtype=torch.float64), e(B, F, dtype=i64)
-            self.vy, self.vst, self.vn32 = e(self.Tv, D), e(self.Tv, 2), e(self.Tv, D)
-            self.vn_op = e(self.Tv, D, dtype=ct) if bf else self.vn32
-            self.ve, self.vest, self.v0_32 = e(self.Tv, H), e(self.Tv, 2), e(self.Tv, H)
-            self.v0_16 = e(self.Tv, H, dtype=ct) if bf else self.v0_32
-            self.vis = EncoderStack(fl, "visual", m.visual_config.num_hidden_layers, B, F, self.vmask, cx.p, cx.seed_dev, cx.sites,
-                                    s_main=stream, s_side=stream)
+        if self.vis is not None:
             self.off_v = cx.sites.next()
-            self.v0_lo = e(self.Tv, H, dtype=ct) if self.vis.pair_x else None
-            self.vn_lo = e(self.Tv, D, dtype=ct) if (self.vis.pair_x and not normalized_input) else None
-            self.vis_out, self.vis_out16 = self.vis.output()
+        if both:                               # what only a backward reads (a single stack is forward only)
+            e = cx.e
+            self.dseq, self.dvis = e(self.Tt, H), e(self.Tv, H)
+            self.de_op = e(self.Tv, H, dtype=cx.ct)
+            self.dvnorm = e(self.Tv, D)            # grad wrt the normalised video (accumulated: encoder + MFM loss)
+
+    def _alloc_text(self, stream):
+        """The text stack on `stream`: input and embedding buffers, the EncoderStack, the lo half of its input pair."""
+        cx, B, W, Tt = self.cx, self.B, self.W, self.Tt
+        e, ct, i64 = cx.e, cx.ct, torch.int64
+        self.ids, self.type_ids, self.amask = e(B, W, dtype=i64), e(B, W, dtype=i64), e(B, W, dtype=i64)
+        self.te, self.test, self.t0_32 = e(Tt, H), e(Tt, 2), e(Tt, H)
+        self.t0_16 = e(Tt, H, dtype=ct) if cx.bf else self.t0_32
+        self.text = EncoderStack(cx.fl, "bert", cx.model.bert_config.num_hidden_layers, B, W, self.amask, cx.p, cx.seed_dev, cx.sites,
+                                 s_main=stream, s_side=stream)
+        self.t0_lo = e(Tt, H, dtype=ct) if self.text.pair_x else None
+        self.seq_out, self.seq_out16 = self.text.output()
+
+    def _alloc_vis(self, stream):
+        """The video stack on `stream`, likewise; + the lo half of the normalised video (A operand of the video embedding product)."""
+        cx, B, F, D, Tv = self.cx, self.B, self.F, self.D, self.Tv
+        e, ct, bf = cx.e, cx.ct, cx.bf
+        self.video, self.vmask = e(B * F, D, dtype=torch.float64), e(B, F, dtype=torch.int64)
+        self.vy, self.vst, self.vn32 = e(Tv, D), e(Tv, 2), e(Tv, D)
+        self.vn_op = e(Tv, D, dtype=ct) if bf else self.vn32
+        self.ve, self.vest, self.v0_32 = e(Tv, H), e(Tv, 2), e(Tv, H)
+        self.v0_16 = e(Tv, H, dtype=ct) if bf else self.v0_32
+        self.vis = EncoderStack(cx.fl, "visual", cx.model.visual_config.num_hidden_layers, B, F, self.vmask, cx.p, cx.seed_dev, cx.sites,
+                                s_main=stream, s_side=stream)
+        self.v0_lo = e(Tv, H, dtype=ct) if self.vis.pair_x else None
+        self.vn_lo = e(Tv, D, dtype=ct) if (self.vis.pair_x and not self.normalized_input) else None
+        self.vis_out, self.vis_out16 = self.vis.output()
+
+    def _text_inputs(self, input_ids, token_type_ids, attention_mask):
+        return [(self.ids, input_ids), (self.type_ids, token_type_ids), (self.amask, attention_mask)]
+
+    def _video_inputs(self, video, video_mask):
+        return [(self.vn32 if self.normalized_input else self.video, video), (self.vmask, video_mask)]
 
     def load_text(self, input_ids, token_type_ids, attention_mask):
-        stage_inputs([(self.ids, input_ids), (self.type_ids, token_type_ids), (self.amask, attention_mask)])
+        stage_inputs(self._text_inputs(input_ids, token_type_ids, attention_mask))
 
     def load_video(self, video, video_mask):
-        stage_inputs([(self.vn32 if self.normalized_input else self.video, video), (self.vmask, video_mask)])
+        stage_inputs(self._video_inputs(video, video_mask))
+
+    def load(self, input_ids, token_type_ids, attention_mask, video, video_mask):
+        """All five inputs through ONE stage_inputs call (one copy kernel)."""
+        stage_inputs(self._text_inputs(input_ids, token_type_ids, attention_mask) + self._video_inputs(video, video_mask))
 
     N = dict(nv_g="normalize_video.visual_norm2d.weight", nv_b="normalize_video.visual_norm2d.bias",
              vw="visual.embeddings.word_embeddings.weight", vb="visual.embeddings.word_embeddings.bias",
@@ -176,11 +170,6 @@ class EncoderPass:
              vlb="visual.embeddings.LayerNorm.bias", bw="bert.embeddings.word_embeddings.weight",
              bp="bert.embeddings.position_embeddings.weight", bt="bert.embeddings.token_type_embeddings.weight",
              blg="bert.embeddings.LayerNorm.weight", blb="bert.embeddings.LayerNorm.bias")
-
-    def load(self, input_ids, token_type_ids, attention_mask, video, video_mask):
-        B, W, F = self.B, self.W, self.F
-        stage_inputs([(self.ids, input_ids), (self.type_ids, token_type_ids), (self.amask, attention_mask),
-                      (self.vn32 if self.normalized_input else self.video, video), (self.vmask, video_mask)])
 
     def build_forward(self, fwd):
         cx, n, fl, dt, bf = self.cx, self.N, self.cx.fl, self.cx.dt, self.cx.bf
@@ -739,6 +728,25 @@ class PretrainHeads:
         # d cross_output = cat(d text part, d video part): written in full (this run has no other consumer)
         bwd.add_callable(lambda: ops.pair_concat_fwd(self.dtpart, self.dvpart, run.enc.amask, run.enc.vmask, self.arange, self.arange,
                                                      B, W, F, run.dcross, None), sm)
+
+
+class EvalSession:
+    """A compiled evaluation-side forward over features the caller supplies: RowFeatures (Bt text rows, Bv video rows) -> CrossRun over
+    the pairs (tidx[p], vidx[p]) -> an optional head -> one Plan.  The head is head(cx, run, *head_args): PoolerSim without loss
+    (cross-encoder similarity, reranking) or DecoderRun without loss (decoder_caption); None: the cross encoder alone
+    (decode.CaptionBeamSearch appends its own launches).  Cached in model._steps beside the Steps (UniVL._eval_session); unlike a Step
+    it has no kind and no fwd / bwd plans, and its cx.training is False."""
+
+    def __init__(self, model, Bt, Bv, W, F, tidx, vidx, head=None, *head_args):
+        cx = self.cx = Ctx(model, False)
+        self.feats = RowFeatures(cx, Bt, Bv, W, F)
+        self.run = CrossRun(cx, self.feats, tidx, vidx)
+        self.plan = Plan()
+        self.run.build_forward(self.plan)
+        self.head = None
+        if head is not None:
+            self.head = head(cx, self.run, *head_args)
+            self.head.build_forward(self.plan)
 
 
 # ------------------------------------------------------------------------------------------------ step assembly
