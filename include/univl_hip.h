@@ -37,7 +37,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 const char* univl_last_error(void);
 int univl_version(void);
-/* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE, 8 BeamStep, 9 SimTopk) -- lets a
+/* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE, 8 BeamStep, 9 SimTopk, 10 VocabScore) -- lets a
  * foreign-language binding verify its struct mirrors at load time */
 int univl_struct_size(int which);
 /* number of CUs / name of the current device, for host-side launch heuristics; returns 0 or hipError_t */
@@ -495,6 +495,45 @@ typedef struct UnivlVocabCE {
 } UnivlVocabCE;
 int univl_vocab_ce_fwd(const UnivlVocabCE* desc, hipStream_t stream);
 int univl_vocab_ce_bwd(const UnivlVocabCE* desc, hipStream_t stream);
+/* K16 scoring form: teacher-forced SCORING on the tied vocabulary classifier -- the forward of K16 with the questions an evaluation asks of the
+ * logits answered in the product's epilogue: for x [rows, K] . table [V, K]^T + bias (module_bert.py:327-330, decoder copy
+ * module_decoder.py:180-183) and labels [rows], what log_softmax + gather + arg-max over the [rows, V] logits would give
+ * (a caller of decoder_caption with get_logits, modeling.py:409-428; the label convention of modeling.py:253) -- and the logits are
+ * never written.  Forward only.  rows = n_seq * seq_len: caption s owns rows [s * seq_len, (s + 1) * seq_len).
+ * A row COUNTS when label != ignore_index and 0 <= label < V; any other label is treated as ignored and reads nothing out of range.
+ * Outputs:
+ *   lse[row]           = logsumexp of the row's logits
+ *   token_logprob[row] = logit[label] - lse[row]; 0 where the row does not count
+ *   top_token[row], top_logprob[row] = the row's arg-max column and max - lse[row].  TIE RULE (the one univl_beam_step and
+ *                        univl_sim_topk fix, part of the contract): equal fp32 logits resolve to the LOWER column
+ *   seq_logprob[s]     = ((t0 + t1) + t2) + ... over the caption's token_logprob in ascending row order, one fp32 chain
+ *   seq_tokens[s]      = the caption's counting rows;  seq_correct[s] = those whose top_token equals the label
+ * Three launches, no host read, capturable: the 128 x 128 tile walk of K16 (a tile's epilogue leaves one (max, sum exp(logit - max),
+ * column of the max) triple per row in slot [row][column tile]: 16-lane shuffles in a wave, LDS across the column waves), a wave per
+ * row that folds the slots in slot order, a wave per caption for the sums.  Every reduction is in fixed order -- results are
+ * bit-reproducible in every mode -- and there are no float atomics.  Behaviour on NaN logits: unspecified.
+ * Range: rows >= 1, V >= 1, K a multiple of 64 (bf16) / 32 (fp32), seq_len >= 1 dividing rows, slots >= ceil(V / 128), ldx / ldt >= K,
+ * x and table 16-byte aligned with 16-byte row pitches, no NULL pointer but bias; otherwise UNIVL_EINVAL. */
+typedef struct UnivlVocabScore {
+    int32_t dtype, rows, V, K;
+    const void* x; int64_t ldx;    /* [rows, K] compute type, K-major */
+    const void* table; int64_t ldt;/* [V, K] compute type, K-major */
+    const float* bias;             /* [V] or null */
+    const int64_t* labels;         /* [rows] */
+    int32_t ignore_index, slots;
+    int32_t seq_len, reserved;     /* reserved: 0 */
+    float* partial;                /* scratch [rows, slots, 2] */
+    int32_t* partial_top;          /* scratch [rows, slots] */
+    float* label_logit;            /* scratch [rows] */
+    float* token_logprob;          /* [rows] */
+    int32_t* top_token;            /* [rows] */
+    float* top_logprob;            /* [rows] */
+    float* lse;                    /* [rows] */
+    float* seq_logprob;            /* [rows / seq_len] */
+    int32_t* seq_tokens;           /* [rows / seq_len] */
+    int32_t* seq_correct;          /* [rows / seq_len] */
+} UnivlVocabScore;
+int univl_vocab_score(const UnivlVocabScore* desc, hipStream_t stream);
 /* masked-frame NCE of UniVL._calculate_mfm_loss (modeling.py:285-297) on the [n,n] logits matrix */
 int univl_mfm_nce_loss(const float* logits, int64_t ld, const int64_t* vmask, const int64_t* labels, int32_t n,
                        float* scratch2, float* loss, float* dlogits, int64_t lddl, hipStream_t stream);

@@ -81,10 +81,17 @@ class SimTopk(C.Structure):
                 ("reserved", i32), ("idx", vp), ("score", vp), ("target", vp), ("gt", vp), ("eq", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+class VocabScore(C.Structure):
+    _fields_ = [("dtype", i32), ("rows", i32), ("V", i32), ("K", i32), ("x", vp), ("ldx", i64), ("table", vp), ("ldt", i64), ("bias", vp),
+                ("labels", vp), ("ignore_index", i32), ("slots", i32), ("seq_len", i32), ("reserved", i32), ("partial", vp),
+                ("partial_top", vp), ("label_logit", vp), ("token_logprob", vp), ("top_token", vp), ("top_logprob", vp), ("lse", vp),
+                ("seq_logprob", vp), ("seq_tokens", vp), ("seq_correct", vp)]
+
+
 BEAM_MAX, BEAM_SLICES = 8, 8       # include/univl_hip.h: UNIVL_BEAM_MAX, UNIVL_BEAM_SLICES
 TOPK_MAX, TOPK_SLICES_MAX = 64, 256   # include/univl_hip.h: UNIVL_TOPK_MAX, UNIVL_TOPK_SLICES_MAX
 
-_STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk]
+_STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk, VocabScore]
 _lib = None
 
 
@@ -109,7 +116,7 @@ def lib():
             raise RuntimeError("ABI mismatch for %s: library %d bytes, ctypes %d" % (st.__name__, n, C.sizeof(st)))
     for name in ("univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_gemm", "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd",
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
-                 "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk"):
+                 "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_pool_pair_fwd.argtypes = [vp, vp, vp]
@@ -197,7 +204,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_dev
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
             "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
-            "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
+            "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 
 

@@ -1000,6 +1000,7 @@ __device__ __forceinline__ void gemm_acc_only(const T* A, long lda, const T* B, 
 }
 
 #include "vocab_ce.h"
+#include "vocab_score.h"
 #include "attn_body.h"
 
 struct AttnFusedArgs {
@@ -2078,6 +2079,41 @@ extern "C" int univl_vocab_ce_bwd(const UnivlVocabCE* d, hipStream_t stream) {
     const int rc = vocab_ce_prepare(d, a, "univl_vocab_ce_bwd", true);
     if (rc != UNIVL_OK) return rc;
     return d->dtype == UNIVL_BF16 ? vocab_ce_launch<__bf16, 4>(a, true, stream) : vocab_ce_launch<float, 2>(a, true, stream);
+}
+
+extern "C" int univl_vocab_score(const UnivlVocabScore* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    const char* who = "univl_vocab_score";
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
+    UNIVL_CHECK_ARG(d->dtype == UNIVL_F32 || d->dtype == UNIVL_BF16, UNIVL_EUNSUPPORTED, "%s: dtype %d", who, d->dtype);
+    const int bk = d->dtype == UNIVL_BF16 ? 64 : 32;
+    UNIVL_CHECK_ARG(d->rows > 0 && d->V > 0 && d->K > 0 && d->K % bk == 0, UNIVL_EINVAL, "%s: rows %d V %d K %d (K must be a multiple of %d)", who,
+                    d->rows, d->V, d->K, bk);
+    UNIVL_CHECK_ARG(d->seq_len > 0 && d->rows % d->seq_len == 0, UNIVL_EINVAL, "%s: rows %d are not whole captions of seq_len %d", who, d->rows,
+                    d->seq_len);
+    UNIVL_CHECK_ARG(d->x && d->table && d->labels && d->partial && d->partial_top && d->label_logit, UNIVL_EINVAL, "%s: null buffer", who);
+    UNIVL_CHECK_ARG(d->token_logprob && d->top_token && d->top_logprob && d->lse && d->seq_logprob && d->seq_tokens && d->seq_correct, UNIVL_EINVAL,
+                    "%s: null output", who);
+    UNIVL_CHECK_ARG(d->ldx >= d->K && d->ldt >= d->K && d->slots >= (d->V + 127) / 128, UNIVL_EINVAL, "%s: ldx %ld ldt %ld slots %d", who, (long)d->ldx,
+                    (long)d->ldt, d->slots);
+    const int al = d->dtype == UNIVL_BF16 ? 8 : 4;      // 16-byte rows for the LDS-DMA
+    UNIVL_CHECK_ARG(d->ldx % al == 0 && d->ldt % al == 0 && ((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->table & 15) == 0, UNIVL_EINVAL,
+                    "%s: operands must be 16-byte aligned with 16-byte row pitches", who);
+    VocabScoreArgs a;
+    a.X = d->x; a.ldx = d->ldx; a.E = d->table; a.lde = d->ldt; a.bias = d->bias;
+    a.rows = d->rows; a.V = d->V; a.K = d->K;
+    a.labels = d->labels;
+    a.partial = d->partial; a.partial_top = d->partial_top; a.slots = d->slots; a.label_logit = d->label_logit;
+    a.nx = (d->V + 127) / 128; a.ny = (d->rows + 127) / 128;
+    const int rc = d->dtype == UNIVL_BF16 ? vocab_score_launch<__bf16, 4>(a, stream) : vocab_score_launch<float, 2>(a, stream);
+    if (rc != UNIVL_OK) return rc;
+    hipLaunchKernelGGL(vocab_score_rows_kernel, dim3((d->rows + 3) / 4), dim3(256), 0, stream, d->partial, d->partial_top, d->slots, a.nx, d->label_logit,
+                       d->labels, d->ignore_index, d->V, d->rows, d->lse, d->token_logprob, d->top_token, d->top_logprob);
+    const int n_seq = d->rows / d->seq_len;
+    hipLaunchKernelGGL(vocab_score_segments_kernel, dim3((n_seq + 3) / 4), dim3(256), 0, stream, d->token_logprob, d->top_token, d->labels, d->ignore_index,
+                       d->V, n_seq, d->seq_len, d->seq_logprob, d->seq_tokens, d->seq_correct);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
 }
 
 extern "C" int univl_gemm_group(const UnivlGemm* d, int n, hipStream_t stream) {

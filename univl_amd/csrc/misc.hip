@@ -33,6 +33,7 @@ extern "C" int univl_struct_size(int which) {
         case 7: return (int)sizeof(UnivlVocabCE);
         case 8: return (int)sizeof(UnivlBeamStep);
         case 9: return (int)sizeof(UnivlSimTopk);
+        case 10: return (int)sizeof(UnivlVocabScore);
         default: return -1;
     }
 }

@@ -1,4 +1,4 @@
-"""Evaluation entry points for callers that can be edited: eval_retrieval, eval_retrieval_streamed and eval_caption (below).
+"""Evaluation entry points for callers that can be edited: eval_retrieval, eval_retrieval_streamed, eval_caption and eval_caption_loss (below).
 
 Retrieval: the device-resident equivalent of main_task_retrieval.py:367-450 (`_run_on_single_gpu`,
 `eval_epoch`) for callers that can be edited.  The unchanged script keeps working through UniVL.get_* and
@@ -9,8 +9,15 @@ from the GPU (univl_amd.metrics).
 Caption: eval_caption is the body of main_task_caption.py:490-618 (`eval_epoch`) around ONE decoding session
 (univl_amd.decode.CaptionBeamSearch) that every batch of the loader reuses, the short last one included (n_active); the
 reference's cut of each hypothesis at "[SEP]" / "[PAD]" runs on the device (univl_beam_captions) and each batch is copied to the
-host once."""
+host once.
+
+Caption likelihood: eval_caption_loss is the validation loss the caption task's training never reports -- the teacher-forced
+CrossEntropyLoss(ignore_index=-1) of modeling.py:246-254 over a whole loader, with perplexity and token accuracy, around ONE scoring
+session (univl_amd.score.CaptionScorer)."""
+import math
 import os
+
+import numpy as np
 
 import torch
 
@@ -175,3 +182,71 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
     scores = torch.cat(scores) if scores else torch.zeros(0, n_best)
     lengths = torch.cat(lengths) if lengths else torch.zeros(0, dtype=torch.int32)
     return CaptionEvalResult(hyps, refs, hyp_ids, scores, lengths, metrics, session)
+
+
+class CaptionLossResult:
+    """What eval_caption_loss returns.  Items are in loader order.
+      seq_logprob [items] float32, seq_tokens [items] int32, seq_correct [items] int32   per-item host arrays (numpy)
+      loss            -sum(seq_logprob) / sum(seq_tokens): CrossEntropyLoss(ignore_index=-1) over the concatenated loader (NaN when no
+                      token counts, as torch's)
+      perplexity      exp(loss)
+      token_accuracy  sum(seq_correct) / sum(seq_tokens)
+      session         the CaptionScorer that scored every batch (None for a stage-one model)
+    float(result) is loss.  The sums are taken in float64 on the host."""
+
+    def __init__(self, seq_logprob, seq_tokens, seq_correct, session):
+        self.seq_logprob = np.asarray(seq_logprob, dtype=np.float32).reshape(-1)
+        self.seq_tokens = np.asarray(seq_tokens, dtype=np.int32).reshape(-1)
+        self.seq_correct = np.asarray(seq_correct, dtype=np.int32).reshape(-1)
+        self.session = session
+        n = int(self.seq_tokens.astype(np.int64).sum())
+        self.loss = -float(self.seq_logprob.astype(np.float64).sum()) / n if n else float("nan")
+        self.perplexity = math.exp(self.loss) if n else float("nan")
+        self.token_accuracy = float(self.seq_correct.astype(np.int64).sum()) / n if n else float("nan")
+
+    def __float__(self):
+        return self.loss
+
+
+@torch.no_grad()
+def eval_caption_loss(model, batches, *, session=None, device="cuda"):
+    """Teacher-forced caption likelihood over a loader.  batches: the reference caption loader's 12-tuples (main_task_caption.py:353-355):
+    input_caption_ids, decoder_mask and output_caption_ids are elements 9, 10 and 11, labels of -1 do not count (modeling.py:253).
+    One CaptionScorer, sized by the first batch (or the `session` passed in, n_cand = 1), scores every batch; a smaller batch runs
+    with n_active, a larger one is a ValueError.  Each batch's three per-item results come to the host in one copy.
+    Returns a CaptionLossResult; for a stage-one model an empty one (loss NaN) without a launch."""
+    from .score import CaptionScorer
+    if model._stage_one:
+        return CaptionLossResult([], [], [], None)
+    was_training = model.training
+    model.eval()
+    packed = []
+    try:
+        for batch in batches:
+            input_ids, input_mask, segment_ids, video, video_mask = [t.to(device, non_blocking=True) for t in batch[:5]]
+            cap_in, cap_mask, cap_out = [t.to(device, non_blocking=True) for t in batch[9:12]]
+            so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
+            n, Wd = int(so.shape[0]), int(cap_in.shape[-1])
+            if session is None:
+                W, F = int(so.shape[1]), int(vo.shape[1])
+                session = model._eval_session(("caption_score", n, W, F, Wd), lambda: CaptionScorer(model, n, W, F, Wd))
+            else:
+                model._flush_pending()                   # what _eval_session does ahead of a session it owns
+                model.flat.refresh_shadow()
+            if n > session.n_inst:
+                raise ValueError("eval_caption_loss: a batch of %d items does not fit the scoring session's %d instances"
+                                 % (n, session.n_inst))
+            if session.n_cand != 1:
+                raise ValueError("eval_caption_loss: the session scores %d captions per item, expected 1" % session.n_cand)
+            r = session.score(so, vo, input_mask, video_mask, cap_in.reshape(n, Wd), cap_mask.reshape(n, Wd), cap_out.reshape(n, Wd),
+                              n_active=None if n == session.n_inst else n)
+            # the one host copy of the batch: three words per item (the int32 counts travel as their bit patterns)
+            packed.append(torch.stack([r.seq_logprob.reshape(-1), r.seq_tokens.reshape(-1).view(torch.float32),
+                                       r.seq_correct.reshape(-1).view(torch.float32)]).cpu())
+    finally:
+        model.train(was_training)
+    if not packed:
+        return CaptionLossResult([], [], [], session)
+    host = torch.cat(packed, dim=1)
+    return CaptionLossResult(host[0].numpy(), host[1].contiguous().view(torch.int32).numpy(), host[2].contiguous().view(torch.int32).numpy(),
+                             session)

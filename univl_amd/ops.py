@@ -554,6 +554,46 @@ def vocab_ce_bwd(desc):
     _lib.check(_lib.lib().univl_vocab_ce_bwd(C.byref(desc), _stream()), "vocab_ce_bwd")
 
 
+def vocab_score_desc(x, table, bias, labels, V, seq_len, ignore_index=-1, out=None):
+    """Descriptor of the scoring form of K16 (include/univl_hip.h: UnivlVocabScore) + the buffers it owns: x [rows, K], table [V(+pad), K]
+    in the compute type, bias [V] fp32 or None, labels [rows] int64; rows = n_seq * seq_len.  out: optional dict of caller-owned output
+    tensors (any of token_logprob, top_token, top_logprob, lse [rows]; seq_logprob, seq_tokens, seq_correct [n_seq]).  Returns
+    (desc, buffers) -- keep `buffers` alive as long as the descriptor is used.  Shapes and dtypes are checked here; the argument RANGE
+    is the library's to refuse."""
+    _require_gpu(x, table, bias, labels)
+    assert x.dim() == 2 and table.dim() == 2 and x.stride(1) == 1 and table.stride(1) == 1 and table.dtype == x.dtype
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous())
+    rows, K = x.shape
+    assert labels.numel() == rows and table.shape[1] == K and table.shape[0] >= V
+    slots = (max(V, 1) + 127) // 128
+    n_seq = rows // seq_len if seq_len > 0 else 0
+    dev = x.device
+    f, i = torch.float32, torch.int32
+    b = dict(partial=torch.empty(rows, slots, 2, device=dev), partial_top=torch.empty(rows, slots, device=dev, dtype=i),
+             label_logit=torch.zeros(rows, device=dev), keep=(x, table, bias, labels))
+    for name, n, dt in (("token_logprob", rows, f), ("top_token", rows, i), ("top_logprob", rows, f), ("lse", rows, f),
+                        ("seq_logprob", n_seq, f), ("seq_tokens", n_seq, i), ("seq_correct", n_seq, i)):
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty(n, device=dev, dtype=dt)
+        _require_gpu(t)
+        assert t.dtype == dt and t.numel() == n and t.is_contiguous(), name
+        b[name] = t
+    d = _lib.VocabScore()
+    d.dtype, d.rows, d.V, d.K = dtype_code(x.dtype), rows, V, K
+    d.x, d.ldx, d.table, d.ldt = _p(x), x.stride(0), _p(table), table.stride(0)
+    d.bias, d.labels, d.ignore_index, d.slots, d.seq_len = _p(bias), _p(labels), ignore_index, slots, seq_len
+    d.partial, d.partial_top, d.label_logit = _p(b["partial"]), _p(b["partial_top"]), _p(b["label_logit"])
+    d.token_logprob, d.top_token, d.top_logprob, d.lse = _p(b["token_logprob"]), _p(b["top_token"]), _p(b["top_logprob"]), _p(b["lse"])
+    d.seq_logprob, d.seq_tokens, d.seq_correct = _p(b["seq_logprob"]), _p(b["seq_tokens"]), _p(b["seq_correct"])
+    return d, b
+
+
+def vocab_score(desc):
+    _lib.check(_lib.lib().univl_vocab_score(C.byref(desc), _stream()), "vocab_score")
+
+
 def mfm_nce_loss(logits, vmask, labels, scratch2, loss, dlogits):
     n = logits.shape[0]
     _lib.check(_lib.lib().univl_mfm_nce_loss(_p(logits), logits.stride(0), _p(vmask), _p(labels), n, _p(scratch2), _p(loss),

@@ -475,7 +475,9 @@ class VocabHead:
     """BertLMPredictionHead tied to BERT's word table + CrossEntropyLoss(ignore_index=-1)
     (module_bert.py:299-330 / module_decoder.py:156-183; modeling.py:252-254, 273-276)."""
 
-    def __init__(self, cx, prefix, T, stream=0):
+    def __init__(self, cx, prefix, T, stream=0, transform_only=False):
+        """transform_only: the buffers of the transform and the labels alone -- no dlogits [T, V] and no backward workspace (score.CaptionScorer
+        feeds the transform's output to univl_vocab_score; build_transform is then the only builder to call)."""
         self.cx, self.prefix, self.T, self.sm = cx, prefix, T, stream
         e, ct, bf = cx.e, cx.ct, cx.bf
         V = cx.model.bert_config.vocab_size
@@ -484,13 +486,15 @@ class VocabHead:
         self.h32 = e(T, H)
         self.h16 = e(T, H, dtype=ct) if bf else self.h32
         self._logits = None                      # materialised only where somebody reads them (evaluation / decoding, vocab_ce=0)
-        self.dlogits = e(T, self.ldv, dtype=ct)
         self.labels = e(T, dtype=torch.int64)
-        self.loss, self.scratch = e(1), e(2)
-        self.dh, self.dg, self.du = e(T, H), e(T, H), e(T, H, dtype=ct)
         # K16 (univl_vocab_ce_fwd / _bwd): per-row (max, sum exp) pairs of the 128-column tiles, the label's logit, the row's log-sum-exp
         self.k16 = None
         self.slots = (V + 127) // 128
+        if transform_only:
+            return
+        self.dlogits = e(T, self.ldv, dtype=ct)
+        self.loss, self.scratch = e(1), e(2)
+        self.dh, self.dg, self.du = e(T, H), e(T, H), e(T, H, dtype=ct)
 
     @property
     def logits(self):
@@ -519,13 +523,19 @@ class VocabHead:
         return dict(tw=p + ".transform.dense.weight", tb=p + ".transform.dense.bias", lg=p + ".transform.LayerNorm.weight",
                     lb=p + ".transform.LayerNorm.bias", bias=p + ".bias", emb="bert.embeddings.word_embeddings.weight")
 
-    def build_forward(self, fwd, x16, with_loss=True):
+    def build_transform(self, fwd, x16):
+        """BertPredictionHeadTransform (dense + GELU + LayerNorm, module_bert.py:299-311): x16 -> self.h16"""
         cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
         W32 = fl.w32
         fwd.add("univl_gemm", _gemm_desc(dt, x16, H, fl.wop(n["tw"]), H, T, H, H, out32=self.hy, ldc=H, bias=W32(n["tb"]),
                                          aux=self.u, ldaux=H, gelu="fwd"), sm)
         fwd.add("univl_layernorm_fwd", ops.layernorm_desc(dt, T, H, x=self.hy, gamma=W32(n["lg"]), beta=W32(n["lb"]), y=self.hy,
                                                           stats=self.hst, out32=self.h32, out16=self.h16 if cx.bf else None), sm)
+
+    def build_forward(self, fwd, x16, with_loss=True):
+        cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
+        W32 = fl.w32
+        self.build_transform(fwd, x16)
         if with_loss and _ab.get("vocab_ce"):
             # K16: the product's epilogue keeps the online log-softmax statistics; the [T, 30522] logits never exist (module_bert.py:327-330 +
             # modeling.py:253 / 275 in one entry point); the backward recomputes the product into dlogits
