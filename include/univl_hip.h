@@ -40,6 +40,10 @@ int univl_version(void);
 /* sizeof of ABI struct #which (0 Gemm, 1 LayerNorm, 2 Attention, 3 EmbedText, 4 Pool, 5 Seg, 6 Adam, 7 VocabCE, 8 BeamStep, 9 SimTopk, 10 VocabScore) -- lets a
  * foreign-language binding verify its struct mirrors at load time */
 int univl_struct_size(int which);
+/* The same table, continued: 0 .. 10 as univl_struct_size, 11 SampleStep; -1 past the end.  univl_struct_size itself stays at the
+ * eleven structs it has always listed -- bindings pin the -1 it returns for the first index past them -- and descriptors added from
+ * here on are numbered in this table only. */
+int univl_abi_sizeof(int which);
 /* number of CUs / name of the current device, for host-side launch heuristics; returns 0 or hipError_t */
 int univl_device_info(int* cu_count, char* name, int name_len);
 /* univl_init(device): optional, idempotent.  Checks that `device` exists and is a gfx950 part (the only code object in the
@@ -411,6 +415,57 @@ int univl_beam_backtrack(const int32_t* hist_parents, const int32_t* hist_tokens
  * 1 <= n_best <= UNIVL_BEAM_MAX, n_inst >= 1, Tmax >= 1, otherwise UNIVL_EINVAL. */
 int univl_beam_captions(const int32_t* hyp, const int32_t* length, int32_t n_inst, int32_t n_best, int32_t Tmax, int32_t eos, int32_t pad,
                         const int32_t* eos_dev, int32_t* cap_tokens, int32_t* cap_len, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- caption sampling
+ * One position of ancestral sampling (top-k, temperature, top-p) for R independent rows, entirely in device memory: two launches, no
+ * host involvement, capturable.  It reads the RAW logits x [R, ld] fp32 that the vocabulary classifier leaves -- no
+ * univl_log_softmax_rows in front of it; only columns < V are candidates, columns V .. ld-1 are padding and never are.
+ * Per row r with done[r] == 0 at position t:
+ *   1. TOP-K: the k largest x[r, v], descending, x_0 >= ... >= x_{k-1} at columns col_j.  TIE RULE (the one univl_beam_step,
+ *      univl_sim_topk and univl_vocab_score fix): equal fp32 values are ordered by LOWER column first.
+ *   2. WEIGHTS: w_j = expf((x_j - x_0) * inv_T), inv_T = 1 / temperature computed by the host in fp32; the subtraction and the
+ *      multiplication are two separately rounded fp32 operations (no fma across them).
+ *   3. CUMULATIVE SUMS: c_0 = w_0, c_j = c_{j-1} + w_j, ONE left-to-right fp32 chain.
+ *   4. NUCLEUS: m = the smallest count with c_{m-1} >= top_p * c_{k-1} (one fp32 product); top_p >= 1 means m = k exactly.
+ *   5. DRAW: r32 = mix32((seed * 0x9E3779B97F4A7C15) ^ (t * 0xD1B54A32D192ED03 + r)) -- the generator and keying of the dropout masks
+ *      (offset t, index r; 64-bit wrap-around arithmetic, mix32 = the murmur3 finaliser's low word), u = (r32 >> 8) * 2^-24,
+ *      tau = u * c_{m-1} (fp32), j* = the first j < m with c_j > tau.
+ *   6. OUTPUTS: tokens_out[r, t] = ids[r] = col_{j*};
+ *      tok_logprob[r, t] = (x_{j*} - max) - log(sum_v exp(x_v - max)), max and the sum over all V columns: the model's own
+ *      log-probability at temperature 1, formed as written (an fp32 difference, then the logarithm subtracted), never as a difference
+ *      of two numbers of the size of the log-sum-exp;   q_logprob[r, t] = log(w_{j*} / c_{m-1}), the proposal's log-probability;
+ *      seq_logprob[r] += tok_logprob, seq_q_logprob[r] += q_logprob (one fp32 addition each, so over positions each is the same
+ *      left-to-right fp32 sum a host forms from the [R, Tmax] arrays);  length[r] += 1;  done[r] <- 1 if col_{j*} == eos.
+ * A row with done[r] != 0 is FROZEN: nothing of it is written and ids[r] stays.  done is per ROW here.
+ * The two logarithms of step 6 are evaluated in fp64 and rounded to fp32 once; the sum of exponentials (fp32 terms) is carried in
+ * fp64.  Behaviour on NaN logits: unspecified, but every index written stays in range.
+ * REPRODUCIBILITY: every reduction has a fixed order and there are no atomics; a row's outputs are a pure function of its V logits,
+ * k, inv_T, top_p, seed, t and r -- not of R, of other rows, of deterministic mode or of how the row was cut into column slices
+ * (the slice count depends on V alone).
+ * inv_T / top_p / seed / eos may each come from DEVICE words instead (sampling_dev, seed_dev, eos_dev), so that one captured hipGraph
+ * serves every temperature, nucleus, seed and end token; the library cannot range-check device words, that is then the caller's.
+ * Range: R >= 1, 1 <= k <= min(UNIVL_SAMPLE_KMAX, V), V <= ld, 0 <= t < Tmax, and without sampling_dev inv_T finite and > 0 and
+ * top_p > 0; otherwise, for a NULL pointer (the optional ones apart) or a short workspace, UNIVL_EINVAL and nothing is launched. */
+#define UNIVL_SAMPLE_KMAX 64
+#define UNIVL_SAMPLE_SLICES 8        /* most column slices a row is scanned in (sizes the workspace) */
+typedef struct UnivlSampleStep {
+    const float* x; int64_t ld;      /* [R, ld] fp32 raw logits                                                                   */
+    int32_t R, V, k;
+    int32_t t, Tmax;                 /* column of the [R, Tmax] outputs written by this call; the offset of the draw              */
+    int32_t eos;                     /* token that ends a row (-1: none)                                                          */
+    float inv_T, top_p;
+    uint64_t seed;
+    const float* sampling_dev;       /* optional device {inv_T, top_p} read INSTEAD of the two fields                             */
+    const uint64_t* seed_dev;        /* optional device word read INSTEAD of seed                                                 */
+    const int32_t* eos_dev;          /* optional device word read INSTEAD of eos (as UnivlBeamStep.eos_dev)                       */
+    uint8_t* done;                   /* [R]        read and written                                                               */
+    int32_t* length;                 /* [R]        read and written                                                               */
+    int64_t* ids;                    /* [R]        written: the ids the next position's univl_embed_text_fwd reads                */
+    int32_t* tokens_out; float* tok_logprob; float* q_logprob;       /* [R, Tmax] each; column t written                         */
+    float* seq_logprob; float* seq_q_logprob;                         /* [R] each, read and written                               */
+    int32_t* topk_idx; float* topk_val;                               /* optional [R, k] each: the list of step 1 (written)      */
+    void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch of >= R * UNIVL_SAMPLE_SLICES * (8 * k + 16) bytes                */
+} UnivlSampleStep;
+int univl_sample_step(const UnivlSampleStep* d, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------- retrieval search
  * The k best gallery rows of every query row by inner product -- torch.matmul(text, video.t()) of modeling.py:389 followed by a
  * row-wise top-k -- WITHOUT the [Nq, Ng] score matrix: the 768-deep product's epilogue keeps a running top-k per query and never

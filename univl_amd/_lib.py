@@ -88,10 +88,18 @@ class VocabScore(C.Structure):
                 ("seq_logprob", vp), ("seq_tokens", vp), ("seq_correct", vp)]
 
 
+class SampleStep(C.Structure):
+    _fields_ = [("x", vp), ("ld", i64), ("R", i32), ("V", i32), ("k", i32), ("t", i32), ("Tmax", i32), ("eos", i32), ("inv_T", f32),
+                ("top_p", f32), ("seed", u64), ("sampling_dev", vp), ("seed_dev", vp), ("eos_dev", vp), ("done", vp), ("length", vp),
+                ("ids", vp), ("tokens_out", vp), ("tok_logprob", vp), ("q_logprob", vp), ("seq_logprob", vp), ("seq_q_logprob", vp),
+                ("topk_idx", vp), ("topk_val", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 BEAM_MAX, BEAM_SLICES = 8, 8       # include/univl_hip.h: UNIVL_BEAM_MAX, UNIVL_BEAM_SLICES
 TOPK_MAX, TOPK_SLICES_MAX = 64, 256   # include/univl_hip.h: UNIVL_TOPK_MAX, UNIVL_TOPK_SLICES_MAX
+SAMPLE_KMAX, SAMPLE_SLICES = 64, 8    # include/univl_hip.h: UNIVL_SAMPLE_KMAX, UNIVL_SAMPLE_SLICES
 
-_STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk, VocabScore]
+_STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk, VocabScore, SampleStep]
 _lib = None
 
 
@@ -110,13 +118,15 @@ def lib():
     L = C.CDLL(LIB_PATH)
     L.univl_last_error.restype = C.c_char_p
     L.univl_struct_size.argtypes = [i32]
+    L.univl_abi_sizeof.argtypes = [i32]
     for k, st in enumerate(_STRUCTS):
-        n = L.univl_struct_size(k)
+        n = L.univl_abi_sizeof(k)          # univl_struct_size's table, continued past its eleven entries (include/univl_hip.h)
         if n != C.sizeof(st):
             raise RuntimeError("ABI mismatch for %s: library %d bytes, ctypes %d" % (st.__name__, n, C.sizeof(st)))
     for name in ("univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_gemm", "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd",
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
-                 "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score"):
+                 "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score",
+                 "univl_sample_step"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_pool_pair_fwd.argtypes = [vp, vp, vp]
@@ -198,12 +208,12 @@ def set_deterministic(on=True):
     check(lib().univl_set_deterministic(1 if on else 0), "set_deterministic")
 
 
-EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_device_info", "univl_init", "univl_destroy",
+EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi_sizeof", "univl_device_info", "univl_init", "univl_destroy",
             "univl_allreduce_bucket", "univl_set_deterministic", "univl_get_deterministic", "univl_gemm", "univl_gemm_group_limited", "univl_gemm_group", "univl_gemm_tile_map", "univl_gemm256_layout", "univl_gemm_pair", "univl_gemm_rider", "univl_gemm_rider_fits", "univl_gemm_rider_prime", "univl_gemm_ln", "univl_gemm_pair_ln",
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

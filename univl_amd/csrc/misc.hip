@@ -38,6 +38,13 @@ extern "C" int univl_struct_size(int which) {
     }
 }
 
+extern "C" int univl_abi_sizeof(int which) {
+    switch (which) {
+        case 11: return (int)sizeof(UnivlSampleStep);
+        default: return which < 11 ? univl_struct_size(which) : -1;
+    }
+}
+
 extern "C" int univl_device_info(int* cu_count, char* name, int name_len) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);

@@ -139,7 +139,9 @@ class CaptionBeamSearch:
     def _step_plan(self, t, beam=False):
         """The plan of position t.  beam=False: embedding .. log-probabilities (what step_logprobs replays; it neither reads nor
         advances the beam state).  beam=True: a second captured form of the same launches with univl_beam_step as its last entry
-        (t, the history row and first_step are baked into that position's descriptor)."""
+        (t, the history row and first_step are baked into that position's descriptor).  A subclass may name further forms
+        (sample.CaptionSampler): _reorders(form) says whether rows change places between positions, _plan_tail(pl, t, form) adds
+        what follows the vocabulary classifier."""
         pl = self.steps.get((t, beam))
         if pl is not None:
             return pl
@@ -147,7 +149,8 @@ class CaptionBeamSearch:
         W32 = fl.w32
         es = 2 if cx.bf else 4
         pl = Plan()
-        cur, prev = t % 2, (t + 1) % 2
+        reorder = self._reorders(beam)
+        cur, prev = (t % 2, (t + 1) % 2) if reorder else (0, 0)     # rows that stay where they are need one cache buffer and no gather
         pos = W32("bert.embeddings.position_embeddings.weight")[t:]
         pl.add("univl_embed_text_fwd", ops.embed_text_desc(
             dt, R, 1, self.ids, W32("bert.embeddings.word_embeddings.weight"), pos, W32("decoder.embeddings.LayerNorm.weight"),
@@ -159,7 +162,7 @@ class CaptionBeamSearch:
             lay = DecoderLayer(pl, fl, l, ws, R)
             nm = lay.nm
             cache = self.cache[l][cur]
-            if t > 0:        # beams continue from re-ordered parents: gather positions [0, t) of the parent rows
+            if t > 0 and reorder:        # beams continue from re-ordered parents: gather positions [0, t) of the parent rows
                 src_c, n_rows, stride, nbytes = self.cache[l][prev], R, Tmax * 2 * H * es, t * 2 * H * es
                 pl.add_callable(lambda s=src_c, d=cache, st=stride, nb=nbytes: ops.gather_rows(s, d, self.src, R, st, nb))
             wqkv, bqkv = fl.wop_fused(nm["s_qkv_w"]), fl.w32_fused(nm["s_qkv_b"])
@@ -176,15 +179,21 @@ class CaptionBeamSearch:
             lay.ffn()
             x32, x16 = ws["o32"], ws["o16"]
         self.head.build_forward(pl, x16, with_loss=False)
+        self._plan_tail(pl, t, beam)
+        pl.keepalive = (pos,)
+        self.steps[(t, beam)] = pl
+        return pl
+
+    def _reorders(self, form):
+        return True
+
+    def _plan_tail(self, pl, t, beam):
         pl.add_callable(lambda: ops.log_softmax_rows(self.head.logits, self.V))
         if beam:
             pl.add("univl_beam_step", ops.beam_step_desc(
                 self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done, length=self.length,
                 tokens=self.ids, src=self.src, hist_parents=self.hist_par, hist_tokens=self.hist_tok, hist_scores=self.hist_sc,
                 ws=self.beam_ws, eos_dev=self.eos_dev))
-        pl.keepalive = (pos,)
-        self.steps[(t, beam)] = pl
-        return pl
 
     # ------------------------------------------------------------------------------------------------- run
     @torch.no_grad()

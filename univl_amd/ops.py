@@ -385,6 +385,48 @@ def beam_step(*a, **kw):
     _lib.check(_lib.lib().univl_beam_step(_BYREF(d), _stream()), "beam_step")
 
 
+def sample_ws(R, k, device):
+    """Scratch of univl_sample_step for R rows and a top-k of k (include/univl_hip.h: UnivlSampleStep.ws)."""
+    return torch.empty(R * _lib.SAMPLE_SLICES * (2 * k + 4), dtype=torch.float32, device=device)
+
+
+def sample_step_desc(x, V, k, t, *, done, length, ids, tokens_out, tok_logprob, q_logprob, seq_logprob, seq_q_logprob, ws, inv_T=1.0,
+                     top_p=1.0, seed=0, eos=-1, sampling_dev=None, seed_dev=None, eos_dev=None, topk_idx=None, topk_val=None):
+    """x: [R, ld] fp32 view of raw logits (row stride ld >= V); state / outputs as in include/univl_hip.h: UnivlSampleStep.
+    sampling_dev: fp32 [2] device {inv_T, top_p}; seed_dev: one 64-bit device word (int64 storage, read as uint64); eos_dev: int32
+    device word -- each read instead of the scalar.  Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
+    _require_gpu(x, done, length, ids, tokens_out, tok_logprob, q_logprob, seq_logprob, seq_q_logprob, ws, sampling_dev, seed_dev,
+                 eos_dev, topk_idx, topk_val)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    R = x.shape[0]
+    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == R and length.dtype == torch.int32 and length.numel() == R
+    assert ids.dtype == torch.int64 and ids.numel() == R
+    Tmax = tokens_out.shape[1]
+    for h, dt_ in ((tokens_out, torch.int32), (tok_logprob, torch.float32), (q_logprob, torch.float32)):
+        assert h.dtype == dt_ and h.is_contiguous() and h.shape == (R, Tmax)
+    for h in (seq_logprob, seq_q_logprob):
+        assert h.dtype == torch.float32 and h.numel() == R and h.is_contiguous()
+    assert sampling_dev is None or (sampling_dev.dtype == torch.float32 and sampling_dev.numel() == 2)
+    assert seed_dev is None or (seed_dev.dtype == torch.int64 and seed_dev.numel() == 1)
+    assert eos_dev is None or eos_dev.dtype == torch.int32
+    assert topk_idx is None or (topk_idx.dtype == torch.int32 and topk_idx.is_contiguous() and topk_idx.shape == (R, k))
+    assert topk_val is None or (topk_val.dtype == torch.float32 and topk_val.is_contiguous() and topk_val.shape == (R, k))
+    d = _lib.SampleStep()
+    d.x, d.ld, d.R, d.V, d.k, d.t, d.Tmax, d.eos = _p(x), x.stride(0), R, V, k, t, Tmax, int(eos)
+    d.inv_T, d.top_p, d.seed = inv_T, top_p, int(seed) & 0xFFFFFFFFFFFFFFFF
+    d.sampling_dev, d.seed_dev, d.eos_dev = _p(sampling_dev), _p(seed_dev), _p(eos_dev)
+    d.done, d.length, d.ids = _p(done), _p(length), _p(ids)
+    d.tokens_out, d.tok_logprob, d.q_logprob = _p(tokens_out), _p(tok_logprob), _p(q_logprob)
+    d.seq_logprob, d.seq_q_logprob, d.topk_idx, d.topk_val = _p(seq_logprob), _p(seq_q_logprob), _p(topk_idx), _p(topk_val)
+    d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
+    return d
+
+
+def sample_step(*a, **kw):
+    d = sample_step_desc(*a, **kw)
+    _lib.check(_lib.lib().univl_sample_step(_BYREF(d), _stream()), "sample_step")
+
+
 def beam_backtrack(hist_parents, hist_tokens, scores, length, n_best):
     """Walk the n_best best beams of every instance back through the history (include/univl_hip.h: univl_beam_backtrack).
     Returns (hyp [n, n_best, Tmax] int32, -1 padded; hyp_scores [n, n_best] fp32)."""
