@@ -466,6 +466,64 @@ typedef struct UnivlSampleStep {
     void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch of >= R * UNIVL_SAMPLE_SLICES * (8 * k + 16) bytes                */
 } UnivlSampleStep;
 int univl_sample_step(const UnivlSampleStep* d, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- caption metrics
+ * N-gram overlap statistics of token rows, per item, in one launch with no host involvement (capturable): the integers BLEU is made
+ * of, the longest common subsequences and ROUGE_L, and, given document-frequency tables, CIDEr.  An ITEM is one hypothesis row and a
+ * list of reference rows of the same table sym [rows, ld] int32 (T columns used) with lengths len [rows]; items may share rows:
+ *   hypothesis of item i = row hyp_row[i];  references = rows ref_rows[ref_begin[i] .. ref_begin[i + 1]), n_refs = ref_begin[items].
+ * Only the first len[row] symbols of a row are read.  An n-gram (n = 1 .. 4) is compared through its exact 64-bit key
+ * sum_{j < n} (s_j + 1) << 16 j, so keys of different n never meet.  With L = len of the hypothesis, per item i:
+ *   guess[i, n-1]   = max(0, L - n + 1)
+ *   correct[i, n-1] = sum over the hypothesis' distinct n-grams g of min(count_hyp(g), max over the references of count_ref(g))
+ *   hyp_len[i] = L;  ref_len[i] = the reference length l that minimises (|l - L|, l)   (bleu_scorer's "closest")
+ *   lcs[ref_begin[i] + r] = length of the longest common subsequence of the hypothesis and reference r
+ *   rouge_l[i] = (1 + b^2) p q / (q + b^2 p) with b = 1.2, p = max_r lcs_r / max(L, 1), q = max_r (lcs_r / max(len_r, 1)); 0 when p or q is 0
+ *   bleu[i] (optional) = the sentence form of BLEU-4 on the item's own counts: (prod_n (correct_n + 1e-15) / (guess_n + 1e-9))^(1/4),
+ *      times exp(1 - 1 / ratio) when ratio = (L + 1e-15) / (ref_len + 1e-9) < 1
+ *   cider[i] (optional; needs the tables) = 10 x mean over the references of the mean over n of val_n, where with
+ *      idf(g) = log(n_docs) - log(max(1, df(g))), df(g) looked up by binary search (0 when absent), the tf-idf vectors of the hypothesis
+ *      and of the reference over their distinct n-grams and their Euclidean norms:  val_n = sum over the hypothesis' distinct g of
+ *      min(tf_h idf, tf_r idf) * (tf_r idf), divided by norm_h norm_r when both are non-zero, times exp(-d^2 / (2 * 6^2)),
+ *      d = max(L - 1, 0) - max(len_r - 1, 0)   (cider_scorer's "length" is the bigram count).
+ * TABLES: df_keys (ascending uint64) / df_cnt (int32) hold the four per-n tables one after the other, the n-th in entries
+ * df_begin[n-1] .. df_begin[n) (HOST words; the keys' construction makes the whole array ascending too).
+ * The integers are exact.  The fp64 values are sums in a fixed order (no atomics on them); they do not depend on the number of items.
+ * RANGE: 1 <= T <= UNIVL_OVERLAP_TMAX, T <= ld, rows >= 1, 1 <= items <= n_refs, cider only with n_docs >= 1 and consistent df_begin;
+ * otherwise, or for a NULL pointer (the optional ones apart), UNIVL_EINVAL and nothing is launched.  What is DATA ON THE DEVICE is
+ * clamped and flagged instead, nothing is read out of range: the bits below are OR-ed into *status (the caller clears it) when a length
+ * is outside [0, T], a symbol read is outside [0, UNIVL_OVERLAP_SYM_MAX], a row index is outside [0, rows), or an item's reference
+ * offsets leave [0, n_refs] or give it no reference; the outputs of such an item are then those of the clamped data. */
+#define UNIVL_OVERLAP_TMAX 128
+#define UNIVL_OVERLAP_SYM_MAX 65534
+#define UNIVL_OVERLAP_BAD_LEN 1
+#define UNIVL_OVERLAP_BAD_SYM 2
+#define UNIVL_OVERLAP_BAD_ROW 4
+#define UNIVL_OVERLAP_BAD_REFS 8
+typedef struct UnivlCaptionOverlap {
+    const int32_t* sym; int64_t ld;  /* [rows, ld] int32 symbols                                                                  */
+    const int32_t* len;              /* [rows]                                                                                    */
+    int32_t rows, T, items, n_refs;
+    const int32_t* hyp_row;          /* [items]                                                                                   */
+    const int32_t* ref_begin;        /* [items + 1]                                                                               */
+    const int32_t* ref_rows;         /* [n_refs]                                                                                  */
+    const uint64_t* df_keys;         /* [df_begin[4]] or NULL                                                                     */
+    const int32_t* df_cnt;           /* [df_begin[4]] or NULL                                                                     */
+    int32_t df_begin[5];
+    int32_t n_docs;
+    int32_t* guess; int32_t* correct;            /* [items, 4] each                                                               */
+    int32_t* hyp_len; int32_t* ref_len;          /* [items] each                                                                  */
+    int32_t* lcs;                    /* [n_refs]                                                                                  */
+    double* rouge_l;                 /* [items]                                                                                   */
+    double* cider;                   /* [items] or NULL                                                                           */
+    double* bleu;                    /* [items] or NULL                                                                           */
+    int32_t* status;                 /* one word, bits OR-ed in                                                                   */
+} UnivlCaptionOverlap;
+/* sizeof(UnivlCaptionOverlap), for a binding's load-time check.  (The two numbered size tables above keep the lengths bindings pin.) */
+int univl_caption_overlap_sizeof(void);
+int univl_caption_overlap(const UnivlCaptionOverlap* d, hipStream_t stream);
+/* pick[i] = the index of the largest of score[i, 0 .. n_samp) (fp64), equal scores resolving to the LOWER index (the tie rule of
+ * univl_beam_step); best[i] (optional) = that score.  A NaN is never the larger one.  n_inst, n_samp >= 1, otherwise UNIVL_EINVAL. */
+int univl_consensus_pick(const double* score, int32_t n_inst, int32_t n_samp, int32_t* pick, double* best, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------- retrieval search
  * The k best gallery rows of every query row by inner product -- torch.matmul(text, video.t()) of modeling.py:389 followed by a
  * row-wise top-k -- WITHOUT the [Nq, Ng] score matrix: the 768-deep product's epilogue keeps a running top-k per query and never

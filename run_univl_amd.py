@@ -12,7 +12,8 @@ Nothing of the reference is edited or copied.  Before the script runs, this file
   * restores what newer libraries removed under the reference's feet: `np.float` & friends (used by every dataloader, e.g.
     dataloaders/dataloader_youcook_retrieval.py:139; gone since NumPy 1.24), `boto3` / `botocore` imports of
     modules/file_utils.py:20-21 (only needed for S3 downloads) and `nlgeval` of main_task_caption.py:12 when they are not
-    installed (stubs that fail only when really used);
+    installed (boto3: a stub that fails only when really used; nlgeval: an NLGEval whose compute_metrics is
+    univl_amd.caption_metrics.CaptionMetrics -- BLEU, ROUGE_L and CIDEr from the device kernel, METEOR nan);
   * translates the `--local-rank` flag that torch >= 2.0 launchers pass into the `--local_rank` the scripts declare
     (main_task_retrieval.py:83), and fills it from LOCAL_RANK when the launcher passes neither;
   * supplies single-process rendezvous defaults (RANK=0, WORLD_SIZE=1, MASTER_ADDR=127.0.0.1, a free MASTER_PORT) so that the
@@ -53,12 +54,16 @@ def install_compat():
     except ImportError:
         ng = types.ModuleType("nlgeval")
 
-        class NLGEval:              # main_task_caption.py:12,612: caption metrics need the Java-based package
-            def __init__(self, *a, **k):
+        class NLGEval:              # main_task_caption.py:12,612: the Java-based package is absent; BLEU / ROUGE_L / CIDEr come
+            def __init__(self, *a, **k):    # from univl_amd.caption_metrics (METEOR is nan).  NLGEval's keywords are ignored.
                 pass
 
-            def compute_metrics(self, *a, **k):
-                raise RuntimeError("nlgeval is not installed: BLEU/METEOR/ROUGE/CIDEr are unavailable (run_univl_amd.py stub)")
+            def compute_metrics(self, ref_list, hyp_list):
+                """Called at the END of an evaluation epoch (main_task_caption.py:612), after the whole test set was decoded: a
+                caption of more than 128 words is cut with a warning instead of raising there (truncate=True).  Malformed lists
+                (lengths that disagree, more than 65534 distinct words) still raise ValueError."""
+                from univl_amd.caption_metrics import CaptionMetrics
+                return CaptionMetrics(truncate=True).compute_metrics(ref_list=ref_list, hyp_list=hyp_list)
         ng.NLGEval = NLGEval
         sys.modules["nlgeval"] = ng
 

@@ -95,9 +95,20 @@ class SampleStep(C.Structure):
                 ("topk_idx", vp), ("topk_val", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+class CaptionOverlap(C.Structure):
+    """include/univl_hip.h: UnivlCaptionOverlap.  Not in _STRUCTS: the numbered size tables keep their lengths, the library states
+    this struct's size through univl_caption_overlap_sizeof (checked in lib())."""
+    _fields_ = [("sym", vp), ("ld", i64), ("len", vp), ("rows", i32), ("T", i32), ("items", i32), ("n_refs", i32), ("hyp_row", vp),
+                ("ref_begin", vp), ("ref_rows", vp), ("df_keys", vp), ("df_cnt", vp), ("df_begin", i32 * 5), ("n_docs", i32),
+                ("guess", vp), ("correct", vp), ("hyp_len", vp), ("ref_len", vp), ("lcs", vp), ("rouge_l", vp), ("cider", vp),
+                ("bleu", vp), ("status", vp)]
+
+
 BEAM_MAX, BEAM_SLICES = 8, 8       # include/univl_hip.h: UNIVL_BEAM_MAX, UNIVL_BEAM_SLICES
 TOPK_MAX, TOPK_SLICES_MAX = 64, 256   # include/univl_hip.h: UNIVL_TOPK_MAX, UNIVL_TOPK_SLICES_MAX
 SAMPLE_KMAX, SAMPLE_SLICES = 64, 8    # include/univl_hip.h: UNIVL_SAMPLE_KMAX, UNIVL_SAMPLE_SLICES
+OVERLAP_TMAX, OVERLAP_SYM_MAX = 128, 65534   # include/univl_hip.h: UNIVL_OVERLAP_TMAX, UNIVL_OVERLAP_SYM_MAX
+OVERLAP_BAD_LEN, OVERLAP_BAD_SYM, OVERLAP_BAD_ROW, OVERLAP_BAD_REFS = 1, 2, 4, 8
 
 _STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk, VocabScore, SampleStep]
 _lib = None
@@ -126,9 +137,16 @@ def lib():
     for name in ("univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_gemm", "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd",
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
                  "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score",
-                 "univl_sample_step"):
+                 "univl_sample_step", "univl_caption_overlap"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
+    L.univl_caption_overlap_sizeof.argtypes = []
+    L.univl_caption_overlap_sizeof.restype = i32
+    if L.univl_caption_overlap_sizeof() != C.sizeof(CaptionOverlap):
+        raise RuntimeError("ABI mismatch for CaptionOverlap: library %d bytes, ctypes %d"
+                           % (L.univl_caption_overlap_sizeof(), C.sizeof(CaptionOverlap)))
+    L.univl_consensus_pick.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.univl_consensus_pick.restype = i32
     L.univl_pool_pair_fwd.argtypes = [vp, vp, vp]
     L.univl_pool_pair_bwd.argtypes = [vp, vp, vp]
     L.univl_gemm_group.argtypes = [vp, i32, vp]
@@ -213,7 +231,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_consensus_pick", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

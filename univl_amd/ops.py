@@ -427,6 +427,55 @@ def sample_step(*a, **kw):
     _lib.check(_lib.lib().univl_sample_step(_BYREF(d), _stream()), "sample_step")
 
 
+def caption_overlap(sym, length, hyp_row, ref_begin, ref_rows, n_refs, *, tables=None, bleu=False, status=None):
+    """N-gram overlap statistics per item (include/univl_hip.h: univl_caption_overlap), one launch, nothing read on the host.
+    sym: [rows, T] int32 (row stride >= T), length: [rows] int32; hyp_row [items], ref_begin [items + 1], ref_rows [n_refs] int32 device
+    tensors; n_refs: the HOST's statement of ref_begin[items].  tables: None, or (df_keys int64 storage of the uint64 keys, df_cnt int32,
+    df_begin: five host ints, n_docs) -- then CIDEr is computed.  bleu: also the sentence BLEU-4 of every item.  status: an int32 device
+    word the flags are OR-ed into (default: a fresh zero).  Returns a dict of device tensors: guess / correct [items, 4] int32, hyp_len /
+    ref_len [items] int32, lcs [n_refs] int32, rouge_l [items] fp64, cider / bleu [items] fp64 or None, status [1] int32."""
+    _require_gpu(sym, length, hyp_row, ref_begin, ref_rows, status)
+    assert sym.dtype == torch.int32 and sym.dim() == 2 and sym.stride(1) == 1
+    rows, T = sym.shape
+    items, dev = hyp_row.numel(), sym.device
+    for h, n in ((length, rows), (hyp_row, items), (ref_begin, items + 1), (ref_rows, int(n_refs))):
+        assert h.dtype == torch.int32 and h.is_contiguous() and h.numel() == n
+    d = _lib.CaptionOverlap()
+    d.sym, d.ld, d.len, d.rows, d.T, d.items, d.n_refs = _p(sym), sym.stride(0), _p(length), rows, T, items, int(n_refs)
+    d.hyp_row, d.ref_begin, d.ref_rows = _p(hyp_row), _p(ref_begin), _p(ref_rows)
+    out = dict(guess=torch.empty(items, 4, dtype=torch.int32, device=dev), correct=torch.empty(items, 4, dtype=torch.int32, device=dev),
+               hyp_len=torch.empty(items, dtype=torch.int32, device=dev), ref_len=torch.empty(items, dtype=torch.int32, device=dev),
+               lcs=torch.zeros(int(n_refs), dtype=torch.int32, device=dev), rouge_l=torch.empty(items, dtype=torch.float64, device=dev),
+               cider=None, bleu=torch.empty(items, dtype=torch.float64, device=dev) if bleu else None,
+               status=torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status)
+    if tables is not None:
+        df_keys, df_cnt, df_begin, n_docs = tables
+        _require_gpu(df_keys, df_cnt)
+        assert len(df_begin) == 5 and df_keys.dtype == torch.int64 and df_cnt.dtype == torch.int32
+        assert df_keys.is_contiguous() and df_cnt.is_contiguous() and df_keys.numel() == df_cnt.numel() == int(df_begin[4])
+        d.df_keys, d.df_cnt, d.n_docs = _p(df_keys), _p(df_cnt), int(n_docs)
+        for n in range(5):
+            d.df_begin[n] = int(df_begin[n])
+        out["cider"] = torch.empty(items, dtype=torch.float64, device=dev)
+    assert out["status"].dtype == torch.int32 and out["status"].numel() == 1
+    d.guess, d.correct, d.hyp_len, d.ref_len, d.lcs = (_p(out[k]) for k in ("guess", "correct", "hyp_len", "ref_len", "lcs"))
+    d.rouge_l, d.cider, d.bleu, d.status = _p(out["rouge_l"]), _p(out["cider"]), _p(out["bleu"]), _p(out["status"])
+    _lib.check(_lib.lib().univl_caption_overlap(_BYREF(d), _stream()), "caption_overlap")
+    return out
+
+
+def consensus_pick(score):
+    """score: [n_inst, n_samp] fp64 device tensor -> (pick [n_inst] int32, best [n_inst] fp64): the arg-max of every row, equal scores
+    to the lower index (include/univl_hip.h: univl_consensus_pick)."""
+    _require_gpu(score)
+    assert score.dtype == torch.float64 and score.dim() == 2 and score.is_contiguous()
+    n, ns = score.shape
+    pick = torch.empty(n, dtype=torch.int32, device=score.device)
+    best = torch.empty(n, dtype=torch.float64, device=score.device)
+    _lib.check(_lib.lib().univl_consensus_pick(_p(score), n, ns, _p(pick), _p(best), _stream()), "consensus_pick")
+    return pick, best
+
+
 def beam_backtrack(hist_parents, hist_tokens, scores, length, n_best):
     """Walk the n_best best beams of every instance back through the history (include/univl_hip.h: univl_beam_backtrack).
     Returns (hyp [n, n_best, Tmax] int32, -1 padded; hyp_scores [n, n_best] fp32)."""
