@@ -1,0 +1,126 @@
+"""One fixed, seeded input set through the evaluation entry points that share csrc/ranked.h and csrc/vocab_ce.h, every output tensor
+written to an .npz: run it once per build of the library, each in a fresh process, and compare the files with numpy.array_equal.
+
+    python scripts/ab_eval_kernels_bitwise.py <libunivl_hip.so> <out.npz>
+
+Entry points: univl_beam_step (a first and a later step, n_bm = 5), univl_sample_step (k = 50), univl_sim_topk (Nq = 33, Ng = 300,
+k = 10, with a target), univl_vocab_score, univl_vocab_ce_fwd / _bwd.  Every input set holds engineered ties: equal values whose
+order only the tie rule (lower index first) decides."""
+import os
+import sys
+
+import numpy as np
+
+
+def main(lib_path, out_path):
+    os.environ["UNIVL_LIB"] = os.path.abspath(lib_path)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from univl_amd import _lib, ops
+    assert os.path.samefile(_lib.LIB_PATH, lib_path)
+    dev = "cuda"
+    out = {}
+
+    def gen(*shape, seed, scale=1.0):
+        return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
+
+    def keep(prefix, **ts):
+        torch.cuda.synchronize()
+        for k, t in ts.items():
+            t = t.detach().cpu()
+            out[prefix + "." + k] = (t.view(torch.int16) if t.dtype == torch.bfloat16 else t).numpy()
+
+    # ---- univl_beam_step: 4 instances x 5 beams, V = 30522 (row stride 30528); ties inside a row, across slices and across beams
+    n_inst, nb, V, LD, Tmax = 4, 5, 30522, 30528, 4
+    R = n_inst * nb
+    lp = torch.log_softmax(gen(R, LD, seed=11), 1)
+    top = float(lp.max()) + 1.0
+    lp[0, [7, 8, 20000, 30521]] = top                  # first step reads row 0 of an instance: four equal best, two slices
+    lp[5, [100, 101]] = top
+    lp[6, 3] = lp[7, 3] = top + 1.0                    # later step: with equal scores, beams 1 and 2 of instance 1 tie on a flat index
+    lp[6, 30000] = lp[7, 29999] = top + 1.0
+    lp = lp.to(dev)
+    state = dict(scores=torch.zeros(R, device=dev), done=torch.zeros(n_inst, dtype=torch.uint8, device=dev),
+                 length=torch.zeros(n_inst, dtype=torch.int32, device=dev), tokens=torch.zeros(R, dtype=torch.int64, device=dev),
+                 src=torch.zeros(R, dtype=torch.int32, device=dev), hist_parents=torch.zeros(Tmax, R, dtype=torch.int32, device=dev),
+                 hist_tokens=torch.zeros(Tmax, R, dtype=torch.int32, device=dev), hist_scores=torch.zeros(Tmax, R, device=dev),
+                 ws=torch.zeros(R * _lib.BEAM_SLICES * nb * 2, device=dev))
+    ops.beam_step(lp, V, n_inst, nb, 0, **state)
+    keep("beam.first", **{k: v.clone() for k, v in state.items() if k != "ws"})
+    state["scores"][5:10] = 0.25                       # instance 1: five equal accumulated scores
+    state["done"][3] = 1                               # a frozen instance
+    ops.beam_step(lp, V, n_inst, nb, 1, **state)
+    keep("beam.later", **{k: v for k, v in state.items() if k != "ws"})
+
+    # ---- univl_sample_step: 12 rows, k = 50, top-p 0.9; rows of few distinct values, so that the k-th entry sits inside a tie
+    Rs, k, Ts = 12, 50, 3
+    x = gen(Rs, LD, seed=12, scale=2.0)
+    x[0] = torch.round(x[0])                           # integers: thousands of equal logits
+    x[1, :] = -1.0
+    x[1, [30521, 5, 4096, 2048]] = 3.0
+    x[2, 1000:1100] = float(x[2].max()) + 0.5          # a hundred equal best, k of them kept: the lowest columns
+    x = x.to(dev)
+    for name, ld_x in (("vec", x), ("scalar", x[:, 1:])):          # 16-byte loads, and the unaligned view that takes the scalar path
+        Vs = V - 1 if name == "scalar" else V
+        s = dict(done=torch.zeros(Rs, dtype=torch.uint8, device=dev), length=torch.zeros(Rs, dtype=torch.int32, device=dev),
+                 ids=torch.zeros(Rs, dtype=torch.int64, device=dev), tokens_out=torch.full((Rs, Ts), -1, dtype=torch.int32, device=dev),
+                 tok_logprob=torch.zeros(Rs, Ts, device=dev), q_logprob=torch.zeros(Rs, Ts, device=dev),
+                 seq_logprob=torch.zeros(Rs, device=dev), seq_q_logprob=torch.zeros(Rs, device=dev), ws=ops.sample_ws(Rs, k, dev),
+                 topk_idx=torch.zeros(Rs, k, dtype=torch.int32, device=dev), topk_val=torch.zeros(Rs, k, device=dev))
+        s["done"][11] = 1
+        for t in range(2):
+            ops.sample_step(ld_x, Vs, k, t, inv_T=1.25, top_p=0.9, seed=1234, **s)
+        keep("sample." + name, **{kk: v for kk, v in s.items() if kk != "ws"})
+
+    # ---- univl_sim_topk: Nq = 33 (two query blocks, the second partial), Ng = 300 (three gallery tiles), k = 10, with a target;
+    # integer operands: exact scores, many equal; duplicated gallery rows tie exactly, within a tile and across tiles; two slice counts
+    q = torch.randint(-2, 3, (33, 768), generator=torch.Generator().manual_seed(13)).float()
+    g = torch.randint(-2, 3, (300, 768), generator=torch.Generator().manual_seed(14)).float()
+    g[5] = g[4] = g[200] = g[299] = g[130]
+    target = (torch.arange(33, dtype=torch.int32) * 9) % 300
+    target[3] = 130
+    for slices in (0, 1):
+        score, idx, gt, eq = ops.sim_topk(q.to(dev), g.to(dev), 10, target=target.to(dev), slices=slices)
+        keep("sim_topk.slices%d" % slices, score=score, idx=idx, gt=gt, eq=eq)
+    score, idx = ops.sim_topk(q[:7].to(dev), g.to(dev), 64)         # one query block, the longest list
+    keep("sim_topk.k64", score=score, idx=idx)
+
+    # ---- the vocabulary head, both forms and the backward, fp32 (K = 32) and bf16 (K = 64): 130 rows x 1002 columns of integer
+    # operands (exact logits), columns 3 / 130 / 1001 identical and lifted to the top on every third row; then real-valued operands at
+    # 50 x 30522
+    for dtype, K in ((torch.float32, 32), (torch.bfloat16, 64)):
+        tag = "fp32" if dtype == torch.float32 else "bf16"
+        gi = torch.Generator().manual_seed(15)
+        rows, Vh = 130, 1002
+        xi = torch.randint(-2, 3, (rows, K), generator=gi)
+        ti = torch.randint(-2, 3, (Vh, K), generator=gi)
+        bi = torch.randint(-3, 4, (Vh,), generator=gi)
+        xi[:, 0], ti[:, 0] = 0, 0
+        xi[::3, 0] = 1
+        for c in (3, 130, 1001):
+            ti[c], bi[c] = ti[3], bi[3]
+            ti[c, 0] = 512
+        lab = torch.randint(0, Vh, (rows,), generator=gi)
+        lab[::5], lab[1], lab[2] = -1, 3, 1001
+        cases = [("ties", xi.to(dev, dtype), ti.to(dev, dtype), bi.to(dev, torch.float32), lab.to(dev), Vh, 10),
+                 ("big", gen(50, K, seed=16).to(dev, dtype), gen(V, K, seed=17, scale=0.2).to(dev, dtype), gen(V, seed=18, scale=0.5).to(dev),
+                  torch.randint(-1, V, (50,), generator=gi).to(dev), V, 5)]
+        for name, xx, tt, bb, ll, Vv, seq_len in cases:
+            d, b = ops.vocab_score_desc(xx, tt, bb, ll, Vv, seq_len)
+            ops.vocab_score(d)
+            keep("vocab_score.%s.%s" % (tag, name), **{kk: v for kk, v in b.items() if kk != "keep"})
+            dl = torch.zeros(xx.shape[0], (Vv + 7) // 8 * 8, device=dev, dtype=dtype)
+            d, b = ops.vocab_ce_desc(xx, tt, bb, ll, dl, Vv)
+            ops.vocab_ce_fwd(d)
+            ops.vocab_ce_bwd(d)
+            keep("vocab_ce.%s.%s" % (tag, name), dlogits=dl, **{kk: v for kk, v in b.items() if kk != "keep"})
+
+    np.savez(out_path, **out)
+    print("wrote %d arrays to %s (library %s)" % (len(out), out_path, lib_path))
+    return 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    sys.exit(main(sys.argv[1], sys.argv[2]))

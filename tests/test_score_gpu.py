@@ -186,6 +186,34 @@ def test_vocab_score_argmax_and_tie_rule_are_exact(dtype, cols):
     assert float((buf["top_logprob"].cpu().double() - (top[:, 0].double() - lse)).abs().max()) < 3e-6 * max(1.0, float(lse.abs().max()))
 
 
+@pytest.mark.parametrize("rows,seq_len,V", [(1, 1, 130), (130, 10, 300), (50, 5, 30522)])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_vocab_score_and_vocab_ce_share_their_statistics(dtype, rows, seq_len, V):
+    """univl_vocab_score and univl_vocab_ce_fwd are two forms of one tile kernel and one row fold (csrc/vocab_ce.h): on the same x, table,
+    bias and labels their lse is the same bits, and so is label_logit on the rows whose label counts (elsewhere neither form writes
+    it).  The fold at every level: 130 columns are two column tiles, the second partial; 130 rows two row tiles; 30522 columns 239
+    slots, more than one round of the row fold's 64 lanes."""
+    K = 64 if dtype == torch.bfloat16 or V > 1000 else 32
+    x = gen(rows, K, seed=1).to(DEV, dtype)
+    table = gen(V, K, seed=2, scale=0.2).to(DEV, dtype)
+    bias = gen(V, seed=3, scale=0.5).to(DEV)
+    labels = _labels(rows, seq_len, V)
+    cnt = _counts(labels, V)
+    assert int(cnt.sum()) >= 1
+    ds, bs = ops.vocab_score_desc(x, table, bias, labels.to(DEV), V, seq_len)
+    dlogits = torch.empty(rows, (V + 7) // 8 * 8, device=DEV, dtype=dtype)
+    dc, bc = ops.vocab_ce_desc(x, table, bias, labels.to(DEV), dlogits, V)
+    bs["lse"].fill_(float("nan"))
+    bc["lse"].fill_(float("nan"))
+    ops.vocab_score(ds)
+    ops.vocab_ce_fwd(dc)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(bs["lse"]).all())
+    assert torch.equal(bs["lse"], bc["lse"])
+    assert torch.equal(bs["label_logit"][cnt.to(DEV)], bc["label_logit"][cnt.to(DEV)])
+    assert torch.equal(bs["partial"], bc["partial"])                    # the slots themselves
+
+
 def test_vocab_score_argument_range():
     """rows < 1, V < 1, K not a multiple of 64 (bf16) / 32 (fp32), seq_len < 1, rows % seq_len != 0, a null output: UNIVL_EINVAL and
     nothing launched."""

@@ -7,25 +7,12 @@
 //            best (value, column) pairs in the workspace.  The score is added HERE, before any comparison, so that ties the fp32 sum
 //            creates between different log-probabilities of a row are seen by the tie rule like any other tie.
 //   phase 2  one wave per instance: the n_bm best of the (1 or n_bm) x slices x n_bm pairs, then parents / tokens / state / history.
-// Order of candidates everywhere: larger value first, equal values by LOWER flat index b * V + v first (`better` below).
-#include <limits.h>
+// Order of candidates everywhere: larger value first, equal values by LOWER flat index b * V + v first (`better`, ranked.h).
 #include "common.h"
+#include "ranked.h"
 #include "univl_hip.h"
 
 namespace {
-
-constexpr int BEAM_NONE = INT_MAX;           // index of an empty top-k slot; loses against every real candidate of any value
-
-__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
-__device__ __forceinline__ void wave_best(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float w = __shfl_xor(v, o, 64);
-        const int j = __shfl_xor(i, o, 64);
-        if (better(w, j, v, i)) { v = w; i = j; }
-    }
-}
 
 template <int NB>
 __device__ __forceinline__ void keep(float (&tv)[NB], int (&ti)[NB], float v, int i) {
@@ -40,7 +27,7 @@ __device__ __forceinline__ void keep(float (&tv)[NB], int (&ti)[NB], float v, in
     }
 }
 
-// ws_val / ws_idx: [rows][slices][NB]; idx is the COLUMN within the row (BEAM_NONE: empty)
+// ws_val / ws_idx: [rows][slices][NB]; idx is the COLUMN within the row (RANK_NONE: empty)
 template <int NB>
 __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict__ lp, long ld, int V, int first_step, const float* __restrict__ scores,
                                                         const uint8_t* __restrict__ done, int chunk, int vec, float* __restrict__ ws_val,
@@ -56,7 +43,7 @@ __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict_
     float tv[NB];
     int ti[NB];
 #pragma unroll
-    for (int k = 0; k < NB; ++k) { tv[k] = -INFINITY; ti[k] = BEAM_NONE; }
+    for (int k = 0; k < NB; ++k) { tv[k] = -INFINITY; ti[k] = RANK_NONE; }
     if (vec) {
         // four 16-byte loads in flight per thread; columns >= V of the last word (padding up to ld) are never candidates
         for (int c = c0 + 4 * tid; c < c1; c += 4 * 1024) {
@@ -93,10 +80,10 @@ __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict_
         for (int w = 1; w < 4; ++w)
             if (better(red_v[r & 1][w], red_i[r & 1][w], v, i)) { v = red_v[r & 1][w]; i = red_i[r & 1][w]; }
         if (tid == 0) { out_v[r] = v; out_i[r] = i; }
-        if (i != BEAM_NONE && ti[0] == i) {
+        if (i != RANK_NONE && ti[0] == i) {
 #pragma unroll
             for (int k = 0; k + 1 < NB; ++k) { tv[k] = tv[k + 1]; ti[k] = ti[k + 1]; }
-            tv[NB - 1] = -INFINITY; ti[NB - 1] = BEAM_NONE;
+            tv[NB - 1] = -INFINITY; ti[NB - 1] = RANK_NONE;
         }
     }
 }
@@ -128,23 +115,23 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict
     for (int c = lane; c < ncand; c += 64) {
         const int b = c / per_row, col = ws_idx[s0 * per_row + c];
         cv[c] = ws_val[s0 * per_row + c];
-        ci[c] = col == BEAM_NONE ? BEAM_NONE : b * V + col;
+        ci[c] = col == RANK_NONE ? RANK_NONE : b * V + col;
     }
     __syncthreads();
     for (int r = 0; r < n_bm; ++r) {
         float v = -INFINITY;
-        int i = BEAM_NONE, at = -1;
+        int i = RANK_NONE, at = -1;
         for (int c = lane; c < ncand; c += 64)
             if (better(cv[c], ci[c], v, i)) { v = cv[c]; i = ci[c]; at = c; }
         const int mine = i;
         wave_best(v, i);
-        if (i != BEAM_NONE && mine == i) { cv[at] = -INFINITY; ci[at] = BEAM_NONE; }      // flat indices are unique: one owner
+        if (i != RANK_NONE && mine == i) { cv[at] = -INFINITY; ci[at] = RANK_NONE; }      // flat indices are unique: one owner
         if (lane == 0) { win_v[r] = v; win_i[r] = i; }
         __syncthreads();
     }
     if (lane < n_bm) {
         // fewer than n_bm comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
-        const int flat = win_i[lane] == BEAM_NONE ? lane * V : win_i[lane], parent = flat / V, token = flat % V;
+        const int flat = win_i[lane] == RANK_NONE ? lane * V : win_i[lane], parent = flat / V, token = flat % V;
         o.scores[s0 + lane] = win_v[lane];
         o.tokens[s0 + lane] = token;
         o.src[s0 + lane] = (int32_t)(s0 + parent);
@@ -236,8 +223,7 @@ extern "C" int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream) {
     const int by_len = (d->V + 1023) / 1024;
     slices = slices > by_len ? by_len : slices;
     slices = slices < 1 ? 1 : (slices > UNIVL_BEAM_SLICES ? UNIVL_BEAM_SLICES : slices);
-    const int chunk = ((d->V + 3) / 4 + slices - 1) / slices * 4;
-    const int vec = (aligned16(d->lp) && d->ld % 4 == 0) ? 1 : 0;      // then every row starts 16-byte aligned and ld >= roundup4(V)
+    const int chunk = slice_chunk(d->V, slices), vec = rows_vec4(d->lp, d->ld);
     float* ws_val = static_cast<float*>(d->ws);
     int* ws_idx = reinterpret_cast<int*>(ws_val + rows * slices * d->n_bm);
     switch (d->n_bm) {

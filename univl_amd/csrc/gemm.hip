@@ -2036,26 +2036,43 @@ extern "C" int univl_proto_layer_ffn(const UnivlGemm* o, const UnivlLayerNorm* l
 }
 #endif  // UNIVL_PROTO
 
-static int vocab_ce_prepare(const UnivlVocabCE* d, VocabCeArgs& a, const char* who, bool bwd) {
+// What UnivlVocabCE and UnivlVocabScore share, D being either.  vocab_head_shape: the checks that come before a form's own.
+template <typename D>
+static int vocab_head_shape(const D* d, const char* who) {
     UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
     UNIVL_CHECK_ARG(d->dtype == UNIVL_F32 || d->dtype == UNIVL_BF16, UNIVL_EUNSUPPORTED, "%s: dtype %d", who, d->dtype);
     const int bk = d->dtype == UNIVL_BF16 ? 64 : 32;
     UNIVL_CHECK_ARG(d->rows > 0 && d->V > 0 && d->K > 0 && d->K % bk == 0, UNIVL_EINVAL, "%s: rows %d V %d K %d (K must be a multiple of %d)", who,
                     d->rows, d->V, d->K, bk);
-    UNIVL_CHECK_ARG(d->x && d->table && d->labels && d->partial && d->label_logit && d->lse && d->rowloss && d->scratch2 && d->loss, UNIVL_EINVAL,
-                    "%s: null buffer", who);
+    return UNIVL_OK;
+}
+
+// vocab_head_operands: the checks that come after a form's own, then the tile kernel's arguments that both forms fill
+template <typename D>
+static int vocab_head_operands(const D* d, VocabCeArgs& a, const char* who) {
     UNIVL_CHECK_ARG(d->ldx >= d->K && d->ldt >= d->K && d->slots >= (d->V + 127) / 128, UNIVL_EINVAL, "%s: ldx %ld ldt %ld slots %d", who, (long)d->ldx,
                     (long)d->ldt, d->slots);
     const int al = d->dtype == UNIVL_BF16 ? 8 : 4;      // 16-byte rows for the LDS-DMA
     UNIVL_CHECK_ARG(d->ldx % al == 0 && d->ldt % al == 0 && ((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->table & 15) == 0, UNIVL_EINVAL,
                     "%s: operands must be 16-byte aligned with 16-byte row pitches", who);
-    if (bwd) UNIVL_CHECK_ARG(d->dlogits && d->lddl >= d->V, UNIVL_EINVAL, "%s: dlogits %p lddl %ld", who, d->dlogits, (long)d->lddl);
+    a = VocabCeArgs{};
     a.X = d->x; a.ldx = d->ldx; a.E = d->table; a.lde = d->ldt; a.bias = d->bias;
     a.rows = d->rows; a.V = d->V; a.K = d->K;
     a.labels = d->labels; a.ignore = d->ignore_index;
     a.partial = d->partial; a.slots = d->slots; a.label_logit = d->label_logit;
-    a.lse = d->lse; a.scal = d->scratch2; a.gout = d->gout; a.dl = d->dlogits; a.lddl = d->lddl;
     a.nx = (d->V + 127) / 128; a.ny = (d->rows + 127) / 128;
+    return UNIVL_OK;
+}
+
+static int vocab_ce_prepare(const UnivlVocabCE* d, VocabCeArgs& a, const char* who, bool bwd) {
+    int rc = vocab_head_shape(d, who);
+    if (rc != UNIVL_OK) return rc;
+    UNIVL_CHECK_ARG(d->x && d->table && d->labels && d->partial && d->label_logit && d->lse && d->rowloss && d->scratch2 && d->loss, UNIVL_EINVAL,
+                    "%s: null buffer", who);
+    rc = vocab_head_operands(d, a, who);                  // resets `a`: this form's own fields are set after it
+    if (rc != UNIVL_OK) return rc;
+    if (bwd) UNIVL_CHECK_ARG(d->dlogits && d->lddl >= d->V, UNIVL_EINVAL, "%s: dlogits %p lddl %ld", who, d->dlogits, (long)d->lddl);
+    a.lse = d->lse; a.scal = d->scratch2; a.gout = d->gout; a.dl = d->dlogits; a.lddl = d->lddl;
     return UNIVL_OK;
 }
 
@@ -2064,7 +2081,7 @@ extern "C" int univl_vocab_ce_fwd(const UnivlVocabCE* d, hipStream_t stream) {
     VocabCeArgs a;
     const int rc = vocab_ce_prepare(d, a, "univl_vocab_ce_fwd", false);
     if (rc != UNIVL_OK) return rc;
-    const int r2 = d->dtype == UNIVL_BF16 ? vocab_ce_launch<__bf16, 4>(a, false, stream) : vocab_ce_launch<float, 2>(a, false, stream);
+    const int r2 = vocab_ce_launch<false, false>(d->dtype, a, stream);
     if (r2 != UNIVL_OK) return r2;
     hipLaunchKernelGGL(vocab_ce_rows_kernel, dim3((d->rows + 3) / 4), dim3(256), 0, stream, d->partial, d->slots, a.nx, d->label_logit, d->labels,
                        d->ignore_index, d->rows, d->lse, d->rowloss);
@@ -2078,34 +2095,24 @@ extern "C" int univl_vocab_ce_bwd(const UnivlVocabCE* d, hipStream_t stream) {
     VocabCeArgs a;
     const int rc = vocab_ce_prepare(d, a, "univl_vocab_ce_bwd", true);
     if (rc != UNIVL_OK) return rc;
-    return d->dtype == UNIVL_BF16 ? vocab_ce_launch<__bf16, 4>(a, true, stream) : vocab_ce_launch<float, 2>(a, true, stream);
+    return vocab_ce_launch<true, false>(d->dtype, a, stream);
 }
 
 extern "C" int univl_vocab_score(const UnivlVocabScore* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     const char* who = "univl_vocab_score";
-    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
-    UNIVL_CHECK_ARG(d->dtype == UNIVL_F32 || d->dtype == UNIVL_BF16, UNIVL_EUNSUPPORTED, "%s: dtype %d", who, d->dtype);
-    const int bk = d->dtype == UNIVL_BF16 ? 64 : 32;
-    UNIVL_CHECK_ARG(d->rows > 0 && d->V > 0 && d->K > 0 && d->K % bk == 0, UNIVL_EINVAL, "%s: rows %d V %d K %d (K must be a multiple of %d)", who,
-                    d->rows, d->V, d->K, bk);
+    int rc = vocab_head_shape(d, who);
+    if (rc != UNIVL_OK) return rc;
     UNIVL_CHECK_ARG(d->seq_len > 0 && d->rows % d->seq_len == 0, UNIVL_EINVAL, "%s: rows %d are not whole captions of seq_len %d", who, d->rows,
                     d->seq_len);
     UNIVL_CHECK_ARG(d->x && d->table && d->labels && d->partial && d->partial_top && d->label_logit, UNIVL_EINVAL, "%s: null buffer", who);
     UNIVL_CHECK_ARG(d->token_logprob && d->top_token && d->top_logprob && d->lse && d->seq_logprob && d->seq_tokens && d->seq_correct, UNIVL_EINVAL,
                     "%s: null output", who);
-    UNIVL_CHECK_ARG(d->ldx >= d->K && d->ldt >= d->K && d->slots >= (d->V + 127) / 128, UNIVL_EINVAL, "%s: ldx %ld ldt %ld slots %d", who, (long)d->ldx,
-                    (long)d->ldt, d->slots);
-    const int al = d->dtype == UNIVL_BF16 ? 8 : 4;      // 16-byte rows for the LDS-DMA
-    UNIVL_CHECK_ARG(d->ldx % al == 0 && d->ldt % al == 0 && ((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->table & 15) == 0, UNIVL_EINVAL,
-                    "%s: operands must be 16-byte aligned with 16-byte row pitches", who);
-    VocabScoreArgs a;
-    a.X = d->x; a.ldx = d->ldx; a.E = d->table; a.lde = d->ldt; a.bias = d->bias;
-    a.rows = d->rows; a.V = d->V; a.K = d->K;
-    a.labels = d->labels;
-    a.partial = d->partial; a.partial_top = d->partial_top; a.slots = d->slots; a.label_logit = d->label_logit;
-    a.nx = (d->V + 127) / 128; a.ny = (d->rows + 127) / 128;
-    const int rc = d->dtype == UNIVL_BF16 ? vocab_score_launch<__bf16, 4>(a, stream) : vocab_score_launch<float, 2>(a, stream);
+    VocabCeArgs a;
+    rc = vocab_head_operands(d, a, who);                  // resets `a`: partial_top is set after it
+    if (rc != UNIVL_OK) return rc;
+    a.partial_top = d->partial_top;
+    rc = vocab_ce_launch<false, true>(d->dtype, a, stream);
     if (rc != UNIVL_OK) return rc;
     hipLaunchKernelGGL(vocab_score_rows_kernel, dim3((d->rows + 3) / 4), dim3(256), 0, stream, d->partial, d->partial_top, d->slots, a.nx, d->label_logit,
                        d->labels, d->ignore_index, d->V, d->rows, d->lse, d->token_logprob, d->top_token, d->top_logprob);

@@ -17,9 +17,9 @@
 // per chunk, starting from zero.  Neither the tile position of the row, the slice, the number of query blocks (16 / 32 row tiles run the
 // same chain) nor deterministic mode enters it, and the target's score is computed by the same chain on gathered rows -- so equality of
 // scores is meaningful (tie rule, eq) and pieces of a gallery searched separately merge exactly.  No float atomics anywhere.
-// Order everywhere: larger score first, equal scores by LOWER gallery index first (`better`).
-#include <limits.h>
+// Order everywhere: larger score first, equal scores by LOWER gallery index first (`better`, ranked.h).
 #include "common.h"
+#include "ranked.h"
 #include "univl_hip.h"
 
 namespace {
@@ -28,43 +28,7 @@ constexpr int RT_H = 768;                   // contraction width (the pooled hid
 constexpr int RT_PITCH = RT_H + 4;          // LDS pitch of a query row: the 16 rows of a fragment read land in distinct banks
 constexpr int RT_TILE = 128;                // gallery rows per tile = 8 waves x 16
 constexpr int RT_SCP = RT_TILE + 4;         // pitch of the score buffer
-constexpr int RT_NONE = INT_MAX;            // index of an empty list slot; loses against every real entry of any value
 constexpr int RT_WGS = 256;                 // workgroups the automatic slice count aims for (one per compute unit)
-
-__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
-// (lv, li): this lane's entry of a wave-wide list sorted best first.  Inserts the wave-uniform candidate; the last entry falls off.
-__device__ __forceinline__ void list_insert(float& lv, int& li, float cv, int ci, int lane) {
-    const int pos = __popcll(__ballot(better(lv, li, cv, ci)));      // the entries that stay in front of it are a prefix
-    const float uv = __shfl_up(lv, 1, 64);
-    const int ui = __shfl_up(li, 1, 64);
-    if (lane == pos) { lv = cv; li = ci; }
-    else if (lane > pos) { lv = uv; li = ui; }
-}
-
-// Offers every lane's (v, base + lane) with ok != 0 to the list: tested against the k-th entry BEFORE any insert, and again when its turn comes.
-__device__ __forceinline__ void list_offer(float& lv, int& li, int k, float v, int base, bool ok, int lane) {
-    float kv = __shfl(lv, k - 1, 64);
-    int ki = __shfl(li, k - 1, 64);
-    unsigned long long m = __ballot(ok && better(v, base + lane, kv, ki));
-    while (m) {                                                       // wave-uniform
-        const int b = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float cv = __shfl(v, b, 64);
-        const int ci = base + b;
-        if (better(cv, ci, kv, ki)) {
-            list_insert(lv, li, cv, ci, lane);
-            kv = __shfl(lv, k - 1, 64);
-            ki = __shfl(li, k - 1, 64);
-        }
-    }
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 struct ScanArgs {
     const float* q; long ldq;
@@ -122,7 +86,7 @@ __global__ __launch_bounds__(512) void sim_topk_scan_kernel(ScanArgs a) {
     int li[NQW], cgt[NQW], ceq[NQW];
 #pragma unroll
     for (int u = 0; u < NQW; ++u) {
-        lv[u] = -INFINITY; li[u] = RT_NONE; cgt[u] = 0; ceq[u] = 0;
+        lv[u] = -INFINITY; li[u] = RANK_NONE; cgt[u] = 0; ceq[u] = 0;
         tv[u] = a.target != nullptr ? tsc[wave * NQW + u] : 0.f;
     }
 
@@ -169,7 +133,7 @@ __global__ __launch_bounds__(512) void sim_topk_scan_kernel(ScanArgs a) {
                     cgt[u] += (ok && s > tv[u]) ? 1 : 0;
                     ceq[u] += (ok && s == tv[u]) ? 1 : 0;
                 }
-                if (a.k > 0) list_offer(lv[u], li[u], a.k, s, j0 + 64 * h, ok, lane);
+                if (a.k > 0) list_offer_run(lv[u], li[u], a.k, s, j0 + 64 * h, ok, lane);
             }
         }
     }
@@ -194,30 +158,16 @@ __global__ __launch_bounds__(64) void sim_topk_merge_kernel(const float* __restr
     const int row = blockIdx.x, lane = threadIdx.x;
     if (k > 0) {
         float lv = -INFINITY;
-        int li = RT_NONE;
+        int li = RANK_NONE;
         for (int s = 0; s < S; ++s) {
             const long at = ((long)row * S + s) * k + lane;
             const float v = lane < k ? ws_val[at] : -INFINITY;
-            const int j = lane < k ? ws_idx[at] : RT_NONE;
-            // list_offer numbers its candidates base + lane; here every lane brings its own index, so the loop is spelled out
-            float kv = __shfl(lv, k - 1, 64);
-            int ki = __shfl(li, k - 1, 64);
-            unsigned long long m = __ballot(j != RT_NONE && better(v, j, kv, ki));
-            while (m) {
-                const int b = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const float cv = __shfl(v, b, 64);
-                const int ci = __shfl(j, b, 64);
-                if (better(cv, ci, kv, ki)) {
-                    list_insert(lv, li, cv, ci, lane);
-                    kv = __shfl(lv, k - 1, 64);
-                    ki = __shfl(li, k - 1, 64);
-                }
-            }
+            const int j = lane < k ? ws_idx[at] : RANK_NONE;
+            list_offer_as<true, true>(lv, li, k, v, j, j != RANK_NONE, lane);      // COPY: see ranked.h
         }
         if (lane < k) {
-            idx[(long)row * k + lane] = li == RT_NONE ? -1 : li;
-            score[(long)row * k + lane] = li == RT_NONE ? -INFINITY : lv;
+            idx[(long)row * k + lane] = li == RANK_NONE ? -1 : li;
+            score[(long)row * k + lane] = li == RANK_NONE ? -INFINITY : lv;
         }
     }
     if (counts) {

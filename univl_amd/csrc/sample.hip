@@ -2,59 +2,28 @@
 // over the RAW logits of every row, the draw, and the row's bookkeeping, as two launches with no host involvement.
 //
 //   scan    grid (rows, slices), 256 threads = 4 waves.  A workgroup reads one column slice of one row once, with 16-byte loads, four
-//           per lane in flight.  Each wave keeps a running top-64 list with ONE ENTRY PER LANE, sorted best first (the mechanism of
-//           csrc/retrieve.hip: every value is tested against the list's k-th entry first, the few that pass are inserted by ballot and
+//           per lane in flight.  Each wave keeps a running top-64 list with ONE ENTRY PER LANE, sorted best first (the list of
+//           csrc/ranked.h: every value is tested against the list's k-th entry first, the few that pass are inserted by ballot and
 //           popcount), and each lane an online (max, sum of exponentials) pair over the columns it read, in the order it read them.
 //           The lanes' pairs fold down a fixed tree to lane 0, the waves' lists and pairs merge through LDS in ascending wave order,
 //           and the slice's k best and its pair go to the workspace.  The log-softmax of the row is never formed.
 //   select  one wave per row: the slices' lists and pairs merge in ascending slice order; then weights, the cumulative chain, the
 //           nucleus, the draw and the outputs (contract steps 2 to 6).
 //
-// Order of candidates everywhere: larger value first, equal values by LOWER column first (`better`).  Nothing here depends on the
+// Order of candidates everywhere: larger value first, equal values by LOWER column first (`better`, ranked.h).  Nothing here depends on the
 // number of rows, on what other rows hold or on deterministic mode: a workgroup sees one row, every reduction has a fixed order, and
 // there are no atomics.  The slice count is a function of V alone.  The sum of exponentials is carried in fp64 (fp32 terms), and the
 // two logarithms of the outputs are taken in fp64 and rounded once, so tok_logprob / q_logprob are within an fp32 rounding of the
 // values the contract's formulas give in exact arithmetic on the fp32 weights.
-#include <limits.h>
 #include <math.h>
 #include "common.h"
+#include "ranked.h"
 #include "univl_hip.h"
 
 namespace {
 
-constexpr int SP_NONE = INT_MAX;             // column of an empty list slot; loses against every real candidate of any value
 constexpr int SP_WAVES = 4;
 constexpr int SP_SLICE_COLS = 2048;          // a row gets one slice per this many columns, at most UNIVL_SAMPLE_SLICES
-
-__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
-// (lv, li): this lane's entry of a wave-wide list sorted best first.  Inserts the wave-uniform candidate; the last entry falls off.
-__device__ __forceinline__ void list_insert(float& lv, int& li, float cv, int ci, int lane) {
-    const int pos = __popcll(__ballot(better(lv, li, cv, ci)));      // the entries that stay in front of it are a prefix
-    const float uv = __shfl_up(lv, 1, 64);
-    const int ui = __shfl_up(li, 1, 64);
-    if (lane == pos) { lv = cv; li = ci; }
-    else if (lane > pos) { lv = uv; li = ui; }
-}
-
-// Offers every lane's own (v, col) with ok != 0 to the list: tested against the k-th entry BEFORE any insert, and again when its
-// turn comes.  Called by whole waves only.
-__device__ __forceinline__ void list_offer(float& lv, int& li, int k, float v, int col, bool ok, int lane) {
-    float kv = __shfl(lv, k - 1, 64);
-    int ki = __shfl(li, k - 1, 64);
-    unsigned long long m = __ballot(ok && better(v, col, kv, ki));
-    while (m) {                                                       // wave-uniform
-        const int b = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float cv = __shfl(v, b, 64);
-        const int ci = __shfl(col, b, 64);
-        if (better(cv, ci, kv, ki)) {
-            list_insert(lv, li, cv, ci, lane);
-            kv = __shfl(lv, k - 1, 64);
-            ki = __shfl(li, k - 1, 64);
-        }
-    }
-}
 
 // (m, s): max and sum over the columns seen so far of exp(x - m).  Equal arguments take the factor 1 without an exponential, so
 // that a pair of (-inf, 0) -- no column yet -- folds away instead of producing inf - inf.
@@ -87,7 +56,7 @@ __global__ __launch_bounds__(256) void sample_scan_kernel(ScanArgs a) {
     const float* x = a.x + (long)row * a.ld;
     const int c0 = slice * a.chunk, c1 = min(a.V, c0 + a.chunk);      // chunk is a multiple of 4; columns >= V are never read as candidates
     float lv = -INFINITY, pm = -INFINITY;
-    int li = SP_NONE;
+    int li = RANK_NONE;
     double ps = 0.0;
     if (a.vec) {
         // a wave takes 256 consecutive columns per step; the loop bounds are wave-uniform (list_offer needs whole waves)
@@ -132,7 +101,7 @@ __global__ __launch_bounds__(256) void sample_scan_kernel(ScanArgs a) {
     if (wave != 0) return;
     for (int w = 1; w < SP_WAVES; ++w) {
         const int j = sh_i[w][lane];
-        list_offer(lv, li, a.k, sh_v[w][lane], j, lane < a.k && j != SP_NONE, lane);
+        list_offer(lv, li, a.k, sh_v[w][lane], j, lane < a.k && j != RANK_NONE, lane);
         pair_merge(pm, ps, sh_m[w], sh_s[w]);                         // every lane folds the same words; lane 0's is the one kept
     }
     const long slot = (long)row * a.S + slice;
@@ -156,13 +125,13 @@ __global__ __launch_bounds__(64) void sample_select_kernel(SelectArgs a) {
     if (a.done[row]) return;                                          // frozen: nothing of the row is written
     // step 1: the k best of the row, lane j holding (x_j, col_j), and the row's (max, sum exp)
     float lv = -INFINITY, pm = -INFINITY;
-    int li = SP_NONE;
+    int li = RANK_NONE;
     double ps = 0.0;
     for (int s = 0; s < a.S; ++s) {
         const long slot = (long)row * a.S + s;
         const float v = lane < k ? a.ws_val[slot * k + lane] : -INFINITY;
-        const int j = lane < k ? a.ws_idx[slot * k + lane] : SP_NONE;
-        list_offer(lv, li, k, v, j, j != SP_NONE, lane);
+        const int j = lane < k ? a.ws_idx[slot * k + lane] : RANK_NONE;
+        list_offer(lv, li, k, v, j, j != RANK_NONE, lane);
         pair_merge(pm, ps, a.ws_max[slot], a.ws_sum[slot]);
     }
     const float inv_T = a.sampling_dev ? a.sampling_dev[0] : a.inv_T, top_p = a.sampling_dev ? a.sampling_dev[1] : a.top_p;
@@ -195,10 +164,10 @@ __global__ __launch_bounds__(64) void sample_select_kernel(SelectArgs a) {
     const float xs = __shfl(lv, js, 64), wsel = __shfl(w, js, 64);
     const int cs = __shfl(li, js, 64);
     // step 6
-    if (a.topk_idx != nullptr && lane < k) a.topk_idx[(long)row * k + lane] = li == SP_NONE ? -1 : li;
+    if (a.topk_idx != nullptr && lane < k) a.topk_idx[(long)row * k + lane] = li == RANK_NONE ? -1 : li;
     if (a.topk_val != nullptr && lane < k) a.topk_val[(long)row * k + lane] = lv;
     if (lane == 0) {
-        const int token = cs == SP_NONE ? 0 : cs;                     // fewer than k comparable candidates (NaN rows: unspecified result)
+        const int token = cs == RANK_NONE ? 0 : cs;                     // fewer than k comparable candidates (NaN rows: unspecified result)
         const float tok_lp = (float)((double)__fsub_rn(xs, pm) - log(ps));
         const float q_lp = (float)log((double)wsel / (double)cm);
         const long at = (long)row * a.Tmax + a.t;
@@ -239,8 +208,7 @@ extern "C" int univl_sample_step(const UnivlSampleStep* d, hipStream_t stream) {
     const int64_t slots = (int64_t)d->R * S;
     ScanArgs a;
     a.x = d->x; a.ld = (long)d->ld; a.V = d->V; a.k = d->k; a.S = S;
-    a.chunk = ((d->V + 3) / 4 + S - 1) / S * 4;
-    a.vec = (aligned16(d->x) && d->ld % 4 == 0) ? 1 : 0;             // then every row starts 16-byte aligned and ld >= roundup4(V)
+    a.chunk = slice_chunk(d->V, S); a.vec = rows_vec4(d->x, d->ld);
     a.done = d->done;
     a.ws_sum = static_cast<double*>(d->ws);
     a.ws_max = reinterpret_cast<float*>(a.ws_sum + slots);

@@ -4,17 +4,22 @@
 // Reference: BertLMPredictionHead.forward (module_bert.py:327-330: h . E_word^T + bias, E_word the tied 30522 x 768 table), its decoder
 // copy (module_decoder.py:180-183), and CrossEntropyLoss(ignore_index=-1) on the result (modeling.py:253, 275).
 //
-// Forward  (vocab_ce_kernel<T, false>): the product is walked in 128 x 128 tiles (the K loop of gemm_tile, gemm_acc_only); a tile's epilogue
-//   reduces its logits to one (max, sum of exp(logit - max)) pair per row -- 16-lane shuffles inside a wave, LDS across the waves of the
-//   column direction -- and writes it to partial[row][column tile]; the one lane that owns (row, label[row]) stores that logit.
-//   vocab_ce_rows_kernel then folds a row's 239 pairs into its log-sum-exp (a wave per row, fixed order) and vocab_ce_loss_kernel sums
-//   lse - label logit over the rows that count (one workgroup, fixed order: the loss is bit-reproducible in every mode).
+// Forward  (vocab_ce_kernel<T, false, TOP>): the product is walked in 128 x 128 tiles (the K loop of gemm_tile, gemm_acc_only); a tile's
+//   epilogue reduces its logits to one (max, sum of exp(logit - max)) pair per row -- 16-lane shuffles inside a wave, LDS across the waves
+//   of the column direction -- and writes it to partial[row][column tile]; the one lane that owns (row, label[row]) stores that logit.
+//   TOP = false, training: vocab_ce_rows_kernel then folds a row's 239 pairs into its log-sum-exp (a wave per row, fixed order) and
+//   vocab_ce_loss_kernel sums lse - label logit over the rows that count (one workgroup, fixed order: the loss is bit-reproducible in
+//   every mode).
+//   TOP = true, scoring (vocab_score.h): the column of the maximum travels beside it through every level, under the order of ranked.h
+//   (of equal logits the LOWER column), into partial_top[row][column tile]; vocab_score_rows_kernel folds the triples.  The pairs, and so
+//   lse, are the same bits in both forms.
 // Backward (vocab_ce_kernel<T, true>): the same product again; the epilogue turns a logit into
 //   (exp(logit - lse[row]) - [col == label[row]]) * gout / n_valid   (0 on ignored rows)
 //   and stores it in the compute type: the matrix autograd calls dlogits, which the two existing backward products consume
 //   (dh = dlogits . E, dE += dlogits^T . h).  What K16 removes per step at 512 tokens: the 62 MB fp32 logits (written by the product, read
 //   by the loss kernel), the loss kernel's 31 MB dlogits write + the scale pass over them; what it adds: one more product.
 #pragma once
+#include "ranked.h"
 
 struct VocabCeArgs {
     const void* X; long ldx;            // [rows, K] head output (compute type), K-major
@@ -23,6 +28,7 @@ struct VocabCeArgs {
     int rows, V, K;
     const int64_t* labels; int ignore;
     float* partial; int slots;          // [rows, slots, 2]
+    int* partial_top;                   // [rows, slots]     (TOP)
     float* label_logit;                 // [rows]
     const float* lse;                   // [rows]            (backward)
     const float* scal;                  // scal[0] = n_valid (backward)
@@ -31,8 +37,26 @@ struct VocabCeArgs {
     int nx, ny;
 };
 
-template <typename T, bool BWD, int WGN>
+// One more (value, column) for a running maximum (m, c), offered in ASCENDING column order: the strict > keeps the lower column of equal
+// values, and an empty maximum (-inf over no valid column) keeps RANK_NONE.  Without TOP there is no column and the maximum is fmaxf's.
+template <bool TOP>
+__device__ __forceinline__ void vocab_max_take(float& m, int& c, float v, int j) {
+    if constexpr (TOP) { if (v > m) { m = v; c = j; } }
+    else m = fmaxf(m, v);
+}
+// the maximum of every aligned group of W lanes, with its column under `better`
+template <bool TOP, int W>
+__device__ __forceinline__ void vocab_max_lanes(float& m, int& c) {
+    if constexpr (TOP) wave_best<W>(m, c);
+    else {
+#pragma unroll
+        for (int o = 1; o < W; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    }
+}
+
+template <typename T, bool BWD, bool TOP, int WGN>
 __global__ __launch_bounds__(128 * WGN, 2) void vocab_ce_kernel(VocabCeArgs a) {
+    static_assert(!(BWD && TOP), "the arg-max column belongs to the forward");
     constexpr int BM = 128, BN = 128, WGM = 2, NC = 2;
     constexpr int WM = BM / WGM, WN = BN / WGN, MI = WM / 16, NI = WN / 16;
     int bx, by, bz;
@@ -55,21 +79,22 @@ __global__ __launch_bounds__(128 * WGN, 2) void vocab_ce_kernel(VocabCeArgs a) {
     }
     if constexpr (!BWD) {
         float* red = reinterpret_cast<float*>(smem_raw);          // [WGN][BM][2]
+        int* redc = reinterpret_cast<int*>(red + WGN * BM * 2);   // [WGN][BM]   (TOP)
 #pragma unroll
         for (int ma = 0; ma < MI; ++ma)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int rl = wm0 + 16 * ma + 4 * g + r, row = m0 + rl;
-                const long lab = row < a.rows ? (long)a.labels[row] : -2;
+                const long lab = row < a.rows ? (long)a.labels[row] : -2;       // a label outside [0, V) matches no column
                 float v[NI], m = -INFINITY;
+                int c = RANK_NONE;
 #pragma unroll
                 for (int b = 0; b < NI; ++b) {
                     v[b] = vcol[b] ? acc[ma][b][r] + bv[b] : -INFINITY;
-                    m = fmaxf(m, v[b]);
+                    vocab_max_take<TOP>(m, c, v[b], col[b]);
                     if (vcol[b] && (long)col[b] == lab) a.label_logit[row] = v[b];
                 }
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                vocab_max_lanes<TOP, 16>(m, c);
                 float s = 0.0f;
                 if (m > -INFINITY) {
 #pragma unroll
@@ -77,22 +102,31 @@ __global__ __launch_bounds__(128 * WGN, 2) void vocab_ce_kernel(VocabCeArgs a) {
                 }
 #pragma unroll
                 for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
-                if (i == 0) { red[(wn * BM + rl) * 2] = m; red[(wn * BM + rl) * 2 + 1] = s; }
+                if (i == 0) {
+                    red[(wn * BM + rl) * 2] = m; red[(wn * BM + rl) * 2 + 1] = s;
+                    if constexpr (TOP) redc[wn * BM + rl] = c;
+                }
             }
         __syncthreads();
         if (tid < BM && m0 + tid < a.rows) {
             float m = -INFINITY;
+            int c = RANK_NONE;
 #pragma unroll
-            for (int w = 0; w < WGN; ++w) m = fmaxf(m, red[(w * BM + tid) * 2]);
+            for (int w = 0; w < WGN; ++w) {                                     // ascending column waves
+                int cw = 0;
+                if constexpr (TOP) cw = redc[w * BM + tid];
+                vocab_max_take<TOP>(m, c, red[(w * BM + tid) * 2], cw);
+            }
             float s = 0.0f;
 #pragma unroll
             for (int w = 0; w < WGN; ++w) {
                 const float mw = red[(w * BM + tid) * 2];
                 if (mw > -INFINITY) s += red[(w * BM + tid) * 2 + 1] * __expf(mw - m);
             }
-            float* out = a.partial + ((long)(m0 + tid) * a.slots + bx) * 2;
-            out[0] = m;
-            out[1] = s;
+            const long at = (long)(m0 + tid) * a.slots + bx;
+            a.partial[at * 2] = m;
+            a.partial[at * 2 + 1] = s;
+            if constexpr (TOP) a.partial_top[at] = c;
         }
     } else {
         const float nvalid = a.scal[0];
@@ -118,23 +152,35 @@ __global__ __launch_bounds__(128 * WGN, 2) void vocab_ce_kernel(VocabCeArgs a) {
     }
 }
 
-// a wave per row: fold the row's `slots` (max, sum) pairs in slot order -> lse[row]; rowloss[row] = lse - label logit (0 on ignored rows)
-__global__ __launch_bounds__(256) void vocab_ce_rows_kernel(const float* partial, int pitch, int slots, const float* label_logit, const int64_t* labels,
-                                                            int ignore, int rows, float* lse, float* rowloss) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const float* p = partial + (long)row * pitch * 2;          // `slots` written column tiles of `pitch` reserved ones
-    float m = -INFINITY;
-    for (int j = lane; j < slots; j += 64) m = fmaxf(m, p[2 * j]);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    float s = 0.0f;
+// The row fold of both forms, by one wave: the row's `slots` pairs (with TOP: triples) in slot order -> in every lane the maximum m, the sum
+// s of exp(logit - m) over the row, and with TOP the maximum's column c.  p / pc: the row's slots (pc is not read without TOP).
+template <bool TOP>
+__device__ __forceinline__ void vocab_row_fold(const float* p, const int* pc, int slots, int lane, float& m, float& s, int& c) {
+    m = -INFINITY;
+    c = RANK_NONE;
+    for (int j = lane; j < slots; j += 64) {                   // ascending slots = ascending columns
+        int cj = 0;
+        if constexpr (TOP) cj = pc[j];
+        vocab_max_take<TOP>(m, c, p[2 * j], cj);
+    }
+    vocab_max_lanes<TOP, 64>(m, c);
+    s = 0.0f;
     for (int j = lane; j < slots; j += 64) {
         const float mj = p[2 * j];
         if (mj > -INFINITY) s += p[2 * j + 1] * expf(mj - m);
     }
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+}
+
+// a wave per row: lse[row]; rowloss[row] = lse - label logit (0 on ignored rows)
+__global__ __launch_bounds__(256) void vocab_ce_rows_kernel(const float* partial, int pitch, int slots, const float* label_logit, const int64_t* labels,
+                                                            int ignore, int rows, float* lse, float* rowloss) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    float m, s;
+    int c;
+    vocab_row_fold<false>(partial + (long)row * pitch * 2, nullptr, slots, lane, m, s, c);     // `slots` written column tiles of `pitch` reserved ones
     if (lane == 0) {
         const float l = m + logf(s);
         lse[row] = l;
@@ -167,19 +213,21 @@ __global__ __launch_bounds__(256) void vocab_ce_loss_kernel(const float* rowloss
     }
 }
 
-template <typename T, int WGN>
-static int vocab_ce_launch(const VocabCeArgs& a, bool bwd, hipStream_t stream) {
+template <typename T, bool BWD, bool TOP, int WGN>
+static int vocab_ce_launch_as(const VocabCeArgs& a, hipStream_t stream) {
     constexpr int NC = 2, BK = NC * Mma<T>::CH, NT = 128 * WGN;
     constexpr size_t smem_k = 2 * (Tile<T, false, 128, BK, NT>::BYTES + Tile<T, false, 128, BK, NT>::BYTES);
-    constexpr size_t smem = smem_k > (size_t)WGN * 128 * 2 * sizeof(float) ? smem_k : (size_t)WGN * 128 * 2 * sizeof(float);
-    static bool done_f[UNIVL_MAX_DEVICES] = {}, done_b[UNIVL_MAX_DEVICES] = {};
-    if (bwd) {
-        if (smem > 48 * 1024) univl_allow_lds(vocab_ce_kernel<T, true, WGN>, smem, done_b);
-        hipLaunchKernelGGL((vocab_ce_kernel<T, true, WGN>), dim3(a.nx * a.ny), dim3(NT), smem, stream, a);
-    } else {
-        if (smem > 48 * 1024) univl_allow_lds(vocab_ce_kernel<T, false, WGN>, smem, done_f);
-        hipLaunchKernelGGL((vocab_ce_kernel<T, false, WGN>), dim3(a.nx * a.ny), dim3(NT), smem, stream, a);
-    }
+    constexpr size_t smem_r = (size_t)WGN * 128 * (TOP ? 3 : 2) * sizeof(float);
+    constexpr size_t smem = smem_k > smem_r ? smem_k : smem_r;
+    static bool done[UNIVL_MAX_DEVICES] = {};
+    if (smem > 48 * 1024) univl_allow_lds(vocab_ce_kernel<T, BWD, TOP, WGN>, smem, done);
+    hipLaunchKernelGGL((vocab_ce_kernel<T, BWD, TOP, WGN>), dim3(a.nx * a.ny), dim3(NT), smem, stream, a);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
+}
+
+// the tile kernel of one form (training forward, backward, scoring forward) for the descriptor's dtype
+template <bool BWD, bool TOP>
+static int vocab_ce_launch(int dtype, const VocabCeArgs& a, hipStream_t stream) {
+    return dtype == UNIVL_BF16 ? vocab_ce_launch_as<__bf16, BWD, TOP, 4>(a, stream) : vocab_ce_launch_as<float, BWD, TOP, 2>(a, stream);
 }

@@ -618,19 +618,25 @@ def ce_loss(logits, labels, V, scratch2, loss, dlogits, ignore_index=-1):
                                         ignore_index, _p(scratch2), _p(loss), _p(dlogits), dlogits.stride(0), _stream()), "ce_loss")
 
 
+def vocab_head_desc(cls, x, table, bias, labels, V, ignore_index=-1):
+    """The leading fields that UnivlVocabCE and UnivlVocabScore share (cls: _lib.VocabCE or _lib.VocabScore): x [rows, K] and table
+    [V(+pad), K] in the compute type, bias [V] fp32 or None, labels [rows] int64; slots = the 128-column tiles of a row, the second
+    dimension of `partial`.  The caller fills the rest."""
+    d = cls()
+    d.dtype, (d.rows, d.K), d.V = dtype_code(x.dtype), x.shape, V
+    d.x, d.ldx, d.table, d.ldt = _p(x), x.stride(0), _p(table), table.stride(0)
+    d.bias, d.labels, d.ignore_index, d.slots = _p(bias), _p(labels), ignore_index, (V + 127) // 128
+    return d
+
+
 def vocab_ce_desc(x, table, bias, labels, dlogits, V, ignore_index=-1):
     """K16 descriptor (include/univl_hip.h: UnivlVocabCE) + the buffers it owns: x [rows, K], table [V(+pad), K] in the compute type,
     dlogits [rows, lddl] in the compute type.  Returns (desc, buffers) -- keep `buffers` alive as long as the descriptor is used."""
-    rows, K = x.shape
-    slots = (V + 127) // 128
-    dev = x.device
-    b = dict(partial=torch.empty(rows, slots, 2, device=dev), label_logit=torch.zeros(rows, device=dev), lse=torch.empty(rows, device=dev),
+    d = vocab_head_desc(_lib.VocabCE, x, table, bias, labels, V, ignore_index)
+    rows, dev = d.rows, x.device
+    b = dict(partial=torch.empty(rows, d.slots, 2, device=dev), label_logit=torch.zeros(rows, device=dev), lse=torch.empty(rows, device=dev),
              rowloss=torch.empty(rows, device=dev), scratch=torch.zeros(2, device=dev), loss=torch.zeros(1, device=dev),
              keep=(x, table, bias, labels, dlogits))
-    d = _lib.VocabCE()
-    d.dtype, d.rows, d.V, d.K = dtype_code(x.dtype), rows, V, K
-    d.x, d.ldx, d.table, d.ldt = _p(x), x.stride(0), _p(table), table.stride(0)
-    d.bias, d.labels, d.ignore_index, d.slots = (_p(bias) if bias is not None else None), _p(labels), ignore_index, slots
     d.partial, d.label_logit, d.lse, d.rowloss = _p(b["partial"]), _p(b["label_logit"]), _p(b["lse"]), _p(b["rowloss"])
     d.scratch2, d.loss, d.gout = _p(b["scratch"]), _p(b["loss"]), None
     d.dlogits, d.lddl = _p(dlogits), dlogits.stride(0)
@@ -657,11 +663,12 @@ def vocab_score_desc(x, table, bias, labels, V, seq_len, ignore_index=-1, out=No
     assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous())
     rows, K = x.shape
     assert labels.numel() == rows and table.shape[1] == K and table.shape[0] >= V
-    slots = (max(V, 1) + 127) // 128
+    d = vocab_head_desc(_lib.VocabScore, x, table, bias, labels, V, ignore_index)
+    d.slots, d.seq_len = max(d.slots, 1), seq_len      # V < 1 is the library's to refuse: the buffers still get a shape
     n_seq = rows // seq_len if seq_len > 0 else 0
     dev = x.device
     f, i = torch.float32, torch.int32
-    b = dict(partial=torch.empty(rows, slots, 2, device=dev), partial_top=torch.empty(rows, slots, device=dev, dtype=i),
+    b = dict(partial=torch.empty(rows, d.slots, 2, device=dev), partial_top=torch.empty(rows, d.slots, device=dev, dtype=i),
              label_logit=torch.zeros(rows, device=dev), keep=(x, table, bias, labels))
     for name, n, dt in (("token_logprob", rows, f), ("top_token", rows, i), ("top_logprob", rows, f), ("lse", rows, f),
                         ("seq_logprob", n_seq, f), ("seq_tokens", n_seq, i), ("seq_correct", n_seq, i)):
@@ -671,10 +678,6 @@ def vocab_score_desc(x, table, bias, labels, V, seq_len, ignore_index=-1, out=No
         _require_gpu(t)
         assert t.dtype == dt and t.numel() == n and t.is_contiguous(), name
         b[name] = t
-    d = _lib.VocabScore()
-    d.dtype, d.rows, d.V, d.K = dtype_code(x.dtype), rows, V, K
-    d.x, d.ldx, d.table, d.ldt = _p(x), x.stride(0), _p(table), table.stride(0)
-    d.bias, d.labels, d.ignore_index, d.slots, d.seq_len = _p(bias), _p(labels), ignore_index, slots, seq_len
     d.partial, d.partial_top, d.label_logit = _p(b["partial"]), _p(b["partial_top"]), _p(b["label_logit"])
     d.token_logprob, d.top_token, d.top_logprob, d.lse = _p(b["token_logprob"]), _p(b["top_token"]), _p(b["top_logprob"]), _p(b["lse"])
     d.seq_logprob, d.seq_tokens, d.seq_correct = _p(b["seq_logprob"]), _p(b["seq_tokens"]), _p(b["seq_correct"])

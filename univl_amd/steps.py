@@ -489,7 +489,6 @@ class VocabHead:
         self.labels = e(T, dtype=torch.int64)
         # K16 (univl_vocab_ce_fwd / _bwd): per-row (max, sum exp) pairs of the 128-column tiles, the label's logit, the row's log-sum-exp
         self.k16 = None
-        self.slots = (V + 127) // 128
         if transform_only:
             return
         self.dlogits = e(T, self.ldv, dtype=ct)
@@ -503,13 +502,9 @@ class VocabHead:
         return self._logits
 
     def _k16_desc(self, x16, bias, table):
-        cx, T = self.cx, self.T
-        e = cx.e
-        self.k16 = k = dict(partial=e(T, self.slots, 2), label_logit=e(T), lse=e(T), rowloss=e(T))
-        d = _lib.VocabCE()
-        d.dtype, d.rows, d.V, d.K = cx.dt, T, self.V, H
-        d.x, d.ldx, d.table, d.ldt, d.bias = x16.data_ptr(), H, table.data_ptr(), H, bias.data_ptr()
-        d.labels, d.ignore_index, d.slots = self.labels.data_ptr(), -1, self.slots
+        e, T = self.cx.e, self.T
+        d = ops.vocab_head_desc(_lib.VocabCE, x16, table, bias, self.labels, self.V)
+        self.k16 = k = dict(partial=e(T, d.slots, 2), label_logit=e(T), lse=e(T), rowloss=e(T))
         d.partial, d.label_logit, d.lse, d.rowloss = (k["partial"].data_ptr(), k["label_logit"].data_ptr(), k["lse"].data_ptr(),
                                                       k["rowloss"].data_ptr())
         d.scratch2, d.loss = self.scratch.data_ptr(), self.loss.data_ptr()
