@@ -669,9 +669,12 @@ int univl_clip_coef(const float* sumsq, const UnivlSeg* segs, int32_t nseg, floa
 /* g *= coef[0] over all active segments (in-place form of clip_grad_norm_) */
 int univl_scale_grads(float* g, const UnivlSeg* segs, const int32_t* chunk_seg, const int64_t* chunk_off,
                       const int32_t* chunk_len, int32_t nchunk, const float* coef, hipStream_t stream);
+/* Alignment: the kernels pick their 16-byte vector path from a chunk's element offset alone (offset % 4 == 0), so p / g / m / v must be
+ * 16-byte aligned and p16 / p16_lo (where given) 8-byte aligned.  univl_bert_adam, univl_bert_adam_range, univl_gemm_rider and the
+ * launches that carry chunks (univl_gemm_ln, univl_attention_fwd_fused) return UNIVL_EINVAL otherwise, before any launch. */
 typedef struct UnivlAdam {
-    float* p; const float* g; float* m; float* v;   /* flat fp32 buffers                                  */
-    void* p16;                   /* optional bf16 shadow of p (same offsets), rewritten by the step       */
+    float* p; const float* g; float* m; float* v;   /* flat fp32 buffers, 16-byte aligned                 */
+    void* p16;                   /* optional bf16 shadow of p (same offsets, 8-byte aligned), rewritten by the step */
     const UnivlSeg* segs; int32_t nseg;
     const int32_t* chunk_seg; const int64_t* chunk_off; const int32_t* chunk_len; int32_t nchunk;
     const float* sumsq;          /* per-segment sum of squares of the UNSCALED g                          */

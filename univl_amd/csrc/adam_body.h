@@ -1,9 +1,32 @@
-// One chunk of the fused BertAdam update (modules/optimization.py:103-168) as a device function, for kernels that carry optimizer
-// work beside their own (gemm.hip: gemm_adam_kernel, EXPERIMENTAL).  Same arithmetic, operation order and non-temporal policy as
-// adam_apply_kernel<NT> in optim.hip (which stays the product path's kernel); NTH = threads of the calling workgroup.
+// The fused BertAdam update (modules/optimization.py:103-168), stated once for every kernel that applies it: adam_elem is the element
+// update of adam_apply_kernel<NT> (optim.hip, which includes this header) and of adam_chunk below; adam_chunk is one chunk of the update
+// as a device function, for the kernels that carry optimizer work beside their own (gemm.hip: gemm_adam_kernel, gemm_adam_rect_kernel,
+// gemm_ln_kernel, attn_fwd_qkv_kernel), with adam_apply_kernel's walk and non-temporal policy; NTH = threads of the calling workgroup.
 #pragma once
 #include "common.h"
 #include "univl_hip.h"
+
+// The update kernels take their 16-byte vector path from a chunk's element offset alone (off & 3), so the flat buffers themselves must sit
+// on those boundaries: p / g / m / v 16-byte aligned, p16 / p16_lo (where given) 8-byte aligned.  Every entry point that carries chunks
+// refuses a descriptor that does not (UNIVL_EINVAL, before any launch).
+static inline bool adam_bases_aligned(const UnivlAdam* a) {
+    return aligned16(a->p) && aligned16(a->g) && aligned16(a->m) && aligned16(a->v) && ((((uintptr_t)a->p16 | (uintptr_t)a->p16_lo) & 7) == 0);
+}
+
+// One element of the update, for EVERY kernel that applies it (adam_apply_kernel in optim.hip, adam_chunk below).  The association is pinned
+// with explicit fused multiply-adds: left to the compiler's contraction, `m * b1 + (1 - b1) * gr` became fma(1 - b1, gr, m * b1) in one
+// kernel and fma(b1, m, (1 - b1) * gr) in another (likewise v), and the launch forms that promise the same bits differed in the last
+// bit of m and v wherever the moments were not zero (tests/test_optim_gpu.py compares them on non-zero moments).
+__device__ __forceinline__ void adam_elem(float& p, const float g, float& m, float& v, const float gs, const float lr, const float wd,
+                                          const float b1, const float b2, const float eps) {
+    const float gr = g * gs;
+    m = __builtin_fmaf(1.0f - b1, gr, m * b1);
+    v = __builtin_fmaf((1.0f - b2) * gr, gr, v * b2);
+    const float upd = __builtin_fmaf(wd, p, m / (sqrtf(v) + eps));
+    p = __builtin_fmaf(-lr, upd, p);
+}
+// ... and of a row nobody ever touched (UnivlAdam.row_flags): what adam_elem gives for g = m = v = 0
+__device__ __forceinline__ float adam_elem_decay_only(const float p, const float lr, const float wd) { return __builtin_fmaf(-lr, wd * p, p); }
 
 bool univl_adam_nt();      // optim.hip: UNIVL_ADAM_NT (default 1): non-temporal loads / stores of the 28 fp32 bytes per parameter
 
@@ -37,11 +60,9 @@ __device__ __forceinline__ void adam_chunk(const UnivlAdam& a, int c) {
     auto update = [&](int i, f32x4_t pp, const f32x4_t gg, f32x4_t mm, f32x4_t vv) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float gr = gg[e] * gs;
-            mm[e] = mm[e] * b1 + (1.0f - b1) * gr;
-            vv[e] = vv[e] * b2 + (1.0f - b2) * gr * gr;
-            const float upd = mm[e] / (sqrtf(vv[e]) + eps) + wd * pp[e];
-            pp[e] -= lr * upd;
+            float pe = pp[e], me = mm[e], ve = vv[e];
+            adam_elem(pe, gg[e], me, ve, gs, lr, wd, b1, b2, eps);
+            pp[e] = pe; mm[e] = me; vv[e] = ve;
         }
         adam_st4<NT>(p, i, pp);
         adam_st4<NT>(m, i, mm);
@@ -69,11 +90,8 @@ __device__ __forceinline__ void adam_chunk(const UnivlAdam& a, int c) {
     }
     for (; i < nv; i += NTH) update(i, adam_ld4<NT>(p, i), adam_ld4<NT>(g, i), adam_ld4<NT>(m, i), adam_ld4<NT>(v, i));
     for (int j = nv * 4 + threadIdx.x; j < len; j += NTH) {
-        const float gr = g[j] * gs;
-        const float mi = m[j] * b1 + (1.0f - b1) * gr;
-        const float vi = v[j] * b2 + (1.0f - b2) * gr * gr;
-        const float upd = mi / (sqrtf(vi) + eps) + wd * p[j];
-        const float pi = p[j] - lr * upd;
+        float pi = p[j], mi = m[j], vi = v[j];
+        adam_elem(pi, g[j], mi, vi, gs, lr, wd, b1, b2, eps);
         p[j] = pi; m[j] = mi; v[j] = vi;
         if (p16) p16[j] = (__bf16)pi;
         if (p16lo) p16lo[j] = (__bf16)(pi - (float)(__bf16)pi);

@@ -1747,6 +1747,7 @@ extern "C" int univl_attention_fwd_fused(const UnivlAttention* at, const UnivlGe
                                          adam->chunk_off && adam->chunk_len && adam->seg_scalars && chunk_begin >= 0 && chunk_count > 0 &&
                                          chunk_begin + chunk_count <= adam->nchunk),
                     UNIVL_EINVAL, "univl_attention_fwd_fused: chunks [%d, +%d)", chunk_begin, chunk_count);
+    UNIVL_CHECK_ARG(chunk_count == 0 || adam_bases_aligned(adam), UNIVL_EINVAL, "univl_attention_fwd_fused: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
     int rc = attn_check(at, "univl_attention_fwd_fused", false);
     if (rc) return rc;
     const int Sk_pad = (at->Sk + 31) / 32 * 32;
@@ -1840,6 +1841,7 @@ extern "C" int univl_gemm_rider(const UnivlGemm* gemm, const UnivlAdam* adam, in
                         adam->seg_scalars && adam->nchunk > 0 && chunk_begin >= 0 && chunk_count >= 0 &&
                         chunk_begin + chunk_count <= adam->nchunk,
                     UNIVL_EINVAL, "univl_gemm_rider: chunks [%d, +%d) of %d", chunk_begin, chunk_count, adam ? adam->nchunk : 0);
+    UNIVL_CHECK_ARG(adam_bases_aligned(adam), UNIVL_EINVAL, "univl_gemm_rider: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
     GemmArgs a;
     int ks, fits;
     int rc = rider_prepare(gemm, a, ks, fits);
@@ -1888,6 +1890,7 @@ extern "C" int univl_gemm_ln(const UnivlGemm* gemm, const UnivlLayerNorm* ln, in
                                          adam->chunk_off && adam->chunk_len && adam->seg_scalars && chunk_begin >= 0 && chunk_count > 0 &&
                                          chunk_begin + chunk_count <= adam->nchunk),
                     UNIVL_EINVAL, "univl_gemm_ln: chunks [%d, +%d)", chunk_begin, chunk_count);
+    UNIVL_CHECK_ARG(chunk_count == 0 || adam_bases_aligned(adam), UNIVL_EINVAL, "univl_gemm_ln: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
     GemmArgs a;
     int ks;
     Choice c;

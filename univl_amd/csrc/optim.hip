@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "univl_hip.h"
+#include "adam_body.h"
 
 namespace {
 
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(UnivlAdam a, int c0, in
             for (int i = threadIdx.x; i < nv; i += 256) {
                 f32x4_t pp = ld4<NT>(p, i);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const float upd = wd * pp[e]; pp[e] -= lr * upd; }
+                for (int e = 0; e < 4; ++e) pp[e] = adam_elem_decay_only(pp[e], lr, wd);
                 st4<NT>(p, i, pp);
                 if (p16) {
                     bf16x4_t w;
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(UnivlAdam a, int c0, in
                 }
             }
             for (int i = nv * 4 + threadIdx.x; i < len; i += 256) {
-                const float pi = p[i] - lr * (wd * p[i]);
+                const float pi = adam_elem_decay_only(p[i], lr, wd);
                 p[i] = pi;
                 if (p16) p16[i] = (__bf16)pi;
                 if (p16lo) p16lo[i] = (__bf16)(pi - (float)(__bf16)pi);
@@ -192,11 +193,9 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(UnivlAdam a, int c0, in
     auto update = [&](int i, f32x4_t pp, const f32x4_t gg, f32x4_t mm, f32x4_t vv) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float gr = gg[e] * gs;
-            mm[e] = mm[e] * b1 + (1.0f - b1) * gr;
-            vv[e] = vv[e] * b2 + (1.0f - b2) * gr * gr;
-            const float upd = mm[e] / (sqrtf(vv[e]) + eps) + wd * pp[e];
-            pp[e] -= lr * upd;
+            float pe = pp[e], me = mm[e], ve = vv[e];
+            adam_elem(pe, gg[e], me, ve, gs, lr, wd, b1, b2, eps);
+            pp[e] = pe; mm[e] = me; vv[e] = ve;
         }
         st4<NT>(p, i, pp);
         st4<NT>(m, i, mm);
@@ -226,11 +225,8 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(UnivlAdam a, int c0, in
     }
     for (; i < nv; i += 256) update(i, ld4<NT>(p, i), ld4<NT>(g, i), ld4<NT>(m, i), ld4<NT>(v, i));
     for (int i = nv * 4 + threadIdx.x; i < len; i += 256) {
-        const float gr = g[i] * gs;
-        const float mi = m[i] * b1 + (1.0f - b1) * gr;
-        const float vi = v[i] * b2 + (1.0f - b2) * gr * gr;
-        const float upd = mi / (sqrtf(vi) + eps) + wd * p[i];
-        const float pi = p[i] - lr * upd;
+        float pi = p[i], mi = m[i], vi = v[i];
+        adam_elem(pi, g[i], mi, vi, gs, lr, wd, b1, b2, eps);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (p16) p16[i] = (__bf16)pi;
         if (p16lo) p16lo[i] = (__bf16)(pi - (float)(__bf16)pi);
@@ -344,6 +340,7 @@ extern "C" int univl_bert_adam(const UnivlAdam* d, hipStream_t stream) {
     UNIVL_CHECK_ARG(d && d->p && d->g && d->m && d->v && d->segs && d->chunk_seg && d->chunk_off && d->chunk_len &&
                         d->sumsq && d->step && d->seg_scalars && d->nseg > 0 && d->nchunk > 0,
                     UNIVL_EINVAL, "univl_bert_adam: bad argument");
+    UNIVL_CHECK_ARG(adam_bases_aligned(d), UNIVL_EINVAL, "univl_bert_adam: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
     hipLaunchKernelGGL(adam_prep_kernel, dim3((d->nseg + 255) / 256), dim3(256), 0, stream, *d);
     if (univl_adam_nt()) hipLaunchKernelGGL(adam_apply_kernel<true>, dim3(d->nchunk), dim3(256), 0, stream, *d, 0, d->nchunk);
     else hipLaunchKernelGGL(adam_apply_kernel<false>, dim3(d->nchunk), dim3(256), 0, stream, *d, 0, d->nchunk);
@@ -357,6 +354,7 @@ extern "C" int univl_bert_adam_range(const UnivlAdam* d, int32_t chunk_begin, in
     UNIVL_CHECK_ARG(d && d->p && d->g && d->m && d->v && d->segs && d->chunk_seg && d->chunk_off && d->chunk_len &&
                         d->sumsq && d->step && d->seg_scalars && d->nseg > 0 && d->nchunk > 0,
                     UNIVL_EINVAL, "univl_bert_adam_range: bad argument");
+    UNIVL_CHECK_ARG(adam_bases_aligned(d), UNIVL_EINVAL, "univl_bert_adam_range: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
     UNIVL_CHECK_ARG(chunk_begin >= 0 && chunk_count >= 0 && chunk_begin + chunk_count <= d->nchunk, UNIVL_EINVAL,
                     "univl_bert_adam_range: chunks [%d, +%d) of %d", chunk_begin, chunk_count, d->nchunk);
     if (do_prep) hipLaunchKernelGGL(adam_prep_kernel, dim3((d->nseg + 255) / 256), dim3(256), 0, stream, *d);

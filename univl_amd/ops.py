@@ -109,10 +109,12 @@ def gemm_pair(dgrad, wgrad, dry_run=False):
     return True
 
 
-def gemm_ln(gemm, ln, counters, dry_run=False):
+def gemm_ln(gemm, ln, counters, dry_run=False, adam=None, chunk_begin=0, chunk_count=0, max_blocks=0):
     """A forward product and the LayerNorm that consumes its fp32 output in ONE launch (univl_gemm_ln).  Returns False when the C side
-    does not carry the pair (deterministic mode, other tiles / layouts); counters: int32 [2 * ceil(M / 64)], zero."""
-    rc = _lib.lib().univl_gemm_ln(_BYREF(gemm), _BYREF(ln), C.c_void_p(counters.data_ptr()), None, 0, 0, 0, int(bool(dry_run)), _stream())
+    does not carry the pair (deterministic mode, other tiles / layouts); counters: int32 [2 * ceil(M / 64)], zero.  adam (adam_desc) +
+    chunk_begin / chunk_count / max_blocks: chunks of a prepared BertAdam update riding in the launch (default: none)."""
+    rc = _lib.lib().univl_gemm_ln(_BYREF(gemm), _BYREF(ln), C.c_void_p(counters.data_ptr()), None if adam is None else _BYREF(adam),
+                                  int(chunk_begin), int(chunk_count), int(max_blocks), int(bool(dry_run)), _stream())
     if rc == _lib.EUNSUPPORTED:
         return False
     _lib.check(rc, "gemm_ln")
@@ -197,10 +199,12 @@ def attention_bwd_fused(attn, odgrad, owgrad=None, dry_run=False):
     return True
 
 
-def attention_fwd_fused(attn, qkv, dry_run=False):
-    """univl_attention_fwd with the q | k | v projection computed inside the launch (univl_attention_fwd_fused, no riding optimizer
-    chunks).  Returns False where the C side does not carry the pair."""
-    rc = _lib.lib().univl_attention_fwd_fused(_BYREF(attn), _BYREF(qkv), None, 0, 0, 0, int(bool(dry_run)), _stream())
+def attention_fwd_fused(attn, qkv, dry_run=False, adam=None, chunk_begin=0, chunk_count=0, max_blocks=0):
+    """univl_attention_fwd with the q | k | v projection computed inside the launch (univl_attention_fwd_fused).  Returns False where
+    the C side does not carry the pair.  adam (adam_desc) + chunk_begin / chunk_count / max_blocks: chunks of a prepared BertAdam update
+    riding in the launch (default: none)."""
+    rc = _lib.lib().univl_attention_fwd_fused(_BYREF(attn), _BYREF(qkv), None if adam is None else _BYREF(adam), int(chunk_begin),
+                                              int(chunk_count), int(max_blocks), int(bool(dry_run)), _stream())
     if rc == _lib.EUNSUPPORTED:
         return False
     _lib.check(rc, "attention_fwd_fused")
@@ -551,6 +555,75 @@ def sim_topk(q, g, k, *, target=None, slices=0):
     if d.k == 0:
         return gt, eq
     return (score, idx) if target is None else (score, idx, gt, eq)
+
+
+class AdamTables:
+    """Device copies of a UnivlSeg[] and a chunk table (adam_tables); keeps the tensors alive for the descriptors that point at them."""
+
+    def __init__(self, segs, chunk_seg, chunk_off, chunk_len):
+        self.segs, self.chunk_seg, self.chunk_off, self.chunk_len = segs, chunk_seg, chunk_off, chunk_len
+        self.nseg, self.nchunk = segs.numel() // C.sizeof(_lib.Seg), chunk_seg.numel()
+
+
+def adam_tables(segs, chunks, device="cuda"):
+    """segs: [(offset, numel, lr, weight_decay, max_grad_norm, active), ...] -> a device UnivlSeg[]; chunks: [(seg, offset, len), ...]
+    -> the chunk_seg / chunk_off / chunk_len arrays, as given (include/univl_hip.h: a tensor's chunks are listed contiguously; nothing
+    here checks or rearranges the lists -- the explicit form of optimization._Tables, for tests and tools)."""
+    arr = (_lib.Seg * len(segs))()
+    for s, (off, numel, lr, wd, mgn, active) in enumerate(segs):
+        arr[s].offset, arr[s].numel = int(off), int(numel)
+        arr[s].lr, arr[s].weight_decay, arr[s].max_grad_norm, arr[s].active = lr, wd, mgn, int(active)
+    return AdamTables(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device),
+                      torch.tensor([c[0] for c in chunks], dtype=torch.int32, device=device),
+                      torch.tensor([c[1] for c in chunks], dtype=torch.int64, device=device),
+                      torch.tensor([c[2] for c in chunks], dtype=torch.int32, device=device))
+
+
+def adam_desc(tb, p, g, m, v, *, sumsq, step, seg_scalars, p16=None, p16_lo=None, coef=None, b1=0.9, b2=0.999, eps=1e-6, warmup=-1.0,
+              t_total=-1, schedule=0, row_flags=None, flag_seg=0, row_len=0):
+    """UnivlAdam over the flat buffers p / g / m / v (and the optional shadow pair) with the tables of adam_tables.  The caller keeps
+    every tensor alive while the descriptor is used."""
+    _require_gpu(p, g, m, v, p16, p16_lo, sumsq, step, seg_scalars, coef, row_flags)
+    d = _lib.Adam()
+    d.p, d.g, d.m, d.v, d.p16, d.p16_lo = _p(p), _p(g), _p(m), _p(v), _p(p16), _p(p16_lo)
+    d.segs, d.nseg = _p(tb.segs), tb.nseg
+    d.chunk_seg, d.chunk_off, d.chunk_len, d.nchunk = _p(tb.chunk_seg), _p(tb.chunk_off), _p(tb.chunk_len), tb.nchunk
+    d.sumsq, d.coef, d.step, d.seg_scalars = _p(sumsq), _p(coef), _p(step), _p(seg_scalars)
+    d.b1, d.b2, d.eps, d.warmup, d.t_total, d.schedule = b1, b2, eps, warmup, int(t_total), int(schedule)
+    d.row_flags, d.flag_seg, d.row_len = _p(row_flags), int(flag_seg), int(row_len)
+    return d
+
+
+def grad_sumsq(g, tb, sumsq):
+    """sumsq[s] += the sum of squares of segment s of g, over the chunks of tb (univl_grad_sumsq)."""
+    _lib.check(_lib.lib().univl_grad_sumsq(_p(g), _p(tb.segs), tb.nseg, _p(tb.chunk_seg), _p(tb.chunk_off), _p(tb.chunk_len), tb.nchunk,
+                                           _p(sumsq), _stream()), "grad_sumsq")
+
+
+def clip_coef(sumsq, tb, max_norm, coef):
+    """coef[0] <- min(1, max_norm / (total norm + 1e-6)), coef[1] <- total norm over the active segments (univl_clip_coef)."""
+    _lib.check(_lib.lib().univl_clip_coef(_p(sumsq), _p(tb.segs), tb.nseg, float(max_norm), _p(coef), _stream()), "clip_coef")
+
+
+def scale_grads(g, tb, coef):
+    """g *= coef[0] over the chunks of tb (univl_scale_grads)."""
+    _lib.check(_lib.lib().univl_scale_grads(_p(g), _p(tb.segs), _p(tb.chunk_seg), _p(tb.chunk_off), _p(tb.chunk_len), tb.nchunk, _p(coef),
+                                            _stream()), "scale_grads")
+
+
+def bert_adam(desc):
+    _lib.check(_lib.lib().univl_bert_adam(_BYREF(desc), _stream()), "bert_adam")
+
+
+def bert_adam_range(desc, chunk_begin, chunk_count, do_prep=False, max_blocks=0):
+    _lib.check(_lib.lib().univl_bert_adam_range(_BYREF(desc), int(chunk_begin), int(chunk_count), int(bool(do_prep)), int(max_blocks),
+                                                _stream()), "bert_adam_range")
+
+
+def gemm_rider(gemm, adam, chunk_begin, chunk_count, max_blocks=0):
+    """A forward product with chunks [chunk_begin, +chunk_count) of a prepared BertAdam update (univl_gemm_rider)."""
+    _lib.check(_lib.lib().univl_gemm_rider(_BYREF(gemm), _BYREF(adam), int(chunk_begin), int(chunk_count), int(max_blocks), _stream()),
+               "gemm_rider")
 
 
 def cast_bf16(src, dst):
