@@ -190,7 +190,7 @@ def test_riding_weight_gradients_only_repackage_the_backward_plan(kw, kind, fres
     def canon(plan):
         chain, wgrads, pairs = [], [], []
         for i, op in enumerate(plan.ops):
-            kind_, name = op[0], op[3]
+            kind_, name = op.kind, op.name
             if kind_ == "call" and name == "univl_gemm":
                 d = plan.descs[i][0]
                 (wgrads if (d.trans_a and d.trans_b and flat_off(d.C32) and flat_off(d.C32)[0] == "g32") else chain).append(("gemm",) + rec(d))
@@ -241,36 +241,36 @@ def test_adam_rider_plan_builds_on_cpu(ab):
     base = build_step(m, "joint", 2, 16, 16, True)
     m._flat.adam_ride = True
     ride = build_step(m, "joint", 2, 16, 16, True)
-    names0 = [op[3] for op in base.fwd.ops]
-    names1 = [op[3] for op in ride.fwd.ops]
+    names0 = [op.name for op in base.fwd.ops]
+    names1 = [op.name for op in ride.fwd.ops]
     L0_fused = cfg.text_num_hidden_layers + cfg.visual_num_hidden_layers
     assert [n.replace("univl_gemm_rider", "univl_gemm") for n in names1] == names0
     # (desc, key, slot, nslots) of every launch that can carry chunks: plain rider launches and the (product + LayerNorm) launches
-    riders = [op[2] for op in ride.fwd.ops if op[0] == "rider"] + [(op[2][0],) + op[2][3:] for op in ride.fwd.ops if op[0] == "gemm_ln" and op[2][3] is not None]
+    riders = [(op.descs[0], op.key, op.slot, op.nslots) for op in ride.fwd.ops if op.kind in ("rider", "gemm_ln") and op.key is not None]
     # round 5: the q | k | v projection of a layer is computed inside the attention forward launch, which carries its quarter of the chunks
-    riders += [(op[2][1],) + op[2][2:] for op in ride.fwd.ops if op[0] == "attn_fwd_fused" and op[2][2] is not None]
+    riders += [(op.descs[0], op.key, op.slot, op.nslots) for op in ride.fwd.ops if op.kind == "attn_fwd_fused" and op.key is not None]
     assert sum(1 for n in names1 if n == "univl_attention_fwd_fused") == L0_fused and "univl_attention_fwd" not in names1
     L_t, L_v = cfg.text_num_hidden_layers, cfg.visual_num_hidden_layers
     assert len(riders) == 4 * ((L_t - 1) + (L_v - 1))
     # K8 / K10: the attention-output and FFN2 products of every layer carry their LayerNorm (round 4); no separate launch is left for those
-    folds = [op for op in ride.fwd.ops if op[0] == "gemm_ln"]
-    assert len(folds) == 2 * (L_t + L_v) and len([op for op in base.fwd.ops if op[0] == "gemm_ln"]) == len(folds)
+    folds = [op for op in ride.fwd.ops if op.kind == "gemm_ln"]
+    assert len(folds) == 2 * (L_t + L_v) and len([op for op in base.fwd.ops if op.kind == "gemm_ln"]) == len(folds)
     assert sum(1 for n in names1 if n == "univl_layernorm_fwd") == 2          # NormalizeVideo + the video embedding LayerNorm
     ab(ln_fold=0)
     unfolded = build_step(m, "joint", 2, 16, 16, True)
     ab(ln_fold=None)
-    assert sum(1 for op in unfolded.fwd.ops if op[3] == "univl_layernorm_fwd") == 2 + len(folds) and not [op for op in unfolded.fwd.ops if op[0] == "gemm_ln"]
+    assert sum(1 for op in unfolded.fwd.ops if op.name == "univl_layernorm_fwd") == 2 + len(folds) and not [op for op in unfolded.fwd.ops if op.kind == "gemm_ln"]
     carried = {("layer", "bert", l) for l in range(1, L_t)} | {("layer", "visual", l) for l in range(1, L_v)}
     assert ride.fwd.rider_keys == carried
     for key in carried:
         assert sorted(r[2] for r in riders if r[1] == key) == [0, 1, 2, 3]
     assert not base.fwd.rider_keys and len(ride.fwd.launches("univl_gemm")) == len(base.fwd.launches("univl_gemm"))
-    assert [op[3] for op in ride.backward_plan(True).ops] == [op[3] for op in base.backward_plan(True).ops]
+    assert [op.name for op in ride.backward_plan(True).ops] == [op.name for op in base.backward_plan(True).ops]
     # ... and the backward twin: every LayerNorm backward of a stack but its topmost one rides in the pair launch of the dgrad that feeds it
-    bw = [op[3] for op in ride.backward_plan(True).ops]
+    bw = [op.name for op in ride.backward_plan(True).ops]
     assert bw.count("univl_gemm_pair_ln") == (2 * L_t - 1) + (2 * L_v - 1)
     ab(ln_fold_bwd=0)
-    bw0 = [op[3] for op in build_step(m, "joint", 2, 16, 16, True).backward_plan(True).ops]
+    bw0 = [op.name for op in build_step(m, "joint", 2, 16, 16, True).backward_plan(True).ops]
     ab(ln_fold_bwd=None)
     assert bw0.count("univl_gemm_pair_ln") == 0 and bw0.count("univl_layernorm_bwd") == bw.count("univl_layernorm_bwd") + bw.count("univl_gemm_pair_ln")
 
@@ -305,15 +305,15 @@ def test_adam_rider_slots_from_1536_tokens_follow_the_library(ab):
     m._flat.adam_ride = True
     for B in (32, 128):
         st = build_step(m, "joint", B, 48, 48, True)
-        riders = [op[2] for op in st.fwd.ops if op[0] == "rider"]
+        riders = [(op.descs[0], op.key, op.slot, op.nslots) for op in st.fwd.ops if op.kind == "rider"]
         assert riders and all(_lib.lib().univl_gemm_rider_fits(C.byref(d)) == 1 for d, _, _, _ in riders)
-        plain = [st.fwd.descs[i][0] for i, op in enumerate(st.fwd.ops) if op[0] == "call" and op[3] == "univl_gemm"]
+        plain = [st.fwd.descs[i][0] for i, op in enumerate(st.fwd.ops) if op.kind == "call" and op.name == "univl_gemm"]
         by_key = {}
         for _, key, slot, n in riders:
             by_key.setdefault(key, []).append((slot, n))
         for op in st.fwd.ops:        # at 1536 tokens the fused attention forward still runs and carries its share (slot 0)
-            if op[0] == "attn_fwd_fused" and op[2][2] is not None:
-                by_key.setdefault(op[2][2], []).append((op[2][3], op[2][4]))
+            if op.kind == "attn_fwd_fused" and op.key is not None:
+                by_key.setdefault(op.key, []).append((op.slot, op.nslots))
         assert set(by_key) == {("layer", "bert", l) for l in range(1, cfg.text_num_hidden_layers)}      # (one video layer: nothing to carry)
         for key, sl in by_key.items():
             assert sorted(s_ for s_, _ in sl) == list(range(sl[0][1])), (B, key, sl)
@@ -455,11 +455,11 @@ def test_deep_weight_gradients_take_the_big_tile_without_fused_bias_gradients(ab
     def groups(plan):
         out, lambdas, pairs = [], 0, 0
         for i, op in enumerate(plan.ops):
-            if op[0] == "group":
+            if op.kind == "group":
                 out.append(plan.descs[i])
-            elif op[0] == "pair":
+            elif op.kind == "pair":
                 pairs += 1
-            elif op[0] == "py" and op[3] == "<lambda>":
+            elif op.kind == "py" and op.name == "<lambda>":
                 lambdas += 1
         return out, lambdas, pairs
 
@@ -608,3 +608,147 @@ def test_gemm256_lds_image_and_fragment_reads_agree_and_are_conflict_free(trans)
                     for half in (range(0, 32), range(32, 64)):      # 32 lanes x 8 bytes = every one of the 64 banks once
                         banks = [((addr[lane] >> 2) + d) & 63 for lane in half for d in (0, 1)]
                         assert len(set(banks)) == 64
+
+
+def test_riders_split_a_range_over_the_slots_and_carry_once():
+    """engine.Riders.take, the one statement of how a key's chunk range is dealt to the launches that carry it: slot s of n gets
+    [first + count * s // n, first + count * (s + 1) // n) -- contiguous, disjoint, covering the range, also where n does not divide
+    the count (or exceeds it: empty parts); a second request for the same (key, slot) and any request under an unknown key get nothing."""
+    from univl_amd import _lib as L_
+    from univl_amd.engine import Riders
+    for first, count in ((0, 1), (5, 7), (3, 64)):
+        for nslots in (1, 2, 3, 5):
+            rd = Riders(L_.Adam(), {"k": (first, count)}, max_blocks=3)
+            parts = [rd.take("k", s, nslots) for s in range(nslots)]
+            assert [lo for lo, _ in parts] == [first + count * s // nslots for s in range(nslots)]
+            assert all(n >= 0 for _, n in parts) and parts[0][0] == first and parts[-1][0] + parts[-1][1] == first + count
+            assert all(a[0] + a[1] == b[0] for a, b in zip(parts, parts[1:]))
+            assert rd.used == {("k", s) for s in range(nslots)}
+            assert all(rd.take("k", s, nslots) is None for s in range(nslots))
+            assert rd.take("other", 0, nslots) is None and rd.take(None, 0, 1) is None and ("other", 0) not in rd.used
+            assert rd.pending() == [("k", first, count, True)] and Riders(L_.Adam(), {"k": (first, count)}).pending() == [("k", first, count, False)]
+            assert rd.signature() == (bytes(L_.Adam()), (("k", (first, count)),), 3)
+
+
+def test_carried_chunk_range_is_validated_once_for_every_entry_point():
+    """csrc/adam_body.h: adam_range_check, the one check of a chunk range of a prepared update, in front of every launch of the four
+    entry points that apply or carry one.  UNIVL_EINVAL with a message that names the entry point for a negative begin, a range one
+    past the table, a negative count, each mandatory table pointer NULL in turn and a misaligned p; the two entry points that also run
+    without an update (univl_gemm_ln, univl_attention_fwd_fused) still pass their dry run with adam = NULL and no chunks, univl_gemm_rider
+    does not take a NULL update.  Host only: every call here returns before anything is launched (null stream, no device)."""
+    import ctypes as C
+    from univl_amd import ops
+    from univl_amd.engine import _gemm_desc
+    L, EINVAL = _lib.lib(), -1
+    bf, dt = torch.bfloat16, _lib.DT_BF16
+    T, H, I, NH, S = 192, 768, 3072, 12, 48
+    a, w, x, x2 = torch.zeros(T, I, dtype=bf), torch.zeros(H, I, dtype=bf), torch.zeros(T, H), torch.zeros(T, H)
+    gm, bt, st, o16 = torch.ones(H), torch.zeros(H), torch.zeros(T, 2), torch.zeros(T, H, dtype=bf)
+    ctr = torch.zeros(2 * 3, dtype=torch.int32)
+    cp = C.c_void_p(ctr.data_ptr())
+    g = _gemm_desc(dt, a, I, w, I, T, H, I, out32=x, ldc=H, ksplit=8)
+    ln = ops.layernorm_desc(dt, T, H, x=x, residual=x2, gamma=gm, beta=bt, y=x, stats=st, out16=o16)
+    xin, wq, qkv = torch.zeros(T, H, dtype=bf), torch.zeros(3 * H, H, dtype=bf), torch.zeros(T, 3 * H, dtype=bf)
+    ctx, lse = torch.zeros(T, H, dtype=bf), torch.zeros(T // S, NH, S)
+    gq = _gemm_desc(dt, xin, H, wq, H, T, 3 * H, H, out16=qkv, ldc=3 * H)
+    at = ops.attention_desc(dt, T // S, NH, S, S, (qkv, 0), 3 * H, (qkv, H), 3 * H, (qkv, 2 * H), 3 * H, ctx, H, lse)
+    # a complete update descriptor over host buffers (never dereferenced: every call below is refused on its fields alone)
+    n, nseg = 7, 2
+    flat = {k: torch.zeros(64) for k in "pgmv"}
+    tabs = dict(segs=torch.zeros(nseg * C.sizeof(_lib.Seg), dtype=torch.uint8), chunk_seg=torch.zeros(n, dtype=torch.int32),
+                chunk_off=torch.zeros(n, dtype=torch.int64), chunk_len=torch.zeros(n, dtype=torch.int32),
+                seg_scalars=torch.zeros(2 * nseg), sumsq=torch.zeros(nseg), step=torch.zeros(nseg, dtype=torch.int32))
+
+    def desc(**over):
+        d = _lib.Adam()
+        for k, t in list(flat.items()) + list(tabs.items()):
+            setattr(d, k, t.data_ptr())
+        d.nseg, d.nchunk = nseg, n
+        for k, v in over.items():
+            setattr(d, k, v)
+        return d
+
+    def ref(d):
+        return None if d is None else C.byref(d)
+
+    entries = {"univl_bert_adam_range": lambda d, b, c: L.univl_bert_adam_range(ref(d), b, c, 0, 0, None),
+               "univl_gemm_rider": lambda d, b, c: L.univl_gemm_rider(C.byref(g), ref(d), b, c, 0, None),
+               "univl_gemm_ln": lambda d, b, c: L.univl_gemm_ln(C.byref(g), C.byref(ln), cp, ref(d), b, c, 0, 1, None),
+               "univl_attention_fwd_fused": lambda d, b, c: L.univl_attention_fwd_fused(C.byref(at), C.byref(gq), ref(d), b, c, 0, 1, None)}
+    tables = ("p", "g", "m", "v", "segs", "chunk_seg", "chunk_off", "chunk_len", "seg_scalars")
+    for name, call in entries.items():
+        bad = [("begin -1", desc(), -1, 2), ("one past the table", desc(), n - 1, 2), ("negative count", desc(), 0, -1),
+               ("misaligned p", desc(p=flat["p"].data_ptr() + 4), 0, n)]
+        bad += [("NULL " + f, desc(**{f: None}), 0, n) for f in tables]
+        for what, d, b, c in bad:
+            assert call(d, b, c) == EINVAL, (name, what)
+            msg = L.univl_last_error().decode()
+            assert name + ":" in msg, (name, what, msg)
+            if what in ("begin -1", "one past the table", "negative count"):
+                assert "%s: chunks [%d, +%d) of %d" % (name, b, c, n) in msg, (name, what, msg)
+            if what == "misaligned p":
+                assert "aligned" in msg, (name, msg)
+    assert entries["univl_gemm_rider"](None, 0, 0) == EINVAL and "univl_gemm_rider:" in L.univl_last_error().decode()
+    assert entries["univl_bert_adam_range"](None, 0, 0) == EINVAL
+    import univl_amd
+    if not univl_amd.deterministic():          # (deterministic mode refuses the fold itself: UNIVL_EUNSUPPORTED, after this check)
+        assert entries["univl_gemm_ln"](None, 0, 0) == 0
+    assert entries["univl_attention_fwd_fused"](None, 0, 0) == 0
+    for name in ("univl_gemm_ln", "univl_attention_fwd_fused"):       # ... but chunks without an update are refused there too
+        assert entries[name](None, 0, 2) == EINVAL and name + ":" in L.univl_last_error().decode()
+
+
+def test_plan_ops_still_read_by_position_like_the_tuples_they_replace():
+    """engine.Op.__getitem__: op[0] .. op[4] are what the five-tuple of every kind held -- (kind, fn, payload, name, stream) for the launch
+    forms with each form's own payload, (kind, f, None, name, stream) for callables, (kind, key, None, kind, stream) for record / wait,
+    ("dep", src, dst, "dep", 0) -- so that tests written against the tuples keep passing; the same values are the named fields."""
+    import ctypes as C
+    from univl_amd.engine import Plan
+    L, G = _lib.lib(), _lib.Gemm
+    d, d2, ln, at, ctr = G(), G(), _lib.LayerNorm(), _lib.Attention(), torch.zeros(6, dtype=torch.int32)
+    d.M, d2.M = 3, 5
+    key = ("layer", "bert", 1)
+
+    def f():
+        pass
+
+    p = Plan()
+    p.add_gemm_rider(d, key, 1, 4, stream=2)
+    p.add_gemm_ln(d, ln, ctr, key, 2, 4)
+    p.add_gemm_ln(d, ln, ctr)
+    p.add("univl_gemm", d, stream=1)
+    p.add_pair_call("univl_pool_pair_fwd", d, d2)
+    p.add_gemm_group([d, d2], stream=1, max_blocks=7)
+    p.add_gemm_pair(d, d2)
+    p.add_attn_fwd_fused(at, d, key, 0, 4)
+    p.add_attn_bwd_fused(at, d, None)
+    p.add_gemm_pair_ln(d, d2, ln, ctr)
+    p.add_callable(f, stream=1)
+    p.add_callable(f, eager=True)
+    p.add_callable(f, with_streams=True)
+    p.wait_point("w", stream=1)
+    p.record("r", stream=2)
+    p.fork(0, 2)
+    ops_ = p.ops
+    assert [tuple(op[i] for i in (0, 3, 4)) for op in ops_] == [(op.kind, op.name, op.stream) for op in ops_] == [
+        ("rider", "univl_gemm_rider", 2), ("gemm_ln", "univl_gemm_ln", 0), ("gemm_ln", "univl_gemm_ln", 0), ("call", "univl_gemm", 1),
+        ("call2", "univl_pool_pair_fwd", 0), ("group", "univl_gemm_group", 1), ("pair", "univl_gemm_pair", 0),
+        ("attn_fwd_fused", "univl_attention_fwd_fused", 0), ("attn_fused", "univl_attention_bwd_fused", 0), ("pair_ln", "univl_gemm_pair_ln", 0),
+        ("py", "f", 1), ("eager", "f", 0), ("pys", "f", 0), ("wait", "wait", 1), ("record", "record", 2), ("dep", "dep", 0)]
+    fns = [L.univl_gemm_rider, L.univl_gemm_ln, L.univl_gemm_ln, L.univl_gemm, L.univl_pool_pair_fwd, L.univl_gemm_group_limited, L.univl_gemm_pair,
+           L.univl_attention_fwd_fused, L.univl_attention_bwd_fused, L.univl_gemm_pair_ln]
+    assert all(op[1] is fn and op.fn is fn for op, fn in zip(ops_, fns))
+    assert [op[1] for op in ops_[10:]] == [f, f, f, "w", "r", 0] and [op[2] for op in ops_[10:]] == [None] * 5 + [2]
+    assert (ops_[13].key, ops_[14].key, ops_[15].src, ops_[15].dst) == ("w", "r", 0, 2)
+    rider, fold, fold0, call, call2, group, pair, afwd, abwd, pln = (op[2] for op in ops_[:10])
+    assert rider[0] is d and rider[1:] == (key, 1, 4) and (ops_[0].key, ops_[0].slot, ops_[0].nslots) == (key, 1, 4) and ops_[0].descs == [d]
+    assert fold[:3] == (d, ln, ctr) and fold[0] is d and fold[2] is ctr and fold[3:] == (key, 2, 4) and fold0[3:] == (None, 0, 1) and ops_[2].key is None
+    assert call._obj is d                                                    # C.byref(desc)
+    assert call2[0] is d and call2[1] is d2 and len(call2) == 2
+    assert [g.M for g in group[0]] == [3, 5] and group[1:] == (2, 7)        # (array of copies, n, max_blocks)
+    assert isinstance(pair, G * 2) and [g.M for g in pair] == [3, 5]
+    assert afwd[0] is at and afwd[1] is d and afwd[2:] == (key, 0, 4) and ops_[7].attn is at
+    assert abwd[0] is at and abwd[1] is d and abwd[2] is None and len(abwd) == 3
+    assert isinstance(pln[0], G * 2) and pln[1] is ln and pln[2] is ctr and len(pln) == 3
+    with pytest.raises(IndexError):
+        ops_[0][5]

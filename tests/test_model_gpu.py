@@ -274,10 +274,10 @@ def plan_ops(model):
     for st in model._steps.values():
         if not hasattr(st, "fwd"):
             continue                   # the evaluation entry points keep other objects in the same cache
-        out += [op[3] for op in st.fwd.ops]
+        out += [op.name for op in st.fwd.ops]
         for fresh in (True, False):
             try:
-                out += [op[3] for op in st.backward_plan(fresh).ops]
+                out += [op.name for op in st.backward_plan(fresh).ops]
             except Exception:          # eval steps have no backward
                 pass
     return out
@@ -535,7 +535,7 @@ def test_large_batch_backward_paths_match_the_default_ones(ab):
     model.train()
     call(model, O.synthetic_batch(cfg, rows, seed=dseed)).backward()
     st = next(iter(model._steps.values()))
-    kinds = [op[3] for op in st.backward_plan(True).ops]
+    kinds = [op.name for op in st.backward_plan(True).ops]
     assert kinds.count("univl_gemm_pair") == 0 and kinds.count("univl_gemm_group") >= cfg.text_num_hidden_layers + cfg.visual_num_hidden_layers
     assert ref.keys() == new.keys()
     assert float(ref["__loss__"]) == float(new["__loss__"])
@@ -1098,7 +1098,7 @@ def test_weight_gradient_packaging_matches_golden(golden_dir, name, ride, ab):
     model.train()
     call(model, O.synthetic_batch(cfg, rows, seed=dseed)).backward()
     st = next(iter(model._steps.values()))
-    kinds = [op[3] for op in st.backward_plan(True).ops]
+    kinds = [op.name for op in st.backward_plan(True).ops]
     if ride == "1":
         # (round 5: the attention-output projection's pair became the fused attention backward, which carries that weight gradient)
         layers = cfg.text_num_hidden_layers + cfg.visual_num_hidden_layers
@@ -1137,11 +1137,11 @@ def test_adam_update_riding_in_rectangular_tile_products_matches_the_plain_updat
 
     def spy(model):
         st = next(iter(model._steps.values()))
-        riders = [op[2] for op in st.fwd.ops if op[0] == "rider"]
-        _probe["riders"] = [(key, slot, n) for _, key, slot, n in riders]
-        _probe["fits"] = [_lib.lib().univl_gemm_rider_fits(C.byref(d)) for d, _, _, _ in riders]
+        riders = [op for op in st.fwd.ops if op.kind == "rider"]
+        _probe["riders"] = [(op.key, op.slot, op.nslots) for op in riders]
+        _probe["fits"] = [_lib.lib().univl_gemm_rider_fits(C.byref(op.descs[0])) for op in riders]
         # at 1536 tokens the fused attention forward still runs and carries its share of the layer's chunks (slot 0)
-        _probe["riders"] += [(op[2][2], op[2][3], op[2][4]) for op in st.fwd.ops if op[0] == "attn_fwd_fused" and op[2][2] is not None]
+        _probe["riders"] += [(op.key, op.slot, op.nslots) for op in st.fwd.ops if op.kind == "attn_fwd_fused" and op.key is not None]
     l, p, info = _train("graph", "joint_b32", steps=3, dtype=torch.bfloat16, spy=spy)
     assert info["mode"] == "whole"
     assert _probe["riders"] and all(f == 1 for f in _probe["fits"]), _probe

@@ -594,3 +594,92 @@ def test_attention_fwd_fused_carrying_chunks():
     assert torch.equal(bits(q1), bits(q0)) and torch.equal(bits(c1), bits(c0)) and torch.equal(l1, l0) and bool(c1.any())
     same_state(a, b)
     a.assert_guards(also_unchanged=("g",))
+
+
+# ---------------------------------------------------------------------------------------------------------------- a plan that carries
+def test_plan_deals_a_range_to_its_three_carrying_forms_once():
+    """engine.Plan with engine.Riders set, on a hand-built plan at the smallest shapes the three carrying kernels accept (192 tokens,
+    hidden 768, 12 heads): a fused attention forward, a (product, LayerNorm) launch (K = 3072 in 8 slices) and a rider product (768 ->
+    3072, GELU) are slots 0 / 1 / 2 of 3 of ONE key; a second rider launch repeats slot 2 and must carry nothing.  The table has 7 chunks
+    (2 / 2 / 3 over the slots), the last tensor's length is no multiple of 4.  After one eager run: p / m / v and both shadows
+    bit-identical to one univl_bert_adam_range over the 7 chunks on a copy, exactly the three slots used, and the products equal to the
+    same plan run with nothing riding -- bit for bit for the attention launch and the rider (the bounds of test_gemm_rider_64_tile and
+    test_attention_fwd_fused_carrying_chunks), within test_gemm_ln_fold_matches_the_two_launches' bounds for the split product that
+    meets in atomics (2e-5 relative to the largest value in fp32, 1e-2 in bf16)."""
+    from univl_amd.engine import Plan, Riders
+    B, S, NH, H, I, bf = 4, 48, 12, 768, 3072, torch.bfloat16
+    T, dt = B * S, ops.dtype_code(torch.bfloat16)
+    # update: three tensors in 2 + 3 + 2 chunks of at most 8192 elements, the last one 8192 + 1027 long
+    CH = 8192
+    segs = [(0, 2 * CH, 1e-3, 0.01, 1.0, 1), (2 * CH, 3 * CH, 2e-3, 0.0, 1.0, 1), (5 * CH, CH + 1027, 1e-3, 0.01, 1.0, 1)]
+    chunks = [(0, 0, CH), (0, CH, CH), (1, 2 * CH, CH), (1, 3 * CH, CH), (1, 4 * CH, CH), (2, 5 * CH, CH), (2, 6 * CH, 1027)]
+    total = 6 * CH + 1027
+    tb = ops.adam_tables(segs, chunks, DEV)
+
+    def state():
+        s = {k: gen(total + 64, seed=i, scale=sc).to(DEV) for i, (k, sc) in enumerate((("p", 0.05), ("g", 0.01), ("m", 0.01), ("v", 0.01)))}
+        s["v"] = s["v"].abs()
+        s["p16"] = s["p"].to(bf)
+        s["p16_lo"] = (s["p"] - s["p16"].float()).to(bf)
+        s["sumsq"] = torch.stack([(s["g"][o:o + k].double() ** 2).sum() for o, k, *_ in segs]).float()
+        s["step"] = torch.full((len(segs),), 7, dtype=torch.int32, device=DEV)
+        s["scal"] = torch.zeros(2 * len(segs), device=DEV)
+        s["coef"] = torch.tensor([1.0, 0.0], device=DEV)
+        d = ops.adam_desc(tb, s["p"], s["g"], s["m"], s["v"], sumsq=s["sumsq"], step=s["step"], seg_scalars=s["scal"], p16=s["p16"],
+                          p16_lo=s["p16_lo"], coef=s["coef"], b1=R.B1, b2=R.B2, eps=R.EPS, warmup=0.1, t_total=50)
+        ops.bert_adam_range(d, 0, 0, do_prep=True)
+        return s, d
+
+    a, da = state()
+    b, db = state()
+    # products
+    x = gen(T, H, seed=11).to(DEV, bf)
+    wqkv, bqkv = gen(3 * H, H, seed=12, scale=0.05).to(DEV, bf), gen(3 * H, seed=13).to(DEV)
+    qkv, ctx, lse = torch.zeros(T, 3 * H, device=DEV, dtype=bf), torch.zeros(T, H, device=DEV, dtype=bf), torch.zeros(B, NH, S, device=DEV)
+    at = ops.attention_desc(dt, B, NH, S, S, (qkv, 0), 3 * H, (qkv, H), 3 * H, (qkv, 2 * H), 3 * H, ctx, H, lse)
+    gq = ops.gemm_desc(x, wqkv, T, 3 * H, H, out16=qkv, bias=bqkv)
+    f, w2, b2 = gen(T, I, seed=14).to(DEV, bf), gen(H, I, seed=15, scale=I ** -0.5).to(DEV, bf), gen(H, seed=16).to(DEV)
+    res, gm, bt = gen(T, H, seed=17).to(DEV), (1.0 + 0.1 * gen(H, seed=18)).to(DEV), gen(H, seed=19).to(DEV)
+    y, stats, o32, o16 = torch.zeros(T, H, device=DEV), torch.zeros(T, 2, device=DEV), torch.zeros(T, H, device=DEV), torch.zeros(T, H, device=DEV, dtype=bf)
+    g2 = ops.gemm_desc(f, w2, T, H, I, out32=y, bias=b2, ksplit=8)
+    ln = ops.layernorm_desc(dt, T, H, x=y, residual=res, gamma=gm, beta=bt, y=y, stats=stats, out32=o32, out16=o16)
+    ctr = torch.zeros(2 * ((T + 63) // 64), dtype=torch.int32, device=DEV)
+    w1, b1 = gen(I, H, seed=20, scale=H ** -0.5).to(DEV, bf), gen(I, seed=21).to(DEV)
+    u, f1 = torch.zeros(T, I, device=DEV, dtype=bf), torch.zeros(T, I, device=DEV, dtype=bf)
+    g1 = ops.gemm_desc(x, w1, T, I, H, out16=f1, bias=b1, aux=u, gelu="fwd")
+    assert ops.attention_fwd_fused(at, gq, dry_run=True) and _lib.lib().univl_gemm_rider_fits(C.byref(g1)) == 1
+    if not univl_amd.deterministic():
+        assert ops.gemm_ln(g2, ln, ctr, dry_run=True)
+    key = ("layer", "test", 1)
+    plan = Plan()
+    plan.add_attn_fwd_fused(at, gq, key, 0, 3)
+    plan.add_gemm_ln(g2, ln, ctr, key, 1, 3)
+    plan.add_gemm_rider(g1, key, 2, 3)
+    plan.add_gemm_rider(g1, key, 2, 3)
+    assert plan.rider_keys == {key} and len(plan) == 4
+    outs = dict(qkv=qkv, ctx=ctx, lse=lse, y=y, stats=stats, o32=o32, o16=o16, u=u, f1=f1)
+    plan.run()
+    torch.cuda.synchronize()
+    plain = {k: t.clone() for k, t in outs.items()}
+    for k in "pmv":
+        assert torch.equal(a[k], b[k])               # nothing rode
+    for t in outs.values():
+        t.zero_()
+    plan.riders = Riders(da, {key: (0, len(chunks))})
+    try:
+        plan.run()
+    finally:
+        rd, plan.riders = plan.riders, None
+    ops.bert_adam_range(db, 0, len(chunks))
+    torch.cuda.synchronize()
+    assert rd.used == {(key, 0), (key, 1), (key, 2)}
+    for k in ("p", "m", "v", "p16", "p16_lo"):
+        assert torch.equal(bits(a[k]), bits(b[k])), k
+    assert torch.equal(a["g"], b["g"]) and torch.equal(a["step"], b["step"]) and not torch.equal(a["p"][:total], gen(total + 64, seed=0, scale=0.05).to(DEV)[:total])
+    assert int(ctr.abs().sum()) == 0
+    for k in ("qkv", "ctx", "lse", "u", "f1"):
+        assert torch.equal(bits(outs[k]), bits(plain[k])) and bool(outs[k].any()), k
+    for k in ("y", "stats", "o32", "o16"):
+        err = float((outs[k].double() - plain[k].double()).abs().max() / plain[k].double().abs().max())
+        print("plan carry: %s relative error %.3g" % (k, err))
+        assert err < (1e-2 if k == "o16" else 2e-5), (k, err)

@@ -397,8 +397,8 @@ def test_candidates_share_one_cross_encoder_run(dtype):
         """the launch's extent: (M, N, K) of a product, (B, Sq, Sk) of an attention (inside a fused launch too), rows otherwise"""
         op, d = plan.ops[i], plan.descs.get(i, [None])[0]
         out = ()
-        if op[0] == "attn_fwd_fused":
-            out += (op[2][0].B, op[2][0].Sq, op[2][0].Sk)
+        if op.kind == "attn_fwd_fused":
+            out += (op.attn.B, op.attn.Sq, op.attn.Sk)
         if isinstance(d, _lib.Gemm):
             return out + (d.M, d.N, d.K)
         if isinstance(d, _lib.Attention):
@@ -406,15 +406,15 @@ def test_candidates_share_one_cross_encoder_run(dtype):
         return out + ((d.rows,) if hasattr(d, "rows") else ())
 
     for plan in (many.plan, one.plan):
-        assert [op[3] for op in plan.ops[:len(base)]] == [op[3] for op in base.ops]
+        assert [op.name for op in plan.ops[:len(base)]] == [op.name for op in base.ops]
         assert [shape_of(plan, i) for i in range(len(base))] == [shape_of(base, i) for i in range(len(base))]
     tail = range(len(base), len(many.plan))
-    attn = [many.plan.descs[i][0] for i in tail if many.plan.ops[i][3] == "univl_attention_fwd"]
+    attn = [many.plan.descs[i][0] for i in tail if many.plan.ops[i].name == "univl_attention_fwd"]
     assert attn and all(d.B == n * nc and d.Sq == Wd and d.Sk in (Wd, S) for d in attn)       # the decoder's, over the captions
-    cross_attn = [op[2][0] if op[0] == "attn_fwd_fused" else many.plan.descs[i][0] for i, op in enumerate(many.plan.ops[:len(base)])
-                  if op[3].startswith("univl_attention")]
+    cross_attn = [op.attn if op.kind == "attn_fwd_fused" else many.plan.descs[i][0] for i, op in enumerate(many.plan.ops[:len(base)])
+                  if op.name.startswith("univl_attention")]
     assert cross_attn and all(d.B == n and d.Sq == S and d.Sk == S for d in cross_attn)      # the cross encoder's, over the instances
-    assert [op[3] for op in many.plan.ops].count("univl_vocab_score") == 1 and many.plan.ops[-1][3] == "univl_vocab_score"
+    assert [op.name for op in many.plan.ops].count("univl_vocab_score") == 1 and many.plan.ops[-1].name == "univl_vocab_score"
     assert not many.plan._side                                   # one stream
 
 

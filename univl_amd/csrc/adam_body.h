@@ -3,6 +3,7 @@
 // as a device function, for the kernels that carry optimizer work beside their own (gemm.hip: gemm_adam_kernel, gemm_adam_rect_kernel,
 // gemm_ln_kernel, attn_fwd_qkv_kernel), with adam_apply_kernel's walk and non-temporal policy; NTH = threads of the calling workgroup.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "univl_hip.h"
 
@@ -11,6 +12,39 @@
 // refuses a descriptor that does not (UNIVL_EINVAL, before any launch).
 static inline bool adam_bases_aligned(const UnivlAdam* a) {
     return aligned16(a->p) && aligned16(a->g) && aligned16(a->m) && aligned16(a->v) && ((((uintptr_t)a->p16 | (uintptr_t)a->p16_lo) & 7) == 0);
+}
+
+// What every kernel that walks chunks of an update reads (univl_bert_adam / _range also need sumsq, step and nseg for the scalar kernel).
+static inline bool adam_tables_present(const UnivlAdam* a) {
+    return a->p && a->g && a->m && a->v && a->segs && a->chunk_seg && a->chunk_off && a->chunk_len && a->seg_scalars && a->nchunk > 0;
+}
+
+// The check of a chunk range [begin, begin + count) of a prepared update, for every entry point `who` that applies or carries one, before
+// any launch.  none_ok: the entry point runs without an update too (count == 0; the descriptor may then be NULL and is not looked at).
+static inline int adam_range_check(const char* who, const UnivlAdam* a, int32_t begin, int32_t count, bool none_ok) {
+    if (none_ok && count == 0) return UNIVL_OK;
+    UNIVL_CHECK_ARG(a != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
+    UNIVL_CHECK_ARG(adam_tables_present(a) && begin >= 0 && count >= 0 && count <= a->nchunk - begin, UNIVL_EINVAL,
+                    "%s: chunks [%d, +%d) of %d", who, begin, count, a->nchunk);
+    UNIVL_CHECK_ARG(adam_bases_aligned(a), UNIVL_EINVAL, "%s: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned", who);
+    return UNIVL_OK;
+}
+
+// A checked range as the kernels take it: the descriptor by value (the zero descriptor when nothing rides), chunks [c0, c1), and the
+// workgroups that walk them (one per chunk, at most max_blocks where that is > 0).
+struct AdamRange {
+    UnivlAdam adam;
+    int c0, c1, blocks;
+};
+static inline AdamRange adam_range(const UnivlAdam* a, int32_t begin, int32_t count, int32_t max_blocks) {
+    AdamRange r = {};
+    r.c0 = r.c1 = begin;
+    if (count > 0) {
+        r.adam = *a;
+        r.c1 = begin + count;
+        r.blocks = (max_blocks > 0 && max_blocks < count) ? max_blocks : count;
+    }
+    return r;
 }
 
 // One element of the update, for EVERY kernel that applies it (adam_apply_kernel in optim.hip, adam_chunk below).  The association is pinned
@@ -29,6 +63,11 @@ __device__ __forceinline__ void adam_elem(float& p, const float g, float& m, flo
 __device__ __forceinline__ float adam_elem_decay_only(const float p, const float lr, const float wd) { return __builtin_fmaf(-lr, wd * p, p); }
 
 bool univl_adam_nt();      // optim.hip: UNIVL_ADAM_NT (default 1): non-temporal loads / stores of the 28 fp32 bytes per parameter
+// f(std::bool_constant<NT>) with the switch's value: the one place that picks the <NT> instantiation of a kernel that applies the update
+template <typename F> static inline void adam_with_nt(F&& f) {
+    if (univl_adam_nt()) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 template <bool NT> __device__ __forceinline__ f32x4_t adam_ld4(const float* p, int i) {
     const f32x4_t* q = reinterpret_cast<const f32x4_t*>(p) + i;

@@ -1743,12 +1743,9 @@ extern "C" int univl_attention_fwd_fused(const UnivlAttention* at, const UnivlGe
                                          int32_t chunk_count, int32_t max_blocks, int32_t dry_run, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     UNIVL_CHECK_ARG(at != nullptr && qkv != nullptr, UNIVL_EINVAL, "univl_attention_fwd_fused: null descriptor");
-    UNIVL_CHECK_ARG(chunk_count == 0 || (adam != nullptr && adam->p && adam->g && adam->m && adam->v && adam->segs && adam->chunk_seg &&
-                                         adam->chunk_off && adam->chunk_len && adam->seg_scalars && chunk_begin >= 0 && chunk_count > 0 &&
-                                         chunk_begin + chunk_count <= adam->nchunk),
-                    UNIVL_EINVAL, "univl_attention_fwd_fused: chunks [%d, +%d)", chunk_begin, chunk_count);
-    UNIVL_CHECK_ARG(chunk_count == 0 || adam_bases_aligned(adam), UNIVL_EINVAL, "univl_attention_fwd_fused: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
-    int rc = attn_check(at, "univl_attention_fwd_fused", false);
+    int rc = adam_range_check("univl_attention_fwd_fused", adam, chunk_begin, chunk_count, true);
+    if (rc) return rc;
+    rc = attn_check(at, "univl_attention_fwd_fused", false);
     if (rc) return rc;
     const int Sk_pad = (at->Sk + 31) / 32 * 32;
     const UnivlGemm* g = qkv;
@@ -1775,19 +1772,14 @@ extern "C" int univl_attention_fwd_fused(const UnivlAttention* at, const UnivlGe
     const bool big = Sk_pad > 64;                      // 65 .. 128 positions: two workgroups (query blocks) per (batch row, head)
     a.n_attn = at->B * at->H * (big ? 2 : 1);
     a.n_attn_pad = (a.n_attn + 7) / 8 * 8;
-    const int nb = chunk_count <= 0 ? 0 : ((max_blocks > 0 && max_blocks < chunk_count) ? max_blocks : chunk_count);
-    UnivlAdam none = {};
-    const UnivlAdam& ad = chunk_count > 0 ? *adam : none;
+    const AdamRange r = adam_range(adam, chunk_begin, chunk_count, max_blocks);
     attn_fwd_fused_allow_lds();
-    const int cb = chunk_begin, ce = chunk_begin + (chunk_count > 0 ? chunk_count : 0);
-    const dim3 grid(a.n_attn_pad + nb);
-    if (big) {
-        if (univl_adam_nt()) hipLaunchKernelGGL((attn_fwd_qkv_kernel<true, true>), grid, dim3(512), ATTN_FWD_FUSED_SMEM_BIG, stream, a, ad, cb, ce);
-        else hipLaunchKernelGGL((attn_fwd_qkv_kernel<false, true>), grid, dim3(512), ATTN_FWD_FUSED_SMEM_BIG, stream, a, ad, cb, ce);
-    } else {
-        if (univl_adam_nt()) hipLaunchKernelGGL((attn_fwd_qkv_kernel<true, false>), grid, dim3(512), ATTN_FWD_FUSED_SMEM, stream, a, ad, cb, ce);
-        else hipLaunchKernelGGL((attn_fwd_qkv_kernel<false, false>), grid, dim3(512), ATTN_FWD_FUSED_SMEM, stream, a, ad, cb, ce);
-    }
+    const dim3 grid(a.n_attn_pad + r.blocks);
+    adam_with_nt([&](auto nt) {
+        constexpr bool NT = decltype(nt)::value;
+        if (big) hipLaunchKernelGGL((attn_fwd_qkv_kernel<NT, true>), grid, dim3(512), ATTN_FWD_FUSED_SMEM_BIG, stream, a, r.adam, r.c0, r.c1);
+        else hipLaunchKernelGGL((attn_fwd_qkv_kernel<NT, false>), grid, dim3(512), ATTN_FWD_FUSED_SMEM, stream, a, r.adam, r.c0, r.c1);
+    });
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
@@ -1836,15 +1828,12 @@ extern "C" int univl_gemm_rider_fits(const UnivlGemm* gemm) {
 extern "C" int univl_gemm_rider(const UnivlGemm* gemm, const UnivlAdam* adam, int32_t chunk_begin, int32_t chunk_count,
                                 int32_t max_blocks, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(gemm != nullptr && adam != nullptr, UNIVL_EINVAL, "univl_gemm_rider: null descriptor");
-    UNIVL_CHECK_ARG(adam->p && adam->g && adam->m && adam->v && adam->segs && adam->chunk_seg && adam->chunk_off && adam->chunk_len &&
-                        adam->seg_scalars && adam->nchunk > 0 && chunk_begin >= 0 && chunk_count >= 0 &&
-                        chunk_begin + chunk_count <= adam->nchunk,
-                    UNIVL_EINVAL, "univl_gemm_rider: chunks [%d, +%d) of %d", chunk_begin, chunk_count, adam ? adam->nchunk : 0);
-    UNIVL_CHECK_ARG(adam_bases_aligned(adam), UNIVL_EINVAL, "univl_gemm_rider: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
+    UNIVL_CHECK_ARG(gemm != nullptr, UNIVL_EINVAL, "univl_gemm_rider: null descriptor");
+    int rc = adam_range_check("univl_gemm_rider", adam, chunk_begin, chunk_count, false);
+    if (rc != UNIVL_OK) return rc;
     GemmArgs a;
     int ks, fits;
-    int rc = rider_prepare(gemm, a, ks, fits);
+    rc = rider_prepare(gemm, a, ks, fits);
     if (rc != UNIVL_OK) return rc;
     if (fits == 2 && adam->p16_lo != nullptr) fits = 0;      // the 64 x 128 rider kernel does not keep the lo half of the shadow pair (adam_chunk<.., LO = false>)
     if (!fits || chunk_count == 0) {          // not a product these kernels carry: the two launches one after the other (same result)
@@ -1854,28 +1843,31 @@ extern "C" int univl_gemm_rider(const UnivlGemm* gemm, const UnivlAdam* adam, in
     }
     const int nx = (gemm->N + (fits == 2 ? 127 : 63)) / (fits == 2 ? 128 : 64), ny = (gemm->M + 63) / 64;
     const int nd = nx * ny * ks, nd_pad = (nd + 7) / 8 * 8;
-    const int nb = (max_blocks > 0 && max_blocks < chunk_count) ? max_blocks : chunk_count;
-    const bool nt = univl_adam_nt();              // optim.hip: the one switch of the update's cache policy (UNIVL_ADAM_NT)
+    const AdamRange r = adam_range(adam, chunk_begin, chunk_count, max_blocks);
     if (fits == 2) {                              // the 64 x 128 tile: 48 KB of LDS, no opt-in
         constexpr size_t smem = 2 * (size_t)(64 + 128) * 64 * sizeof(__bf16);
-        const int nb8 = (nb + 7) / 8 * 8;         // whole groups of 8 (the kernel's interleaving); surplus workgroups find no chunk
-        if (nt) hipLaunchKernelGGL(gemm_adam_rect_kernel<true>, dim3(nd_pad + nb8), dim3(512), smem, stream, a, nd, nd_pad, nx, ny, ks, *adam,
-                                   chunk_begin, chunk_begin + chunk_count);
-        else hipLaunchKernelGGL(gemm_adam_rect_kernel<false>, dim3(nd_pad + nb8), dim3(512), smem, stream, a, nd, nd_pad, nx, ny, ks, *adam,
-                                chunk_begin, chunk_begin + chunk_count);
+        const int nb8 = (r.blocks + 7) / 8 * 8;   // whole groups of 8 (the kernel's interleaving); surplus workgroups find no chunk
+        adam_with_nt([&](auto nt) {
+            hipLaunchKernelGGL(gemm_adam_rect_kernel<decltype(nt)::value>, dim3(nd_pad + nb8), dim3(512), smem, stream, a, nd, nd_pad, nx, ny,
+                               ks, r.adam, r.c0, r.c1);
+        });
         UNIVL_LAUNCH_CHECK();
         return UNIVL_OK;
     }
     rider_allow_lds();
-    if (nt) {
-        hipLaunchKernelGGL(gemm_adam_kernel<true>, dim3(nd_pad + nb), dim3(512), RIDER_SMEM, stream, a, nd, nd_pad, nx, ny, ks, *adam,
-                           chunk_begin, chunk_begin + chunk_count);
-    } else {
-        hipLaunchKernelGGL(gemm_adam_kernel<false>, dim3(nd_pad + nb), dim3(512), RIDER_SMEM, stream, a, nd, nd_pad, nx, ny, ks, *adam,
-                           chunk_begin, chunk_begin + chunk_count);
-    }
+    adam_with_nt([&](auto nt) {
+        hipLaunchKernelGGL(gemm_adam_kernel<decltype(nt)::value>, dim3(nd_pad + r.blocks), dim3(512), RIDER_SMEM, stream, a, nd, nd_pad, nx, ny,
+                           ks, r.adam, r.c0, r.c1);
+    });
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
+}
+
+// (Stays behind univl_gemm_rider: its two lines are the first use of gemm_ln_kernel<NT>, and the device code is emitted in that order.)
+static void gemm_ln_allow_lds() {
+    static bool done_nt[UNIVL_MAX_DEVICES] = {}, done_t[UNIVL_MAX_DEVICES] = {};
+    univl_allow_lds(gemm_ln_kernel<true>, RIDER_SMEM, done_nt);
+    univl_allow_lds(gemm_ln_kernel<false>, RIDER_SMEM, done_t);
 }
 
 // The same launch with the LayerNorm that consumes the product's fp32 output folded in (gemm_ln_kernel); adam may be null (no chunks).
@@ -1886,15 +1878,12 @@ extern "C" int univl_gemm_ln(const UnivlGemm* gemm, const UnivlLayerNorm* ln, in
                              int32_t chunk_begin, int32_t chunk_count, int32_t max_blocks, int32_t dry_run, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     UNIVL_CHECK_ARG(gemm != nullptr && ln != nullptr && counters != nullptr, UNIVL_EINVAL, "univl_gemm_ln: null argument");
-    UNIVL_CHECK_ARG(chunk_count == 0 || (adam != nullptr && adam->p && adam->g && adam->m && adam->v && adam->segs && adam->chunk_seg &&
-                                         adam->chunk_off && adam->chunk_len && adam->seg_scalars && chunk_begin >= 0 && chunk_count > 0 &&
-                                         chunk_begin + chunk_count <= adam->nchunk),
-                    UNIVL_EINVAL, "univl_gemm_ln: chunks [%d, +%d)", chunk_begin, chunk_count);
-    UNIVL_CHECK_ARG(chunk_count == 0 || adam_bases_aligned(adam), UNIVL_EINVAL, "univl_gemm_ln: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
+    int rc = adam_range_check("univl_gemm_ln", adam, chunk_begin, chunk_count, true);
+    if (rc != UNIVL_OK) return rc;
     GemmArgs a;
     int ks;
     Choice c;
-    const int rc = prepare(gemm, a, ks, c);
+    rc = prepare(gemm, a, ks, c);
     if (rc != UNIVL_OK) return rc;
     const int nx = (gemm->N + 63) / 64, ny = (gemm->M + 63) / 64;
     UNIVL_CHECK_ARG(!univl_deterministic() && gemm->dtype == UNIVL_BF16 && !gemm->trans_a && !gemm->trans_b && c.tile == 64 && c.nc == 4 &&
@@ -1906,22 +1895,15 @@ extern "C" int univl_gemm_ln(const UnivlGemm* gemm, const UnivlLayerNorm* ln, in
     if (dry_run) return UNIVL_OK;
     a.flags |= UNIVL_GEMM_ATOMIC;            // every contribution an fp32 atomic into the pre-zeroed output, also when the product is not split
     const int nd = nx * ny * ks, nd_pad = (nd + 7) / 8 * 8;
-    const int nb = chunk_count <= 0 ? 0 : ((max_blocks > 0 && max_blocks < chunk_count) ? max_blocks : chunk_count);
-    UnivlAdam none = {};
-    const UnivlAdam& ad = chunk_count > 0 ? *adam : none;
+    const AdamRange r = adam_range(adam, chunk_begin, chunk_count, max_blocks);
     LnFold f;
     f.ln = *ln;
     f.counters = counters;
-    static bool done_nt[UNIVL_MAX_DEVICES] = {}, done_t[UNIVL_MAX_DEVICES] = {};
-    univl_allow_lds(gemm_ln_kernel<true>, RIDER_SMEM, done_nt);
-    univl_allow_lds(gemm_ln_kernel<false>, RIDER_SMEM, done_t);
-    if (univl_adam_nt()) {
-        hipLaunchKernelGGL(gemm_ln_kernel<true>, dim3(nd_pad + nb), dim3(512), RIDER_SMEM, stream, a, nd, nd_pad, nx, ny, ks, ad,
-                           chunk_begin, chunk_begin + (chunk_count > 0 ? chunk_count : 0), f);
-    } else {
-        hipLaunchKernelGGL(gemm_ln_kernel<false>, dim3(nd_pad + nb), dim3(512), RIDER_SMEM, stream, a, nd, nd_pad, nx, ny, ks, ad,
-                           chunk_begin, chunk_begin + (chunk_count > 0 ? chunk_count : 0), f);
-    }
+    gemm_ln_allow_lds();
+    adam_with_nt([&](auto nt) {
+        hipLaunchKernelGGL(gemm_ln_kernel<decltype(nt)::value>, dim3(nd_pad + r.blocks), dim3(512), RIDER_SMEM, stream, a, nd, nd_pad, nx, ny,
+                           ks, r.adam, r.c0, r.c1, f);
+    });
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
@@ -1932,9 +1914,7 @@ extern "C" int univl_gemm_rider_prime(hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     rider_allow_lds();
     attn_fwd_fused_allow_lds();
-    static bool done_nt[UNIVL_MAX_DEVICES] = {}, done_t[UNIVL_MAX_DEVICES] = {};
-    univl_allow_lds(gemm_ln_kernel<true>, RIDER_SMEM, done_nt);
-    univl_allow_lds(gemm_ln_kernel<false>, RIDER_SMEM, done_t);
+    gemm_ln_allow_lds();
     return UNIVL_OK;
 }
 

@@ -337,13 +337,12 @@ extern "C" int univl_scale_grads(float* g, const UnivlSeg* segs, const int32_t* 
 
 extern "C" int univl_bert_adam(const UnivlAdam* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d && d->p && d->g && d->m && d->v && d->segs && d->chunk_seg && d->chunk_off && d->chunk_len &&
-                        d->sumsq && d->step && d->seg_scalars && d->nseg > 0 && d->nchunk > 0,
-                    UNIVL_EINVAL, "univl_bert_adam: bad argument");
+    UNIVL_CHECK_ARG(d && adam_tables_present(d) && d->sumsq && d->step && d->nseg > 0, UNIVL_EINVAL, "univl_bert_adam: bad argument");
     UNIVL_CHECK_ARG(adam_bases_aligned(d), UNIVL_EINVAL, "univl_bert_adam: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
     hipLaunchKernelGGL(adam_prep_kernel, dim3((d->nseg + 255) / 256), dim3(256), 0, stream, *d);
-    if (univl_adam_nt()) hipLaunchKernelGGL(adam_apply_kernel<true>, dim3(d->nchunk), dim3(256), 0, stream, *d, 0, d->nchunk);
-    else hipLaunchKernelGGL(adam_apply_kernel<false>, dim3(d->nchunk), dim3(256), 0, stream, *d, 0, d->nchunk);
+    adam_with_nt([&](auto nt) {
+        hipLaunchKernelGGL(adam_apply_kernel<decltype(nt)::value>, dim3(d->nchunk), dim3(256), 0, stream, *d, 0, d->nchunk);
+    });
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
@@ -351,18 +350,13 @@ extern "C" int univl_bert_adam(const UnivlAdam* d, hipStream_t stream) {
 extern "C" int univl_bert_adam_range(const UnivlAdam* d, int32_t chunk_begin, int32_t chunk_count, int32_t do_prep,
                                      int32_t max_blocks, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d && d->p && d->g && d->m && d->v && d->segs && d->chunk_seg && d->chunk_off && d->chunk_len &&
-                        d->sumsq && d->step && d->seg_scalars && d->nseg > 0 && d->nchunk > 0,
-                    UNIVL_EINVAL, "univl_bert_adam_range: bad argument");
-    UNIVL_CHECK_ARG(adam_bases_aligned(d), UNIVL_EINVAL, "univl_bert_adam_range: p / g / m / v must be 16-byte aligned, p16 / p16_lo 8-byte aligned");
-    UNIVL_CHECK_ARG(chunk_begin >= 0 && chunk_count >= 0 && chunk_begin + chunk_count <= d->nchunk, UNIVL_EINVAL,
-                    "univl_bert_adam_range: chunks [%d, +%d) of %d", chunk_begin, chunk_count, d->nchunk);
+    UNIVL_CHECK_ARG(d && adam_tables_present(d) && d->sumsq && d->step && d->nseg > 0, UNIVL_EINVAL, "univl_bert_adam_range: bad argument");
+    if (const int rc = adam_range_check("univl_bert_adam_range", d, chunk_begin, chunk_count, false)) return rc;
     if (do_prep) hipLaunchKernelGGL(adam_prep_kernel, dim3((d->nseg + 255) / 256), dim3(256), 0, stream, *d);
-    if (chunk_count > 0) {
-        const int grid = (max_blocks > 0 && max_blocks < chunk_count) ? max_blocks : chunk_count;
-        if (univl_adam_nt()) hipLaunchKernelGGL(adam_apply_kernel<true>, dim3(grid), dim3(256), 0, stream, *d, chunk_begin, chunk_begin + chunk_count);
-        else hipLaunchKernelGGL(adam_apply_kernel<false>, dim3(grid), dim3(256), 0, stream, *d, chunk_begin, chunk_begin + chunk_count);
-    }
+    const AdamRange r = adam_range(d, chunk_begin, chunk_count, max_blocks);
+    if (r.blocks > 0) adam_with_nt([&](auto nt) {
+        hipLaunchKernelGGL(adam_apply_kernel<decltype(nt)::value>, dim3(r.blocks), dim3(256), 0, stream, r.adam, r.c0, r.c1);
+    });
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

@@ -308,6 +308,168 @@ class GradState:
         plan.add_callable(lambda: ops.sumsq_finish(self.flat.partials, seg, start, count, out))
 
 
+class Riders:
+    """The prepared BertAdam update that rides in ONE run of a plan (Plan.riders): its descriptor, the chunk range (first, count) of
+    every key the run carries, and which (key, slot) launches have taken their part so far."""
+    __slots__ = ("desc", "ref", "ranges", "max_blocks", "used")
+
+    def __init__(self, desc, ranges, max_blocks=0):
+        self.desc, self.ref, self.ranges, self.max_blocks, self.used = desc, C.byref(desc), dict(ranges), int(max_blocks), set()
+
+    def take(self, key, slot, nslots):
+        """(first, count) of the chunks the launch that is slot `slot` of `nslots` for `key` carries now, or None: nothing rides under
+        that key, or the slot has gone out -- a stack that runs twice in one forward (pretrain: clean and masked pass) carries once."""
+        rng = self.ranges.get(key)
+        if rng is None or (key, slot) in self.used:
+            return None
+        self.used.add((key, slot))
+        lo = rng[0] + rng[1] * slot // nslots
+        return lo, rng[0] + rng[1] * (slot + 1) // nslots - lo
+
+    def signature(self):
+        """What a capture of the carrying plan bakes in (UniVL._run_plan replays a graph only under the signature it was captured with)."""
+        return bytes(self.desc), tuple(sorted(self.ranges.items())), self.max_blocks
+
+    def pending(self):
+        """[(key, first, count, partly)] of every range of this run: partly False, nothing of it has gone out; True, some slot has -- the
+        slots are fractions only the plan knows, so which chunks did cannot be told from here (UniVL._unadopt_pending_update)."""
+        sent = {key for key, _ in self.used}
+        return [(key, c0, n, key in sent) for key, (c0, n) in self.ranges.items()]
+
+
+class Op:
+    """One entry of Plan.ops.  Every op has kind, name (the entry point's name) and stream; launch forms (the subclasses below) have fn
+    and descs (their GEMM-family descriptors: Plan.descs[i] is the same list), and key / slot / nslots where they can carry optimizer
+    chunks (key None: they carry none); "eager" / "pys" / "py" have fn, "record" / "wait" key, "dep" src and dst.  `was`: what stood at
+    position 2 of the five-tuple an op used to be, kept for __getitem__ alone."""
+    __slots__ = ("kind", "name", "stream", "fn", "descs", "key", "slot", "nslots", "src", "dst", "was")
+
+    def __init__(self, kind, name, stream=0, fn=None, key=None, src=None, dst=None):
+        self.kind, self.name, self.stream, self.fn, self.key, self.src, self.dst = kind, name, stream, fn, key, src, dst
+        self.descs = self.slot = self.nslots = self.was = None
+
+    def __getitem__(self, i):
+        """op[0] .. op[4] of the former tuple, (kind, fn | key | src, payload | dst, name, stream): the tests of earlier commits read plans
+        that way and must keep passing against this one.  Nothing in the package does; new readers use the fields."""
+        a, b = (self.src, self.dst) if self.kind == "dep" else (self.key if self.fn is None else self.fn, self.was)
+        return (self.kind, a, b, self.name, self.stream)[i]
+
+
+class Launch(Op):
+    """A launch form: how it is enqueued on a stream handle (enqueue -> rc; `riders`: Plan.riders of this run) and how Plan.launches
+    replays it (replay -> (launch(handle) -> rc, descriptors)).  This one: an entry point called as fn(*args, handle), replayed as it ran."""
+    __slots__ = ("args",)
+
+    def __init__(self, kind, name, stream, descs, args, key=None, slot=0, nslots=1, entry=None):
+        Op.__init__(self, kind, name, stream, getattr(_lib.lib(), entry or name), key)
+        self.descs, self.args, self.slot, self.nslots = descs, args, int(slot), int(nslots)
+
+    def enqueue(self, h, riders=None):
+        return self.fn(*self.args, h)
+
+    def counts_as(self, prefix):  # ("call2": univl_pool_pair_fwd / _bwd, in no replayed family)
+        return self.kind != "call2" and self.name.startswith(prefix)
+
+    def replay(self, carried):
+        return self.enqueue, self.descs
+
+
+class _Carrier(Launch):
+    """A launch that does other work beside its dense contractions (optimizer chunks, a LayerNorm, the attention around a projection):
+    replayed as the contractions alone.  `gemms`: where among args their descriptors sit."""
+    __slots__ = ()
+    gemms = slice(0, 1)
+
+    def part(self, riders):
+        """(first, count) of the optimizer chunks this launch carries in this run, or None."""
+        return None if riders is None or self.key is None else riders.take(self.key, self.slot, self.nslots)
+
+    def dense(self, h):
+        """The dense contraction alone: what the launch falls back to without the work it carries, and what it is replayed as."""
+        g = [a for a in self.args[self.gemms] if a is not None]
+        return _lib.lib().univl_gemm(g[0], h) if len(g) == 1 else _lib.lib().univl_gemm_pair(g[0], g[1], 0, h)
+
+    def replay(self, carried):    # (optimizer chunks never replay: they would change the parameters)
+        return self.dense, self.descs
+
+
+class _Rider(_Carrier):           # args: (product,)
+    __slots__ = ()
+
+    def enqueue(self, h, riders=None):
+        part = self.part(riders)
+        if part is None:
+            return self.dense(h)
+        return self.fn(self.args[0], riders.ref, part[0], part[1], riders.max_blocks, h)
+
+
+class _LnFold(_Carrier):
+    """... that finishes the LayerNorm `ln` behind its product: folded(h) is the launch with it and without chunks."""
+    __slots__ = ("ln",)
+
+    def replay(self, carried):    # carried: with its LayerNorm, whose descriptor then ends the list
+        return (self.folded, self.descs + [self.ln]) if carried else (self.dense, self.descs)
+
+
+class _GemmLn(_LnFold):           # args: (product, LayerNorm, counters)
+    __slots__ = ()
+
+    def folded(self, h, ad=(None, 0, 0, 0)):
+        return self.fn(*self.args, *ad, 0, h)
+
+    def enqueue(self, h, riders=None):
+        part = self.part(riders)
+        if part is None:
+            rc = self.folded(h)
+            if rc == _lib.EUNSUPPORTED:      # deterministic mode (or a shape the fold does not carry): the two launches
+                rc = self.dense(h) or _lib.lib().univl_layernorm_fwd(self.args[1], h)
+        else:
+            ad = (riders.ref, part[0], part[1], riders.max_blocks)
+            rc = self.folded(h, ad)
+            if rc == _lib.EUNSUPPORTED:
+                rc = _lib.lib().univl_gemm_rider(self.args[0], *ad, h) or _lib.lib().univl_layernorm_fwd(self.args[1], h)
+        return rc
+
+
+class _PairLn(_LnFold):           # args: (dgrad, wgrad, LayerNorm, counters, 0)
+    __slots__ = ()
+    gemms = slice(0, 2)
+
+    def folded(self, h):
+        return self.fn(*self.args, h)
+
+    def enqueue(self, h, riders=None):
+        rc = self.folded(h)
+        if rc == _lib.EUNSUPPORTED:
+            rc = self.dense(h) or _lib.lib().univl_layernorm_bwd(self.args[2], h)
+        return rc
+
+
+class _FusedAttn(_Carrier):
+    """... the fused attention launches: the dense contractions inside them belong to the GEMM family, and to no other, and are replayed
+    the way they ran before the fused launches existed (the family's accounting)."""
+    __slots__ = ()
+
+    def counts_as(self, prefix):
+        return prefix == "univl_gemm"
+
+
+class _AttnFwdFused(_FusedAttn):  # args: (attention, q | k | v projection)
+    __slots__ = ("attn",)
+    gemms = slice(1, 2)
+
+    def enqueue(self, h, riders=None):
+        part = self.part(riders)
+        if part is None:
+            return self.fn(*self.args, None, 0, 0, 0, 0, h)
+        return self.fn(*self.args, riders.ref, part[0], part[1], riders.max_blocks, 0, h)
+
+
+class _AttnBwdFused(_FusedAttn):  # args: (attention, attention-output dgrad, its weight gradient or None, 0)
+    __slots__ = ()
+    gemms = slice(1, 3)
+
+
 class Plan:
     """A static list of kernel enqueues over a small set of HIP streams.
 
@@ -318,50 +480,48 @@ class Plan:
     the video encoder) run concurrently on the 256 CUs instead of queueing behind the critical path."""
 
     def __init__(self):
-        self.ops = []
+        self.ops = []                # Op records, in enqueue order
         self.keep = []
         self.descs = {}              # op index -> the C descriptors of that launch (measurement / introspection)
         self.external = {}           # key -> event recorded by somebody else (see wait_point)
         self._side = {}
         self._segments = None
         self.rider_keys = set()      # chunk-group keys this plan can carry beside its forward products (add_gemm_rider)
-        self.riders = None           # set for the duration of one run: dict(desc=UnivlAdam, ranges={key: (first, count)}, max_blocks=int)
+        self.riders = None           # set for the duration of one run: the Riders that run carries (None: nothing rides)
+
+    def _launch(self, op, keep, was):
+        self.keep += keep
+        op.was = was
+        self.descs[len(self.ops)] = op.descs
+        if op.key is not None:
+            self.rider_keys.add(op.key)
+        self.ops.append(op)
+        return op
 
     def add_gemm_rider(self, desc, key, slot, nslots, stream=0):
         """A forward product that, while self.riders names a chunk range for `key`, also carries
         the slot-th of nslots parts of that range of a prepared BertAdam update (univl_gemm_rider); otherwise a plain univl_gemm."""
-        self.keep.append(desc)
-        self.descs[len(self.ops)] = [desc]
-        self.rider_keys.add(key)
-        self.ops.append(("rider", _lib.lib().univl_gemm_rider, (desc, key, int(slot), int(nslots)), "univl_gemm_rider", stream))
+        self._launch(_Rider("rider", "univl_gemm_rider", stream, [desc], (C.byref(desc),), key, slot, nslots), [desc], (desc, key, int(slot), int(nslots)))
 
     def add_gemm_ln(self, desc, ln_desc, counters, key=None, slot=0, nslots=1, stream=0):
         """A forward product AND the LayerNorm that consumes its fp32 output in one launch (univl_gemm_ln: the last workgroups to
         contribute to a 64-row block normalise it); with `key` it also carries optimizer chunks like add_gemm_rider.  `counters`: the
         call site's int32 arrival counters (zeroed at allocation, left zero by every launch)."""
-        self.keep += [desc, ln_desc, counters]
-        self.descs[len(self.ops)] = [desc]
-        if key is not None:
-            self.rider_keys.add(key)
-        self.ops.append(("gemm_ln", _lib.lib().univl_gemm_ln, (desc, ln_desc, counters, key, int(slot), int(nslots)), "univl_gemm_ln", stream))
+        args = (C.byref(desc), C.byref(ln_desc), C.c_void_p(counters.data_ptr()))
+        was = (desc, ln_desc, counters, key, int(slot), int(nslots))
+        self._launch(_GemmLn("gemm_ln", "univl_gemm_ln", stream, [desc], args, key, slot, nslots), was[:3], was).ln = ln_desc
 
     def add(self, fn_name, desc, stream=0):
-        fn = getattr(_lib.lib(), fn_name)
-        self.keep.append(desc)
-        self.descs[len(self.ops)] = [desc]
-        self.ops.append(("call", fn, C.byref(desc), fn_name, stream))
+        ref = C.byref(desc)
+        self._launch(Launch("call", fn_name, stream, [desc], (ref,)), [desc], ref)
 
     def add_pair_call(self, fn_name, da, db, stream=0):
         """An entry point that takes two descriptors (univl_pool_pair_fwd / _bwd)."""
-        fn = getattr(_lib.lib(), fn_name)
-        self.keep += [da, db]
-        self.descs[len(self.ops)] = [da, db]
-        self.ops.append(("call2", fn, (da, db), fn_name, stream))
+        self._launch(Launch("call2", fn_name, stream, [da, db], (C.byref(da), C.byref(db))), [da, db], (da, db))
 
     def add_gemm_group(self, descs, stream=0, max_blocks=0):
         """Independent GEMMs with the same operand layouts as ONE launch (univl_gemm_group), in chunks of GEMM_GROUP_MAX.
         max_blocks > 0: at most that many workgroups (the kernel walks its tiles)."""
-        fn = _lib.lib().univl_gemm_group_limited
         if not _ab.get("group_wgrad"):           # A/B: one launch per member
             for d in descs:
                 self.add("univl_gemm", d, stream)
@@ -369,42 +529,35 @@ class Plan:
         for i in range(0, len(descs), _lib.GEMM_GROUP_MAX):
             chunk = descs[i:i + _lib.GEMM_GROUP_MAX]
             arr = (_lib.Gemm * len(chunk))(*chunk)
-            self.keep.append(arr)
-            self.descs[len(self.ops)] = list(chunk)
-            self.ops.append(("group", fn, (arr, len(chunk), int(max_blocks)), "univl_gemm_group", stream))
+            args = (arr, len(chunk), int(max_blocks))
+            self._launch(Launch("group", "univl_gemm_group", stream, list(chunk), args, entry="univl_gemm_group_limited"), [arr], args)
 
     def add_gemm_pair(self, dgrad, wgrad, stream=0):
         """A dgrad product and the weight-gradient product fed by the same upstream gradient as
         ONE launch (univl_gemm_pair) -- the weight-gradient tiles fill the compute units the latency-bound dgrad leaves idle."""
-        fn = _lib.lib().univl_gemm_pair
         arr = (_lib.Gemm * 2)(dgrad, wgrad)
-        self.keep.append(arr)
-        self.descs[len(self.ops)] = [dgrad, wgrad]
-        self.ops.append(("pair", fn, arr, "univl_gemm_pair", stream))
+        self._launch(Launch("pair", "univl_gemm_pair", stream, [dgrad, wgrad], (C.byref(arr[0]), C.byref(arr[1]), 0)), [arr], arr)
 
     def add_attn_fwd_fused(self, attn, qkv, key=None, slot=0, nslots=1, stream=0):
         """The attention forward with the q | k | v projection computed inside the launch (univl_attention_fwd_fused); with `key` it
         also carries optimizer chunks like add_gemm_rider."""
-        self.keep += [attn, qkv]
-        self.descs[len(self.ops)] = [qkv]
-        if key is not None:
-            self.rider_keys.add(key)
-        self.ops.append(("attn_fwd_fused", _lib.lib().univl_attention_fwd_fused, (attn, qkv, key, int(slot), int(nslots)), "univl_attention_fwd_fused", stream))
+        args = (C.byref(attn), C.byref(qkv))
+        self._launch(_AttnFwdFused("attn_fwd_fused", "univl_attention_fwd_fused", stream, [qkv], args, key, slot, nslots), [attn, qkv],
+                     (attn, qkv, key, int(slot), int(nslots))).attn = attn
 
     def add_attn_bwd_fused(self, attn, odgrad, owgrad, stream=0):
         """The attention backward with the attention-output dgrad that feeds it computed inside the launch, the weight gradient of
         that projection riding as extra workgroups (univl_attention_bwd_fused; owgrad may be None)."""
-        self.keep += [attn, odgrad, owgrad]
-        self.descs[len(self.ops)] = [odgrad] + ([owgrad] if owgrad is not None else [])
-        self.ops.append(("attn_fused", _lib.lib().univl_attention_bwd_fused, (attn, odgrad, owgrad), "univl_attention_bwd_fused", stream))
+        args = (C.byref(attn), C.byref(odgrad), C.byref(owgrad) if owgrad is not None else None, 0)
+        descs = [odgrad] + ([owgrad] if owgrad is not None else [])
+        self._launch(_AttnBwdFused("attn_fused", "univl_attention_bwd_fused", stream, descs, args), [attn, odgrad, owgrad], (attn, odgrad, owgrad))
 
     def add_gemm_pair_ln(self, dgrad, wgrad, ln_desc, counters, stream=0):
         """add_gemm_pair with the LayerNorm BACKWARD that consumes the dgrad's fp32 output finished inside the launch
         (univl_gemm_pair_ln); falls back to the two launches at run time where the library refuses (deterministic mode)."""
         arr = (_lib.Gemm * 2)(dgrad, wgrad)
-        self.keep += [arr, ln_desc, counters]
-        self.descs[len(self.ops)] = [dgrad, wgrad]
-        self.ops.append(("pair_ln", _lib.lib().univl_gemm_pair_ln, (arr, ln_desc, counters), "univl_gemm_pair_ln", stream))
+        args = (C.byref(arr[0]), C.byref(arr[1]), C.byref(ln_desc), C.c_void_p(counters.data_ptr()), 0)
+        self._launch(_PairLn("pair_ln", "univl_gemm_pair_ln", stream, [dgrad, wgrad], args), [arr, ln_desc, counters], (arr, ln_desc, counters)).ln = ln_desc
 
     def add_zeros(self, tensors, stream=0):
         """Clear several buffers with one launch (univl_zero_many)."""
@@ -419,24 +572,24 @@ class Plan:
         has enqueued work on so far (the calling stream first) -- a gradient exchange on a communication stream of its own waits for
         exactly those, without joining them into the main chain."""
         kind = "eager" if eager else ("pys" if with_streams else "py")
-        self.ops.append((kind, f, None, getattr(f, "__name__", "callable"), stream))
+        self.ops.append(Op(kind, getattr(f, "__name__", "callable"), stream, fn=f))
 
     def wait_point(self, key, stream=0):
         """If an event is registered under `key` in self.external when the plan runs, `stream` waits for it; otherwise a
         no-op.  The pipelined training step (univl_amd.graphed) applies the previous step's BertAdam update layer by layer
         on its own stream and registers one event per layer; the forward plan waits for a layer's parameters only where it
         first reads them."""
-        self.ops.append(("wait", key, None, "wait", stream))
+        self.ops.append(Op("wait", "wait", stream, key=key))
 
     def record(self, key, stream=0):
         """Mark the work enqueued on `stream` so far; a later wait_point(key, other_stream) waits for exactly that much
         (fork / join always wait for everything enqueued on the source up to the moment of the wait)."""
-        self.ops.append(("record", key, None, "record", stream))
+        self.ops.append(Op("record", "record", stream, key=key))
 
     def fork(self, src, dst):
         """dst waits for all work enqueued on src so far."""
         if src != dst:
-            self.ops.append(("dep", src, dst, "dep", 0))
+            self.ops.append(Op("dep", "dep", 0, src=src, dst=dst))
 
     def join(self, src, dst):
         self.fork(src, dst)
@@ -451,141 +604,46 @@ class Plan:
         return st
 
     def _run_ops(self, ops_, cur, forked=None):
-        handles, events = {}, {}
+        handles, events, riders = {}, {}, self.riders
         forked = set() if forked is None else set(forked)       # side-stream indices ordered behind `cur` in this run
         for op in ops_:
-            kind, a, b, name, sidx = op
-            if kind == "call":
+            kind, sidx = op.kind, op.stream
+            if op.descs is not None:                            # a launch form
                 h = handles.get(sidx)
                 if h is None:
                     h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                rc = a(b, h)
+                rc = op.enqueue(h, riders)
                 if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "call2":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                rc = a(C.byref(b[0]), C.byref(b[1]), h)
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "group":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                rc = a(b[0], b[1], b[2], h)
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "rider":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                desc, key, slot, nslots = b
-                rd = self.riders
-                rng = rd["ranges"].get(key) if rd else None
-                if rng is not None and (key, slot) in rd["used"]:
-                    rng = None               # a stack that runs twice in one forward (pretrain: clean and masked pass) carries once
-                if rng is None:
-                    rc = _lib.lib().univl_gemm(C.byref(desc), h)
-                else:
-                    rd["used"].add((key, slot))
-                    lo, hi = rng[0] + rng[1] * slot // nslots, rng[0] + rng[1] * (slot + 1) // nslots
-                    rc = a(C.byref(desc), C.byref(rd["desc"]), lo, hi - lo, int(rd.get("max_blocks", 0)), h)
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "gemm_ln":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                desc, lnd, ctr, key, slot, nslots = b
-                rd = self.riders
-                rng = rd["ranges"].get(key) if (rd and key is not None) else None
-                if rng is not None and (key, slot) in rd["used"]:
-                    rng = None
-                L_ = _lib.lib()
-                if rng is None:
-                    rc = a(C.byref(desc), C.byref(lnd), C.c_void_p(ctr.data_ptr()), None, 0, 0, 0, 0, h)
-                    if rc == _lib.EUNSUPPORTED:          # deterministic mode (or a shape the fold does not carry): the two launches
-                        rc = L_.univl_gemm(C.byref(desc), h) or L_.univl_layernorm_fwd(C.byref(lnd), h)
-                else:
-                    rd["used"].add((key, slot))
-                    lo, hi = rng[0] + rng[1] * slot // nslots, rng[0] + rng[1] * (slot + 1) // nslots
-                    rc = a(C.byref(desc), C.byref(lnd), C.c_void_p(ctr.data_ptr()), C.byref(rd["desc"]), lo, hi - lo, int(rd.get("max_blocks", 0)), 0, h)
-                    if rc == _lib.EUNSUPPORTED:
-                        rc = (L_.univl_gemm_rider(C.byref(desc), C.byref(rd["desc"]), lo, hi - lo, int(rd.get("max_blocks", 0)), h)
-                              or L_.univl_layernorm_fwd(C.byref(lnd), h))
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "pair_ln":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                arr, lnd, ctr = b
-                rc = a(C.byref(arr[0]), C.byref(arr[1]), C.byref(lnd), C.c_void_p(ctr.data_ptr()), 0, h)
-                if rc == _lib.EUNSUPPORTED:
-                    rc = _lib.lib().univl_gemm_pair(C.byref(arr[0]), C.byref(arr[1]), 0, h) or _lib.lib().univl_layernorm_bwd(C.byref(lnd), h)
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "pair":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                rc = a(C.byref(b[0]), C.byref(b[1]), 0, h)
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "attn_fwd_fused":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                at, qd, key, slot, nslots = b
-                rd = self.riders
-                rng = rd["ranges"].get(key) if (rd and key is not None) else None
-                if rng is not None and (key, slot) in rd["used"]:
-                    rng = None
-                if rng is None:
-                    rc = a(C.byref(at), C.byref(qd), None, 0, 0, 0, 0, h)
-                else:
-                    rd["used"].add((key, slot))
-                    lo, hi = rng[0] + rng[1] * slot // nslots, rng[0] + rng[1] * (slot + 1) // nslots
-                    rc = a(C.byref(at), C.byref(qd), C.byref(rd["desc"]), lo, hi - lo, int(rd.get("max_blocks", 0)), 0, h)
-                if rc != 0:
-                    _lib.check(rc, name)
-            elif kind == "attn_fused":
-                h = handles.get(sidx)
-                if h is None:
-                    h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
-                rc = a(C.byref(b[0]), C.byref(b[1]), C.byref(b[2]) if b[2] is not None else None, 0, h)
-                if rc != 0:
-                    _lib.check(rc, name)
+                    _lib.check(rc, op.name)
             elif kind == "record":
                 ev = torch.cuda.Event()
                 ev.record(self._stream(sidx, cur))
-                events[a] = ev
+                events[op.key] = ev
             elif kind == "wait":
-                ev = events.get(a)
+                ev = events.get(op.key)
                 if ev is None and self.external:
-                    ev = self.external.get(a)
+                    ev = self.external.get(op.key)
                 if ev is not None:
                     self._stream(sidx, cur).wait_event(ev)
             elif kind == "eager":
                 for sd in self._side.values():             # host-driven exchange point: everything planned so far
                     if sd.device == cur.device:
                         cur.wait_stream(sd)
-                a()
+                op.fn()
             elif kind == "pys":
                 # only the side streams THIS run has forked so far (the last "dep" into a stream orders it behind the calling
                 # stream; under capture a stream that has not joined the capture yet must not be waited for)
-                a([cur] + [self._stream(i, cur) for i in sorted(forked)])
+                op.fn([cur] + [self._stream(i, cur) for i in sorted(forked)])
             elif kind == "py":
                 if sidx == 0:
-                    a()
+                    op.fn()
                 else:
                     with torch.cuda.stream(self._stream(sidx, cur)):
-                        a()
+                        op.fn()
             else:
-                self._stream(b, cur).wait_stream(self._stream(a, cur))
-                if b != 0:
-                    forked.add(b)
+                self._stream(op.dst, cur).wait_stream(self._stream(op.src, cur))
+                if op.dst != 0:
+                    forked.add(op.dst)
 
     def run(self, upto=None):
         self._run_ops(self.ops if upto is None else self.ops[:upto], torch.cuda.current_stream())
@@ -594,7 +652,7 @@ class Plan:
         """[("graph", ops) | ("eager", op), ...]: maximal runs of capturable ops between eager ops."""
         out, cur = [], []
         for op in self.ops:
-            if op[0] == "eager":
+            if op.kind == "eager":
                 if cur:
                     out.append(("graph", cur))
                     cur = []
@@ -616,13 +674,13 @@ class Plan:
                 if kind == "eager":
                     segs.append(["eager", payload, None])
                 else:
-                    sides = sorted({op[4] for op in payload if op[0] != "dep" and op[4] != 0}
-                                   | {x for op in payload if op[0] == "dep" for x in (op[1], op[2]) if x != 0})
+                    sides = sorted({op.stream for op in payload if op.kind != "dep" and op.stream != 0}
+                                   | {x for op in payload if op.kind == "dep" for x in (op.src, op.dst) if x != 0})
                     segs.append(["graph", payload, None, sides])
             self._segments = segs
         for seg in self._segments:
             if seg[0] == "eager":
-                seg[1][1]()
+                seg[1].fn()
                 continue
             if seg[2] is None:
                 g = torch.cuda.CUDAGraph()
@@ -643,39 +701,9 @@ class Plan:
         order -- bench.py replays one kernel family alone to time it with HIP events.  A product that CARRIES other work in the step
         (optimizer chunks: add_gemm_rider; the LayerNorm behind it: add_gemm_ln / add_gemm_pair_ln) is replayed without it by
         default -- the dense contraction alone, the quantity rounds 1-3 report -- and with its LayerNorm when carried=True (the
-        descriptor list then ends with that LayerNorm descriptor; optimizer chunks never replay: they would change the parameters)."""
-        out = []
-        for i, op in enumerate(self.ops):
-            kind, fn, arg, name, _ = op
-            if kind == "call" and name.startswith(prefix):
-                out.append((lambda h, fn=fn, arg=arg: fn(arg, h), self.descs[i]))
-            elif kind == "group" and name.startswith(prefix):
-                out.append((lambda h, fn=fn, arg=arg: fn(arg[0], arg[1], arg[2], h), self.descs[i]))
-            elif kind == "rider" and name.startswith(prefix):
-                out.append((lambda h, d=arg[0]: _lib.lib().univl_gemm(C.byref(d), h), self.descs[i]))
-            elif kind == "pair" and name.startswith(prefix):
-                out.append((lambda h, fn=fn, arg=arg: fn(C.byref(arg[0]), C.byref(arg[1]), 0, h), self.descs[i]))
-            elif kind == "attn_fwd_fused" and prefix == "univl_gemm":
-                out.append((lambda h, arg=arg: _lib.lib().univl_gemm(C.byref(arg[1]), h), self.descs[i]))
-            elif kind == "attn_fused" and prefix == "univl_gemm":
-                # the dense contractions inside the fused launch, replayed the way they ran before it existed (the family's accounting)
-                if arg[2] is not None:
-                    out.append((lambda h, arg=arg: _lib.lib().univl_gemm_pair(C.byref(arg[1]), C.byref(arg[2]), 0, h), self.descs[i]))
-                else:
-                    out.append((lambda h, arg=arg: _lib.lib().univl_gemm(C.byref(arg[1]), h), self.descs[i]))
-            elif kind == "pair_ln" and name.startswith(prefix):
-                if carried:
-                    out.append((lambda h, fn=fn, arg=arg: fn(C.byref(arg[0][0]), C.byref(arg[0][1]), C.byref(arg[1]), C.c_void_p(arg[2].data_ptr()), 0, h),
-                                self.descs[i] + [arg[1]]))
-                else:
-                    out.append((lambda h, arg=arg: _lib.lib().univl_gemm_pair(C.byref(arg[0][0]), C.byref(arg[0][1]), 0, h), self.descs[i]))
-            elif kind == "gemm_ln" and name.startswith(prefix):
-                if carried:
-                    out.append((lambda h, fn=fn, arg=arg: fn(C.byref(arg[0]), C.byref(arg[1]), C.c_void_p(arg[2].data_ptr()), None, 0, 0, 0, 0, h),
-                                self.descs[i] + [arg[1]]))
-                else:
-                    out.append((lambda h, d=arg[0]: _lib.lib().univl_gemm(C.byref(d), h), self.descs[i]))
-        return out
+        descriptor list then ends with that LayerNorm descriptor; optimizer chunks never replay: they would change the parameters).
+        The fused attention launches count under "univl_gemm" only, as the dense contractions inside them."""
+        return [op.replay(carried) for op in self.ops if op.descs is not None and op.counts_as(prefix)]
 
     @property
     def calls(self):

@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from . import _ab, _lib, ops
-from .engine import FlatParams, Plan
+from .engine import FlatParams, Plan, Riders
 from .parallel import BucketReducer, broadcast_parameters
 
 logger = logging.getLogger(__name__)
@@ -705,8 +705,7 @@ class UniVL(UniVLPreTrainedModel):
             if plan.rider_keys:
                 # a captured plan holds the riding update's descriptor and chunk ranges: replay only while they are the ones captured
                 # (steady state of a training loop: same optimizer tables, same buffers), else capture again
-                rd = plan.riders
-                sig = None if rd is None else (bytes(rd["desc"]), tuple(sorted(rd["ranges"].items())), int(rd.get("max_blocks", 0)))
+                sig = None if plan.riders is None else plan.riders.signature()
                 if getattr(plan, "_rider_sig", None) != sig:
                     # captured segments are kept PER signature: under gradient accumulation the forward after step() carries
                     # riders and the following ones do not -- both graphs are captured once and replayed, not re-captured at every
@@ -829,19 +828,16 @@ class UniVL(UniVLPreTrainedModel):
         import ctypes as C
         for st in self._steps.values():
             rd = getattr(getattr(st, "fwd", None), "riders", None)
-            if rd is None or rd.get("desc") is not ru["desc"]:
+            if rd is None or rd.desc is not ru["desc"]:
                 continue
             h = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            done = {}
-            for key, slot in rd["used"]:
-                done.setdefault(key, set()).add(slot)
-            for key, (c0, n) in rd["ranges"].items():
-                if key in done:
+            for key, c0, n, partly in rd.pending():
+                if partly:
                     # a stack whose first products already carried a part: the slots are fractions of the range only the plan knows;
                     # nothing here can tell which chunks went out -- refuse to guess
                     raise RuntimeError("univl_amd.UniVL.forward failed after a part of the riding BertAdam update was enqueued; the "
                                        "parameters hold a partial update (model.auto_ride = False avoids riding updates)")
-                _lib.check(_lib.lib().univl_bert_adam_range(C.byref(rd["desc"]), c0, n, 0, 0, h), "bert_adam_range")
+                _lib.check(_lib.lib().univl_bert_adam_range(rd.ref, c0, n, 0, 0, h), "bert_adam_range")
             st.fwd.riders = None
 
     def _adopt_pending_update(self):
@@ -882,7 +878,7 @@ class UniVL(UniVLPreTrainedModel):
             first = False
         if first:                     # nothing went out as a prologue launch: the per-tensor scalars still have to be prepared
             _lib.check(L.univl_bert_adam_range(C.byref(d), 0, 0, 1, 0, h), "bert_adam_range")
-        st.fwd.riders = dict(desc=d, ranges=ranges, max_blocks=int(ru.get("max_blocks", 0)), used=set())
+        st.fwd.riders = Riders(d, ranges, ru.get("max_blocks", 0))
 
     def get_sequence_visual_output(self, input_ids, token_type_ids, attention_mask, video, video_mask, shaped=False):
         """modeling.py:299-313.  `shaped=True` means the caller already flattened the pair dim AND normalised the video
