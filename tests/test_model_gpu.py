@@ -858,6 +858,116 @@ def test_forward_that_fails_after_adopting_the_pending_update_hands_it_back():
     assert all(torch.equal(p_bad[n], p_ok[n]) for n in p_ok), [n for n in p_ok if not torch.equal(p_bad[n], p_ok[n])][:5]
 
 
+class _Injected(Exception):
+    """Raised by the host between two launches of a forward plan."""
+
+
+def _carriers(plan):
+    """[(op index, key)] of the launches of a forward plan that can carry chunks of the optimizer update, in plan order."""
+    return [(i, op.key) for i, op in enumerate(plan.ops) if op.descs is not None and op.key is not None]
+
+
+def _loop_with_a_forward_that_fails(body, at=3, go_on=True):
+    """The unchanged loop on joint_small.  body None: undisturbed.  Else forward call number `at` (from 0), which has adopted the update
+    of the iteration before it and started it, runs body(model, plan, st) in place of UniVL._run_plan and then fails on the host;
+    go_on: the loop goes on, six whole iterations in all.  -> losses, final parameters, rides, the exception the failed forward raised."""
+    cfg, model, opt, batch = _loop_model()
+    losses, raised = [], None
+    for it in range(6):
+        if body is not None and it == at:
+            assert opt.has_pending and opt._auto_deferred
+
+            def failing(plan, st):
+                assert plan is st.fwd and plan.riders is not None and plan.riders.ranges
+                body(model, plan, st)
+                torch.cuda.synchronize()           # (the failure is the host's: nothing of the cut-off run is left in flight)
+                raise _Injected("between two launches")
+            model._run_plan = failing
+            try:
+                with pytest.raises(Exception) as ei:
+                    call(model, batch)
+            finally:
+                del model._run_plan
+            raised = ei.value
+            st = next(iter(model._steps.values()))
+            assert not opt.has_pending and model._rider_update is None and st.fwd.riders is None
+            if not go_on:
+                break
+        losses.append(_one_iteration(model, opt, batch))
+    final = {n: p.detach().clone() for n, p in model.named_parameters()}
+    return losses, final, model.auto_ride_count, raised
+
+
+@pytest.fixture(scope="module")
+def undisturbed_loop():
+    return _loop_with_a_forward_that_fails(None)
+
+
+def _same_as(run, ok):
+    (l_bad, p_bad, rides_bad, raised), (l_ok, p_ok, rides_ok, _) = run, ok
+    assert isinstance(raised, _Injected)
+    assert rides_bad == rides_ok == 5
+    assert l_bad == l_ok
+    assert all(torch.equal(p_bad[n], p_ok[n]) for n in p_ok), [n for n in p_ok if not torch.equal(p_bad[n], p_ok[n])][:5]
+
+
+@pytest.mark.parametrize("where", ["before_the_first_launch", "on_a_key_boundary"])
+def test_forward_that_fails_after_starting_the_pending_update_completes_it(where, undisturbed_loop):
+    """the forward fails on the host AFTER the update it adopted has begun to go out -- in front of the plan's first launch
+    (every riding range is still to come) or between the last launch that carries the first layer key and whatever follows.  What has
+    not gone out goes out as plain range launches (optimization.PendingUpdate.complete_after_failure), the injected exception
+    propagates, nothing stays pending, and the loop that goes on ends bit-identical to the loop that never saw the failure: every
+    parameter saw the update exactly once."""
+    def body(model, plan, st):
+        keys = _carriers(plan)
+        assert keys
+        k = 0
+        if where == "on_a_key_boundary":
+            k = max(i for i, key in keys if key == keys[0][1]) + 1      # every carrier of the first key has run ...
+            assert {key for i, key in keys if i < k} == {keys[0][1]}     # ... and none of another
+        plan.run(upto=k)
+    _same_as(_loop_with_a_forward_that_fails(body), undisturbed_loop)
+
+
+def test_forward_that_fails_inside_a_carried_key_reports_the_partial_update():
+    """... one carrier into a layer key: which chunks of that key went out only the plan knows.  Nobody guesses -- RuntimeError that
+    names the partial update, caused by the injected exception, and nothing is pending afterwards."""
+    _, _, _, raised = _loop_with_a_forward_that_fails(lambda model, plan, st: plan.run(upto=_carriers(plan)[0][0] + 1), go_on=False)
+    assert isinstance(raised, RuntimeError) and "partial update" in str(raised)
+    assert isinstance(raised.__cause__, _Injected)
+
+
+def test_forward_that_fails_after_the_graph_replay_applies_nothing_twice(undisturbed_loop):
+    """The form the loop runs in from its third iteration on: the plan is REPLAYED as a graph, no launch takes its part from the
+    Riders on the host.  A failure behind the last replay (reading the loss out, an interrupt) finds every range applied by the graph:
+    nothing goes out again, and the loop ends bit-identical to the undisturbed one."""
+    def body(model, plan, st):
+        caps = model.graph_captures
+        assert plan._segments is not None or plan._seg_cache        # the third forward captured this plan with riders
+        type(model)._run_plan(model, plan, st)
+        assert model.graph_captures == caps and plan.riders.graphed is True and not plan.riders.used     # a replay, not a capture
+    _same_as(_loop_with_a_forward_that_fails(body), undisturbed_loop)
+
+
+def test_forward_that_fails_while_its_plan_is_captured_reports_the_partial_update():
+    """The third forward is the first to capture its plan with riders.  A host failure inside that capture (here a raising host op at
+    the plan's end, behind the joins of its side streams): the carrying launches took their parts while capturing, but no kernel of the
+    graph has run -- what the host saw tells nothing, so the forward raises the partial-update RuntimeError instead of counting those
+    layers as applied, and nothing is pending."""
+    def body(model, plan, st):
+        def op():
+            assert torch.cuda.is_current_stream_capturing()
+            raise _Injected("inside the capture")
+        plan.add_callable(op)
+        try:
+            type(model)._run_plan(model, plan, st)
+        finally:
+            plan.ops.pop()
+    _, _, _, raised = _loop_with_a_forward_that_fails(body, at=2, go_on=False)
+    assert isinstance(raised, RuntimeError) and "partial update" in str(raised)
+    assert isinstance(raised.__cause__, _Injected)
+
+
 def test_load_state_dict_and_dirty_marks_with_an_update_pending():
     """with optimizer.step()'s update still pending, (1) model.load_state_dict() must end with exactly the loaded weights in the
     fp32 master AND in the bf16 shadow the next forward reads (the pending update belongs to the old weights: it is applied first and then

@@ -311,10 +311,15 @@ class GradState:
 class Riders:
     """The prepared BertAdam update that rides in ONE run of a plan (Plan.riders): its descriptor, the chunk range (first, count) of
     every key the run carries, and which (key, slot) launches have taken their part so far."""
-    __slots__ = ("desc", "ref", "ranges", "max_blocks", "used")
+    __slots__ = ("desc", "ref", "ranges", "max_blocks", "used", "nslots", "graphed")
 
     def __init__(self, desc, ranges, max_blocks=0):
         self.desc, self.ref, self.ranges, self.max_blocks, self.used = desc, C.byref(desc), dict(ranges), int(max_blocks), set()
+        self.nslots = {}             # key -> over how many launches its range is dealt (known once one of them took its part)
+        # None: the run enqueues its launches directly, `used` tells what has gone out.  Plan.run_graphed: a capture takes parts that no
+        # kernel has applied yet and a replay applies parts nobody takes, so `used` tells nothing -- False while that run is under way
+        # (what has gone out cannot be told), True once its last segment has been replayed (every range has).
+        self.graphed = None
 
     def take(self, key, slot, nslots):
         """(first, count) of the chunks the launch that is slot `slot` of `nslots` for `key` carries now, or None: nothing rides under
@@ -323,6 +328,7 @@ class Riders:
         if rng is None or (key, slot) in self.used:
             return None
         self.used.add((key, slot))
+        self.nslots[key] = nslots
         lo = rng[0] + rng[1] * slot // nslots
         return lo, rng[0] + rng[1] * (slot + 1) // nslots - lo
 
@@ -332,9 +338,17 @@ class Riders:
 
     def pending(self):
         """[(key, first, count, partly)] of every range of this run: partly False, nothing of it has gone out; True, some slot has -- the
-        slots are fractions only the plan knows, so which chunks did cannot be told from here (UniVL._unadopt_pending_update)."""
-        sent = {key for key, _ in self.used}
+        slots are fractions only the plan knows, so which chunks did cannot be told from here -- unless all of them did: whole()
+        (optimization.PendingUpdate.complete_after_failure).  A run through graphs: every key counts as partly sent."""
+        sent = set(self.ranges) if self.graphed is not None else {key for key, _ in self.used}
         return [(key, c0, n, key in sent) for key, (c0, n) in self.ranges.items()]
+
+    def whole(self, key):
+        """Every slot of `key` has gone out: its range is applied."""
+        if self.graphed is not None:
+            return self.graphed
+        n = self.nslots.get(key, 0)
+        return n > 0 and all((key, s) in self.used for s in range(n))
 
 
 class Op:
@@ -485,7 +499,9 @@ class Plan:
         self.descs = {}              # op index -> the C descriptors of that launch (measurement / introspection)
         self.external = {}           # key -> event recorded by somebody else (see wait_point)
         self._side = {}
-        self._segments = None
+        self._segments = None        # captured segments of run_graphed() under the rider signature _rider_sig ...
+        self._rider_sig = None
+        self._seg_cache = {}         # ... and those of other signatures (select_segments)
         self.rider_keys = set()      # chunk-group keys this plan can carry beside its forward products (add_gemm_rider)
         self.riders = None           # set for the duration of one run: the Riders that run carries (None: nothing rides)
 
@@ -614,6 +630,8 @@ class Plan:
                     h = handles[sidx] = C.c_void_p(self._stream(sidx, cur).cuda_stream)
                 rc = op.enqueue(h, riders)
                 if rc != 0:
+                    if riders is not None and op.key is not None:
+                        riders.nslots[op.key] = 0           # whether a part this launch took went out cannot be told: never whole()
                     _lib.check(rc, op.name)
             elif kind == "record":
                 ev = torch.cuda.Event()
@@ -663,6 +681,21 @@ class Plan:
             out.append(("graph", cur))
         return out
 
+    def select_segments(self, sig, keep):
+        """Make the captured segments of rider signature `sig` (Riders.signature(), None: nothing rides) the ones run_graphed() replays;
+        True: there are none, run_graphed() is going to capture.  A capture bakes in the riding update's descriptor and chunk ranges, so
+        segments are kept PER signature: under gradient accumulation the forward after step() carries riders and the following ones do
+        not -- both are captured once and replayed, not re-captured at every transition.  At most `keep` signatures stay alive, this
+        one included; the one unused longest goes first."""
+        if sig != self._rider_sig:
+            segs = self._seg_cache.pop(sig, None)
+            if self._segments is not None:
+                self._seg_cache[self._rider_sig] = self._segments
+                while len(self._seg_cache) >= keep:
+                    self._seg_cache.pop(next(iter(self._seg_cache)))
+            self._segments, self._rider_sig = segs, sig
+        return self._segments is None
+
     def run_graphed(self):
         """Replay the plan as hipGraphs: every run of kernels between two eager ops is captured once (on first use)
         and replayed afterwards; eager ops (collectives) are issued from the host between the replays, on the calling
@@ -678,6 +711,8 @@ class Plan:
                                    | {x for op in payload if op.kind == "dep" for x in (op.src, op.dst) if x != 0})
                     segs.append(["graph", payload, None, sides])
             self._segments = segs
+        if self.riders is not None:
+            self.riders.graphed = False      # until the last replay below: a failure in between cannot tell what has gone out
         for seg in self._segments:
             if seg[0] == "eager":
                 seg[1].fn()
@@ -695,6 +730,8 @@ class Plan:
                         cur.wait_stream(sd)
                 seg[2] = g
             seg[2].replay()
+        if self.riders is not None:
+            self.riders.graphed = True
 
     def launches(self, prefix, carried=False):
         """[(launch(stream_handle), [descriptors])] for every planned launch whose entry point starts with `prefix`, in plan

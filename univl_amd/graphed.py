@@ -112,8 +112,6 @@ class GraphedTrainStep:
             self.model._in_pipelined_call = False
         loss.backward()
         self._clip_and_step(defer)
-        if defer:
-            self.model._pending_update = self.opt
         self.opt.zero_grad()
         return loss
 
@@ -148,12 +146,11 @@ class GraphedTrainStep:
 
     def _forward_riding(self, args, kw):
         """The pending BertAdam update is applied BY the forward: UniVL.forward launches what cannot ride, its forward products
-        carry the rest (UniVL._start_riding_update).  Same stream throughout: no event, no graph branch."""
-        opt, model = self.opt, self.model
+        carry the rest (optimization.PendingUpdate.start).  Same stream throughout: no event, no graph branch."""
+        model = self.model
         fl = model.flat
         assert getattr(fl, "shard_reducer", None) is None, "UNIVL_ADAM_RIDE does not combine with the sharded optimizer"
-        model._rider_update = dict(desc=opt._last_desc, groups=opt.chunk_groups(), max_blocks=self.adam_blocks)
-        opt._deferred = False                 # from here on the update counts as applied (launch_deferred's bookkeeping)
+        model._rider_update = self.opt._update.adopt(max_blocks=self.adam_blocks)
         fl.shadow_valid = True
         model._in_pipelined_call = True
         try:
@@ -248,8 +245,6 @@ class GraphedTrainStep:
                 with no_gc(), torch.cuda.graph(self._g_rest, pool=self._g_fwd.pool(), capture_error_mode="thread_local"):
                     self.loss.backward()
                     self._clip_and_step(defer=self.pipeline)
-                    if self.pipeline:
-                        self.model._pending_update = self.opt
                     self.opt.zero_grad()
                 self.mode = "whole"
             elif one_graph:

@@ -16,7 +16,8 @@ import torch
 from torch import nn
 
 from . import _ab, _lib, ops
-from .engine import FlatParams, Plan, Riders
+from .engine import FlatParams, Plan
+from .optimization import ADOPTED, STARTED
 from .parallel import BucketReducer, broadcast_parameters
 
 logger = logging.getLogger(__name__)
@@ -436,10 +437,12 @@ class UniVL(UniVLPreTrainedModel):
         self._flat = None
         self._steps = {}
         self._param_events = {}        # filled by a pipelined optimizer update in flight (univl_amd.graphed)
-        self._pending_update = None    # the optimizer holding a deferred update, if any
-        self._rider_update = None      # riding optimizer update (graphed.GraphedTrainStep): dict(desc, groups, max_blocks) of a prepared BertAdam update
-                                       # that THIS forward applies -- prologue launches + riders of its forward products
+        self._pending_update = None    # the optimizer that last deferred an update (optimization.BertAdam._defer), if any
+        self._rider_update = None      # the optimization.PendingUpdate THIS forward applies (adopted by _adopt_pending_update or by
+                                       # graphed.GraphedTrainStep) -- prologue launches + riders of its forward products
         self._in_pipelined_call = False
+        self.auto_ride_count = 0       # forwards that applied an update the unchanged loop's optimizer.step() left to them
+        self.graph_captures = 0        # captures of plans that can carry an update (_run_plan)
         self._reducer = None
         self._dp_checked, self._implicit_dp = False, False
         self._seed_dev = None
@@ -508,7 +511,7 @@ class UniVL(UniVLPreTrainedModel):
         itself asks for them only between backward and step (clip_grad_norm_(model.parameters(), ...), main_task_retrieval.py:347),
         where nothing is pending."""
         o = self.__dict__.get("_pending_update")
-        if o is not None and getattr(o, "_auto_deferred", False):
+        if o is not None and o._auto_deferred:
             self._flush_pending()
         return super().named_parameters(*a, **kw)
 
@@ -704,24 +707,14 @@ class UniVL(UniVLPreTrainedModel):
         if (self.graph_backward or hot) and not torch.cuda.is_current_stream_capturing():
             if plan.rider_keys:
                 # a captured plan holds the riding update's descriptor and chunk ranges: replay only while they are the ones captured
-                # (steady state of a training loop: same optimizer tables, same buffers), else capture again
+                # (steady state of a training loop: same optimizer tables, same buffers, so "no riders" + one update descriptor),
+                # else capture again
                 sig = None if plan.riders is None else plan.riders.signature()
-                if getattr(plan, "_rider_sig", None) != sig:
-                    # captured segments are kept PER signature: under gradient accumulation the forward after step() carries
-                    # riders and the following ones do not -- both graphs are captured once and replayed, not re-captured at every
-                    # transition.  At most GRAPH_SIGS signatures are kept (steady state: "no riders" + one update descriptor).
-                    cache = plan.__dict__.setdefault("_seg_cache", {})
-                    if plan._segments is not None:
-                        cache[getattr(plan, "_rider_sig", None)] = plan._segments
-                        while len(cache) > self.GRAPH_SIGS:
-                            cache.pop(next(iter(cache)))
-                    plan._segments = cache.pop(sig, None)
-                    if plan._segments is None:
-                        self.graph_captures = getattr(self, "graph_captures", 0) + 1
-                if plan._segments is None and sig is not None:
-                    import ctypes as C                  # the rider kernels' large-LDS opt-in must not happen inside the capture
-                    _lib.check(_lib.lib().univl_gemm_rider_prime(C.c_void_p(torch.cuda.current_stream().cuda_stream)), "gemm_rider_prime")
-                plan._rider_sig = sig
+                if plan.select_segments(sig, self.GRAPH_SIGS):
+                    self.graph_captures += 1
+                    if sig is not None:
+                        import ctypes as C              # the rider kernels' large-LDS opt-in must not happen inside the capture
+                        _lib.check(_lib.lib().univl_gemm_rider_prime(C.c_void_p(torch.cuda.current_stream().cuda_stream)), "gemm_rider_prime")
             plan.run_graphed()
         else:
             plan.run()
@@ -770,10 +763,11 @@ class UniVL(UniVLPreTrainedModel):
             raise RuntimeError("UniVL.forward: the caption path needs input_caption_ids / decoder_mask / output_caption_ids")
         if not self._dp_checked:
             self._auto_data_parallel()
-        adopted, riding = False, False
+        st, own = None, self._rider_update is None      # own: an update this forward applies is one it adopted itself
         try:
-            adopted = self._adopt_pending_update()
-            if not adopted:
+            self._adopt_pending_update()
+            upd = self._rider_update               # the update THIS forward applies: adopted just now, or by graphed.GraphedTrainStep
+            if upd is None:
                 self._flush_pending()
             fl = self.flat
             if getattr(fl, "shard_reducer", None) is not None:
@@ -788,97 +782,48 @@ class UniVL(UniVLPreTrainedModel):
                 st.decoder.load(input_caption_ids, decoder_mask, output_caption_ids)
             anchor = fl.params[self.ANCHOR]
             st.calls += 1
-            ru = self._rider_update
-            if ru is not None:
-                riding = True
-                self._start_riding_update(st, ru)
-            try:
-                if torch.is_grad_enabled() and anchor.requires_grad:
-                    out = _StepLossFn.apply(anchor, self, st).as_subclass(_LossTensor)
-                    out._univl = (self, st)
-                    return out
+            if upd is not None:
+                st.fwd.riders = upd.start(st.fwd.rider_keys)
+            if torch.is_grad_enabled() and anchor.requires_grad:
+                out = _StepLossFn.apply(anchor, self, st).as_subclass(_LossTensor)
+                out._univl = (self, st)
+            else:
                 self._run_plan(st.fwd, st)
-                return _loss_out(st)
-            finally:
-                st.fwd.riders = None
-        except BaseException:
-            if adopted:
-                self._unadopt_pending_update(riding)
+                out = _loss_out(st)
+            if upd is not None:
+                upd.done()
+            return out
+        except BaseException as ex:
+            # an update this forward took is never left behind or half applied in silence (optimization.PendingUpdate).  Nothing of it
+            # launched yet (a bad batch shape, out of memory while a new step was built, a failing join): handed back, pending again,
+            # the next forward or any flush applies it once.  Started: what has not gone out goes out now, or RuntimeError(PARTIAL).
+            # An update graphed.GraphedTrainStep adopted keeps that object's rule: the capture it failed in never ran, the prepared
+            # update is dropped with it (has_pending stays False) and the next call prepares a new one.
+            upd = self._rider_update if own else None
+            if upd is not None and upd.state == ADOPTED:
+                upd.hand_back()
+            elif upd is not None and upd.state == STARTED:
+                upd.complete_after_failure(None if st is None else st.fwd.riders, ex)
             raise
         finally:
-            # an update this forward adopted is never left behind: either it went out with the plan, or the except branch
-            # above handed it back to the optimizer; graphed.GraphedTrainStep sets and clears its own descriptor around its calls
-            if adopted:
-                self._rider_update = None
-
-    def _unadopt_pending_update(self, riding):
-        """forward() adopted the optimizer's pending update and failed.  Before any launch of the update went out (bad batch shape, out of
-        memory while a new step was built, a failing join): hand it back -- it is pending again and the next forward (or any flush) applies
-        it exactly once.  After _start_riding_update began enqueueing it cannot be taken back (some chunk ranges are applied, the ones
-        riding in the failed plan are not): apply the whole set of ranges that have not gone out as plain launches, so that every
-        parameter sees the update exactly once, and leave nothing pending."""
-        o, ru = self._pending_update, self._rider_update
-        self._rider_update = None
-        if o is None or ru is None:
-            return
-        if not riding:
-            o._deferred, o._auto_deferred = True, True
-            self.auto_ride_count = getattr(self, "auto_ride_count", 1) - 1
-            return
-        import ctypes as C
-        for st in self._steps.values():
-            rd = getattr(getattr(st, "fwd", None), "riders", None)
-            if rd is None or rd.desc is not ru["desc"]:
-                continue
-            h = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for key, c0, n, partly in rd.pending():
-                if partly:
-                    # a stack whose first products already carried a part: the slots are fractions of the range only the plan knows;
-                    # nothing here can tell which chunks went out -- refuse to guess
-                    raise RuntimeError("univl_amd.UniVL.forward failed after a part of the riding BertAdam update was enqueued; the "
-                                       "parameters hold a partial update (model.auto_ride = False avoids riding updates)")
-                _lib.check(_lib.lib().univl_bert_adam_range(rd.ref, c0, n, 0, 0, h), "bert_adam_range")
-            st.fwd.riders = None
+            if st is not None:
+                st.fwd.riders = None
+            self._rider_update = None
 
     def _adopt_pending_update(self):
         """The unchanged training loop (main_task_retrieval.py:333-353): optimizer.step() left its BertAdam update pending
         (optimization.BertAdam.step: auto-deferred), and THIS forward applies it -- the chunk groups the plan cannot carry as launches in
-        front of it, the rest as extra workgroups of its own products (_start_riding_update) -- exactly what the captured step of
-        graphed.GraphedTrainStep does.  Anything else that reads the parameters flushes the update first (_flush_pending)."""
+        front of it, the rest as extra workgroups of its own products (optimization.PendingUpdate.start) -- exactly what the captured
+        step of graphed.GraphedTrainStep does.  Anything else that reads the parameters flushes the update first (_flush_pending)."""
         o = self._pending_update
-        if (o is None or self._in_pipelined_call or self._rider_update is not None or not getattr(o, "has_pending", False)
-                or not getattr(o, "_auto_deferred", False)):
-            return False
+        if o is None or self._in_pipelined_call or self._rider_update is not None or not o._auto_deferred:
+            return
         fl = self.flat
-        if not getattr(fl, "adam_ride", False) or getattr(fl, "shard_reducer", None) is not None or torch.cuda.is_current_stream_capturing():
-            return False
-        self._rider_update = dict(desc=o._last_desc, groups=o.chunk_groups(), max_blocks=0)
-        o._deferred = False                   # from here on the update counts as applied (launch_deferred's bookkeeping)
-        o._auto_deferred = False
+        if not fl.adam_ride or getattr(fl, "shard_reducer", None) is not None or torch.cuda.is_current_stream_capturing():
+            return
         # fl.shadow_valid is left as it is: the update rewrites the bf16 shadow of the tensors it updates, and a shadow that was marked
         # dirty (mark_params_dirty, a broadcast) is still refreshed from the fp32 master by this forward, in front of the riders
-        self.auto_ride_count = getattr(self, "auto_ride_count", 0) + 1
-        return True
-
-    def _start_riding_update(self, st, ru):
-        """Riding optimizer update (univl_amd.graphed, UNIVL_ADAM_RIDE): the BertAdam update of the previous iteration is applied BY this
-        forward -- chunk groups the forward plan cannot carry (embedding tables, vectors, the first layer of each stack, the
-        cross encoder / decoder) as ordinary launches on the calling stream right now, the others as extra workgroups of the
-        forward products of the layer before (engine.Plan.add_gemm_rider)."""
-        import ctypes as C
-        from . import _lib
-        L, d = _lib.lib(), ru["desc"]
-        h = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        ranges, first = {}, True
-        for key, c0, n in ru["groups"]:
-            if key in st.fwd.rider_keys and key not in ranges:
-                ranges[key] = (c0, n)
-                continue
-            _lib.check(L.univl_bert_adam_range(C.byref(d), c0, n, 1 if first else 0, 0, h), "bert_adam_range")
-            first = False
-        if first:                     # nothing went out as a prologue launch: the per-tensor scalars still have to be prepared
-            _lib.check(L.univl_bert_adam_range(C.byref(d), 0, 0, 1, 0, h), "bert_adam_range")
-        st.fwd.riders = Riders(d, ranges, ru.get("max_blocks", 0))
+        self._rider_update = o._update.adopt(max_blocks=0)
 
     def get_sequence_visual_output(self, input_ids, token_type_ids, attention_mask, video, video_mask, shaped=False):
         """modeling.py:299-313.  `shaped=True` means the caller already flattened the pair dim AND normalised the video

@@ -13,7 +13,7 @@ import torch
 from torch.optim import Optimizer
 
 from . import _ab, _lib
-from .engine import FLAT_REGISTRY
+from .engine import FLAT_REGISTRY, Riders
 
 CHUNK = 8192   # elements per workgroup
 
@@ -238,6 +238,133 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, deferred=True):
     return tb.coef[1]
 
 
+PENDING, ADOPTED, STARTED, APPLIED = "pending", "adopted", "started", "applied"
+PARTIAL = ("univl_amd.UniVL.forward failed after a part of the riding BertAdam update was enqueued; the parameters hold a partial "
+           "update (model.auto_ride = False avoids riding updates)")
+
+
+class PendingUpdate:
+    """The BertAdam update that step() prepared and left for later, and where it currently is -- the one owner of that fact:
+
+      PENDING   prepared, nothing launched.  flush() applies it (-> APPLIED); adopt() hands it to a forward (-> ADOPTED).
+      ADOPTED   a forward has taken it, nothing launched yet.  hand_back() (the forward failed: -> PENDING, the next forward or any
+                flush applies it, once); start() (-> STARTED).
+      STARTED   start() enqueued the chunk groups the forward plan cannot carry and returned the engine.Riders of the rest, which the
+                plan's own products carry.  done() after the plan ran, complete_after_failure() after it did not (both -> APPLIED).
+      APPLIED   the update is over: every parameter has seen it once -- or complete_after_failure() raised RuntimeError(PARTIAL),
+                because it could not tell or could not finish.  Terminal (BertAdam._after_update runs on the way in).
+
+    Any other transition raises.  `auto`: the unchanged training loop deferred it (step() without arguments; only such an update is
+    adopted by UniVL.forward on its own), else step(defer=True) did (graphed.GraphedTrainStep adopts it itself)."""
+    __slots__ = ("opt", "desc", "auto", "model", "max_blocks", "state", "left", "prepared", "in_flight")
+
+    def __init__(self, opt, desc, auto, model=lambda: None):
+        self.opt, self.desc, self.auto, self.model, self.max_blocks, self.state = opt, desc, bool(auto), model, 0, PENDING
+        self.left = []              # STARTED: the chunk groups that have not gone out as plain launches (after start(): the carried ones)
+        self.prepared = False       # a range launch with do_prep = 1 went out (exactly one per update does)
+        self.in_flight = False      # a range launch was called and did not return: whether it went out cannot be told
+
+    def _require(self, state):
+        if self.state != state:
+            raise RuntimeError("BertAdam update is %s, not %s" % (self.state, state))
+
+    def _move(self, src, dst):
+        self._require(src)
+        self.state = dst
+
+    def _applied(self, src):
+        self._move(src, APPLIED)
+        self.opt._after_update(self.opt._fl)
+
+    def _rides(self, by):
+        model = self.model()
+        if self.auto and model is not None:
+            model.auto_ride_count += by
+
+    def _range(self, c0, n, stream, max_blocks=0):
+        """One univl_bert_adam_range launch; the first of an update prepares the per-tensor scalars."""
+        self.in_flight = True
+        rc = _lib.lib().univl_bert_adam_range(C.byref(self.desc), c0, n, 0 if self.prepared else 1, int(max_blocks), stream)
+        self.in_flight = False      # (a refused launch, rc != 0, did not go out)
+        _lib.check(rc, "bert_adam_range")
+        self.prepared = True
+
+    def flush(self, groups=None, on_group=None, max_blocks=0):
+        """Enqueue the whole update on the current stream: in one launch (groups None) or one launch per chunk group, calling
+        on_group(key) after the last launch of each key."""
+        self._require(PENDING)              # (an adopted update is the forward's to apply)
+        h = _stream()
+        if groups is None:
+            _lib.check(_lib.lib().univl_bert_adam(C.byref(self.desc), h), "bert_adam")
+        else:
+            for i, (key, c0, n) in enumerate(groups):
+                self._range(c0, n, h, max_blocks)
+                if on_group is not None and (i + 1 == len(groups) or groups[i + 1][0] != key):
+                    on_group(key)
+        # (the update rewrites the bf16 shadow of the tensors it updates: a valid shadow stays valid, and one that was marked dirty --
+        # tensors outside this update may be stale -- stays dirty until refresh_shadow)
+        self._applied(PENDING)
+
+    def adopt(self, max_blocks=0):
+        """A forward takes the update: from here on it counts as applied (has_pending is False).  `max_blocks`: grid cap of the carried
+        parts (0: none)."""
+        self._move(PENDING, ADOPTED)
+        self.max_blocks = int(max_blocks)
+        self._rides(+1)
+        return self
+
+    def hand_back(self):
+        self._move(ADOPTED, PENDING)
+        self._rides(-1)
+
+    def start(self, rider_keys, stream=None):
+        """The forward is about to run: chunk groups its plan cannot carry (embedding tables, vectors, the first layer of each stack, the
+        cross encoder / decoder; a second run of a carried key) go out as ordinary launches on `stream` (default: the current one) right
+        now, the others ride as extra workgroups of the forward products of the layer before (engine.Plan.add_gemm_rider): their Riders
+        are returned for the plan."""
+        self._move(ADOPTED, STARTED)
+        h = _stream() if stream is None else stream
+        left = self.left = list(self.opt.chunk_groups())            # (taken here, not at step(): chunk_groups() keeps its cache)
+        ranges, i = {}, 0
+        while i < len(left):
+            key, c0, n = left[i]
+            if key in rider_keys and key not in ranges:
+                ranges[key] = (c0, n)
+                i += 1
+            else:
+                self._range(c0, n, h)
+                del left[i]
+        if not self.prepared:         # nothing went out as a prologue launch: the per-tensor scalars still have to be prepared
+            self._range(0, 0, h)
+        return Riders(self.desc, ranges, self.max_blocks)
+
+    def done(self):
+        self._applied(STARTED)
+
+    def complete_after_failure(self, riders=None, cause=None):
+        """The forward failed after start(): the update cannot be taken back (some chunk ranges are applied), so every range that has not
+        gone out -- groups start() did not reach, keys of `riders` (the failed run's; None: start() itself failed) that no launch carried
+        -- goes out as a plain launch: every parameter sees the update exactly once.  Where that cannot be done -- a key went out in part
+        (its slots are fractions only the plan knows), the plan ran through graphs and failed before its last replay (engine.Riders.graphed),
+        a launch failed without telling whether it went out, a completing launch is refused, somebody is capturing the stream --
+        RuntimeError(PARTIAL), chained from `cause`.  Either way nothing is pending afterwards: the update is over (APPLIED)."""
+        self._require(STARTED)
+        sent = set() if riders is None else {key for key, _, _, partly in riders.pending() if partly}
+        ok = not (self.in_flight or any(not riders.whole(key) for key in sent) or torch.cuda.is_current_stream_capturing())
+        h = _stream()
+        try:
+            while ok and self.left:
+                key, c0, n = self.left[0]
+                if key not in sent:
+                    self._range(c0, n, h)
+                del self.left[0]
+        except RuntimeError:                # a completing launch was refused: its range has not gone out
+            ok = False
+        self._applied(STARTED)
+        if not ok:
+            raise RuntimeError(PARTIAL) from cause
+
+
 class BertAdam(Optimizer):
     """Fused BERT-Adam (see module docstring).  Arguments as modules/optimization.py:66-84."""
 
@@ -266,8 +393,7 @@ class BertAdam(Optimizer):
         self._fl = None
         self._tb = None
         self._m = self._v = self._step_dev = None
-        self._auto_deferred = False     # ... and step() itself did, for the model's next forward to apply (the unchanged training loop)
-        self._deferred = False          # step(defer=True) prepared an update that launch_deferred() / flush() still has to enqueue
+        self._update = None             # the PendingUpdate of the last step() that deferred (None: that step launched its update itself)
         self._last_desc = None
 
     def get_lr(self):
@@ -392,7 +518,15 @@ class BertAdam(Optimizer):
     # --------------------------------------------------------------------------------------- deferred / layer-wise update
     @property
     def has_pending(self):
-        return self._deferred
+        """step() prepared an update that nothing has launched or adopted yet (PendingUpdate: PENDING)."""
+        return self._update is not None and self._update.state == PENDING
+
+    _deferred = has_pending
+
+    @property
+    def _auto_deferred(self):
+        """... and step() without arguments did, for the model's next forward to adopt (the unchanged training loop)."""
+        return self.has_pending and self._update.auto
 
     def chunk_groups(self):
         """[(key, first_chunk, n_chunks)] over the chunk table of the last step(), in the order a forward pass needs the
@@ -421,22 +555,9 @@ class BertAdam(Optimizer):
 
     def launch_deferred(self, groups=None, on_group=None, max_blocks=0):
         """Enqueue the update prepared by step(defer=True) on the current stream: in one launch (groups None) or one launch
-        per chunk group, calling on_group(key) after the last launch of each key."""
-        d = self._last_desc
-        if not self._deferred or d is None:
-            return
-        L, h = _lib.lib(), _stream()
-        if groups is None:
-            _lib.check(L.univl_bert_adam(C.byref(d), h), "bert_adam")
-        else:
-            for i, (key, c0, n) in enumerate(groups):
-                _lib.check(L.univl_bert_adam_range(C.byref(d), c0, n, 1 if i == 0 else 0, int(max_blocks), h), "bert_adam_range")
-                if on_group is not None and (i + 1 == len(groups) or groups[i + 1][0] != key):
-                    on_group(key)
-        self._deferred = False
-        # (the update rewrites the bf16 shadow of the tensors it updates: a valid shadow stays valid, and one that was marked dirty --
-        # tensors outside this update may be stale -- stays dirty until refresh_shadow)
-        self._after_update(self._fl)
+        per chunk group, calling on_group(key) after the last launch of each key.  Nothing pending: nothing to do."""
+        if self.has_pending:
+            self._update.flush(groups, on_group, max_blocks)
 
     def _after_update(self, fl):
         """Sharded optimizer: this rank updated its pieces only -- all-gather what the next forward reads (the bf16 shadow;
@@ -462,9 +583,16 @@ class BertAdam(Optimizer):
 
     def flush(self):
         """Apply a deferred update now (checkpointing, evaluation, a forward outside the pipelined loop)."""
-        if self._deferred:
-            self._auto_deferred = False
-            self.launch_deferred()
+        self.launch_deferred()
+
+    def _defer(self, fl, desc, auto):
+        """The one place an update becomes pending -- and where the model learns which optimizer to ask for it (UniVL._flush_pending,
+        UniVL._adopt_pending_update)."""
+        owner = getattr(fl, "owner", lambda: None)      # (a flat buffer built without a model has none)
+        self._update = PendingUpdate(self, desc, auto, owner)
+        model = owner()
+        if model is not None:
+            model._pending_update = self
 
     def _can_ride(self, fl):
         """step() without arguments may leave its launch to the model's next forward (riding update): bf16 compute on a HIP device, one
@@ -473,7 +601,7 @@ class BertAdam(Optimizer):
         model = getattr(fl, "owner", lambda: None)()
         return bool(model is not None and getattr(fl, "adam_ride", False) and fl.compute_dtype == torch.bfloat16 and fl.device.type == "cuda"
                     and getattr(fl, "shard_reducer", None) is None and getattr(fl, "owned", None) is None
-                    and model.training and getattr(model, "auto_ride", True) and model._reducer is None
+                    and model.training and model.auto_ride and model._reducer is None
                     and not model._in_pipelined_call and not torch.cuda.is_current_stream_capturing())
 
     def zero_grad(self, set_to_none=True):
@@ -486,8 +614,7 @@ class BertAdam(Optimizer):
         """defer=True prepares the update (descriptor, per-tensor scalars inputs) but leaves its launch to launch_deferred():
         univl_amd.graphed.GraphedTrainStep overlaps it with the next forward pass."""
         loss = closure() if closure is not None else None
-        if self._deferred:
-            self.flush()
+        self.flush()
         fl = self._bind()
         auto = (not defer) and closure is None and self._can_ride(fl)
         pw = []
@@ -529,18 +656,15 @@ class BertAdam(Optimizer):
         else:
             d.row_flags, d.flag_seg, d.row_len = None, -1, 1
         self._last_desc = d
-        self._auto_deferred = auto
-        if auto:
-            # The unchanged training loop: leave the launch to the NEXT forward of the model, whose own products carry the update's
+        if auto or defer:
+            # auto, the unchanged training loop: leave the launch to the NEXT forward of the model, whose own products carry the update's
             # chunks as extra workgroups (UniVL._adopt_pending_update) -- the update is a 0.8 ms HBM stream, the forward a chain of
             # latency-bound launches on a third of the compute units (2.74 -> 2.53 ms per step in round 3, for the captured step).
             # Everything that reads the parameters before that forward applies the update first (UniVL._flush_pending: state_dict,
             # eval(), the evaluation entry points, optimizer.state_dict(), zero_grad(set_to_none=False)).
-            self._deferred = True
-            fl.owner()._pending_update = self
-        elif defer:
-            self._deferred = True
+            self._defer(fl, d, auto)
         else:
+            self._update = None
             _lib.check(_lib.lib().univl_bert_adam(C.byref(d), _stream()), "bert_adam")
             self._after_update(fl)      # (the step rewrote the bf16 shadow of what it updated; a dirty shadow stays dirty)
         for n in cfg:
