@@ -524,6 +524,22 @@ int univl_caption_overlap(const UnivlCaptionOverlap* d, hipStream_t stream);
 /* pick[i] = the index of the largest of score[i, 0 .. n_samp) (fp64), equal scores resolving to the LOWER index (the tie rule of
  * univl_beam_step); best[i] (optional) = that score.  A NaN is never the larger one.  n_inst, n_samp >= 1, otherwise UNIVL_EINVAL. */
 int univl_consensus_pick(const double* score, int32_t n_inst, int32_t n_samp, int32_t* pick, double* best, hipStream_t stream);
+/* Rewards -> per-caption training weights (the advantage of self-critical sequence training), on the device.  reward [n, ns] fp64, in
+ * the layout univl_caption_overlap writes rouge_l / bleu in; weight [n, ns] fp32 (the seq_weight of UnivlVocabCEW).
+ *   baseline_kind UNIVL_ADV_LOO   (baseline = NULL): the leave-one-out mean of the video's other samples,
+ *       A[i, s] = r[i, s] - (S_i - r[i, s]) / (m_i - 1),  S_i the left-to-right sum of the video's finite rewards, m_i their number
+ *       (m_i = ns when every reward is finite).  Needs ns >= 2, otherwise UNIVL_EINVAL.
+ *   baseline_kind UNIVL_ADV_GIVEN (baseline [n] fp64, e.g. the reward of the greedy or beam caption):  A[i, s] = r[i, s] - b[i].
+ * weight[i, s] = (float)(A[i, s] * scale): fp64 throughout, rounded once.  A non-finite reward gives weight 0 for that sample, leaves
+ * the other samples' baseline without it, and sets bit 0 (UNIVL_ADV_NONFINITE) of *status; so does a non-finite b[i] (every weight of
+ * the video 0), a video left with m_i < 2 under LOO (its weights 0) and a product that is not finite in fp32: no NaN or infinity is ever
+ * written.  One thread per video, sums in sample order: bit-reproducible; the one atomic is the integer OR into the status word.
+ * n, ns >= 1, no NULL pointer but baseline under LOO; otherwise UNIVL_EINVAL. */
+#define UNIVL_ADV_LOO 0
+#define UNIVL_ADV_GIVEN 1
+#define UNIVL_ADV_NONFINITE 1
+int univl_caption_advantage(const double* reward, const double* baseline, int32_t n, int32_t ns, int32_t baseline_kind, double scale,
+                            float* weight, int32_t* status, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------- retrieval search
  * The k best gallery rows of every query row by inner product -- torch.matmul(text, video.t()) of modeling.py:389 followed by a
  * row-wise top-k -- WITHOUT the [Nq, Ng] score matrix: the 768-deep product's epilogue keeps a running top-k per query and never
@@ -608,6 +624,43 @@ typedef struct UnivlVocabCE {
 } UnivlVocabCE;
 int univl_vocab_ce_fwd(const UnivlVocabCE* desc, hipStream_t stream);
 int univl_vocab_ce_bwd(const UnivlVocabCE* desc, hipStream_t stream);
+/* K16 weighted form: the same classifier + online log-softmax cross entropy with one fp32 weight per CAPTION -- what self-critical
+ * sequence training, minimum-risk training and importance- or confidence-weighted fine-tuning need.  rows = n_seq * seq_len: caption c
+ * owns rows [c * seq_len, (c + 1) * seq_len), the convention of UnivlVocabScore.  A row COUNTS when label != ignore_index; with
+ * nll_r = lse_r - logit_r[label_r] on counting rows and w_r = seq_weight[r / seq_len]:
+ *   univl_vocab_ce_weighted_fwd:
+ *     lse[rows]      as univl_vocab_ce_fwd: the same bits on the same operands (the tile walk is the unweighted kernel itself);
+ *     rowloss[r]   = w_r * nll_r, 0 on ignored rows;
+ *     scratch2[0]  = n_valid, the number of counting rows, independent of the weights;  scratch2[1] = the sum of rowloss;
+ *     loss         = (sum_r rowloss[r]) / n_valid, summed in the fixed order of the unweighted loss kernel; NaN when no row counts.
+ *   univl_vocab_ce_weighted_bwd:
+ *     dlogits[r, col] = (exp(logit - lse_r) - [col == label_r]) * (w_r * (gout / n_valid)) in the compute type; ignored rows and rows whose
+ *     weight is 0.0f are exact zeros; columns >= V stay untouched.  Call after the weighted forward with the same descriptor.
+ * Weights may be negative or zero.  With every weight 1.0f all outputs (loss, lse, rowloss, scratch2, dlogits) are bit-identical to
+ * univl_vocab_ce_fwd / _bwd.  Behaviour on non-finite weights: unspecified.  Every reduction is in fixed order, there are no atomics.
+ * Range: as univl_vocab_ce_fwd / _bwd, plus seq_len >= 1 dividing rows and seq_weight != NULL; otherwise UNIVL_EINVAL.
+ * The struct is in neither numbered size table: univl_vocab_ce_weighted_sizeof states its size. */
+typedef struct UnivlVocabCEW {
+    int32_t dtype, rows, V, K;
+    const void* x; int64_t ldx;
+    const void* table; int64_t ldt;
+    const float* bias;             /* [V] or null */
+    const int64_t* labels;         /* [rows] */
+    int32_t ignore_index, slots;
+    float* partial;                /* [rows, slots, 2] */
+    float* label_logit;            /* [rows] */
+    float* lse;                    /* [rows] */
+    float* rowloss;                /* [rows] */
+    float* scratch2;               /* [0] n_valid, [1] sum of the weighted row losses */
+    float* loss;                   /* [1] */
+    const float* gout;             /* backward: upstream gradient of the loss, one float on the device; null = 1 */
+    void* dlogits; int64_t lddl;   /* backward output */
+    const float* seq_weight;       /* [rows / seq_len] fp32, on the device */
+    int32_t seq_len, reserved;     /* reserved: 0 */
+} UnivlVocabCEW;
+int univl_vocab_ce_weighted_sizeof(void);
+int univl_vocab_ce_weighted_fwd(const UnivlVocabCEW* desc, hipStream_t stream);
+int univl_vocab_ce_weighted_bwd(const UnivlVocabCEW* desc, hipStream_t stream);
 /* K16 scoring form: teacher-forced SCORING on the tied vocabulary classifier -- the forward of K16 with the questions an evaluation asks of the
  * logits answered in the product's epilogue: for x [rows, K] . table [V, K]^T + bias (module_bert.py:327-330, decoder copy
  * module_decoder.py:180-183) and labels [rows], what log_softmax + gather + arg-max over the [rows, V] logits would give

@@ -2047,7 +2047,9 @@ static int vocab_head_operands(const D* d, VocabCeArgs& a, const char* who) {
     return UNIVL_OK;
 }
 
-static int vocab_ce_prepare(const UnivlVocabCE* d, VocabCeArgs& a, const char* who, bool bwd) {
+// D: UnivlVocabCE or UnivlVocabCEW (the same fields under the same names; the weighted form's own two are checked by its entry points)
+template <typename D>
+static int vocab_ce_prepare(const D* d, VocabCeArgs& a, const char* who, bool bwd) {
     int rc = vocab_head_shape(d, who);
     if (rc != UNIVL_OK) return rc;
     UNIVL_CHECK_ARG(d->x && d->table && d->labels && d->partial && d->label_logit && d->lse && d->rowloss && d->scratch2 && d->loss, UNIVL_EINVAL,
@@ -2079,6 +2081,41 @@ extern "C" int univl_vocab_ce_bwd(const UnivlVocabCE* d, hipStream_t stream) {
     const int rc = vocab_ce_prepare(d, a, "univl_vocab_ce_bwd", true);
     if (rc != UNIVL_OK) return rc;
     return vocab_ce_launch<true, false>(d->dtype, a, stream);
+}
+
+extern "C" int univl_vocab_ce_weighted_sizeof(void) { return (int)sizeof(UnivlVocabCEW); }
+
+// the weighted form's own checks + fields, after vocab_ce_prepare
+static int vocab_ce_weighted_prepare(const UnivlVocabCEW* d, VocabCeArgs& a, const char* who, bool bwd) {
+    const int rc = vocab_ce_prepare(d, a, who, bwd);
+    if (rc != UNIVL_OK) return rc;
+    UNIVL_CHECK_ARG(d->seq_len >= 1 && d->rows % d->seq_len == 0, UNIVL_EINVAL, "%s: rows %d are not whole captions of seq_len %d", who, d->rows,
+                    d->seq_len);
+    UNIVL_CHECK_ARG(d->seq_weight != nullptr, UNIVL_EINVAL, "%s: null seq_weight", who);
+    a.seq_weight = d->seq_weight; a.seq_len = d->seq_len;
+    return UNIVL_OK;
+}
+
+extern "C" int univl_vocab_ce_weighted_fwd(const UnivlVocabCEW* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    VocabCeArgs a;
+    const int rc = vocab_ce_weighted_prepare(d, a, "univl_vocab_ce_weighted_fwd", false);
+    if (rc != UNIVL_OK) return rc;
+    const int r2 = vocab_ce_launch<false, false>(d->dtype, a, stream);          // the unweighted tile kernel: the weight enters in the row fold
+    if (r2 != UNIVL_OK) return r2;
+    hipLaunchKernelGGL(vocab_ce_rows_weighted_kernel, dim3((d->rows + 3) / 4), dim3(256), 0, stream, d->partial, d->slots, a.nx, d->label_logit,
+                       d->labels, d->ignore_index, d->rows, d->lse, d->rowloss, d->seq_weight, d->seq_len);
+    hipLaunchKernelGGL(vocab_ce_loss_kernel, dim3(1), dim3(256), 0, stream, d->rowloss, d->labels, d->ignore_index, d->rows, d->scratch2, d->loss);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_vocab_ce_weighted_bwd(const UnivlVocabCEW* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    VocabCeArgs a;
+    const int rc = vocab_ce_weighted_prepare(d, a, "univl_vocab_ce_weighted_bwd", true);
+    if (rc != UNIVL_OK) return rc;
+    return vocab_ce_launch<true, false, true>(d->dtype, a, stream);
 }
 
 extern "C" int univl_vocab_score(const UnivlVocabScore* d, hipStream_t stream) {

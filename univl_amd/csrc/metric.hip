@@ -271,7 +271,58 @@ __global__ __launch_bounds__(64) void consensus_pick_kernel(const double* score,
     if (best != nullptr) best[i] = v;
 }
 
+__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }      // false for NaN and both infinities
+
+// one thread per video: rewards -> fp32 weights (include/univl_hip.h: univl_caption_advantage)
+__global__ __launch_bounds__(64) void caption_advantage_kernel(const double* reward, const double* baseline, int n, int ns, int kind, double scale,
+                                                               float* weight, int32_t* status) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* r = reward + (long)i * ns;
+    float* w = weight + (long)i * ns;
+    bool bad = false, have = true;
+    double sum = 0.0, b = 0.0;
+    int m = 0;
+    if (kind == UNIVL_ADV_LOO) {
+        for (int s = 0; s < ns; ++s)                                // left to right over the finite rewards
+            if (finite_f64(r[s])) { sum += r[s]; ++m; }
+        have = m >= 2;
+        bad = m < ns;
+    } else {
+        b = baseline[i];
+        have = finite_f64(b);
+        bad = !have;
+    }
+    for (int s = 0; s < ns; ++s) {
+        const double x = r[s];
+        float out = 0.0f;
+        if (!finite_f64(x)) bad = true;
+        else if (have) {
+            const double adv = kind == UNIVL_ADV_LOO ? x - (sum - x) / (double)(m - 1) : x - b;
+            out = (float)(adv * scale);
+            if (!(out - out == 0.0f)) { out = 0.0f; bad = true; }
+        }
+        w[s] = out;
+    }
+    if (bad) atomicOr(status, UNIVL_ADV_NONFINITE);
+}
+
 }  // namespace
+
+extern "C" int univl_caption_advantage(const double* reward, const double* baseline, int32_t n, int32_t ns, int32_t baseline_kind, double scale,
+                                       float* weight, int32_t* status, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(baseline_kind == UNIVL_ADV_LOO || baseline_kind == UNIVL_ADV_GIVEN, UNIVL_EINVAL, "univl_caption_advantage: baseline_kind %d",
+                    baseline_kind);
+    UNIVL_CHECK_ARG(reward && weight && status && (baseline_kind == UNIVL_ADV_LOO || baseline), UNIVL_EINVAL,
+                    "univl_caption_advantage: null pointer");
+    UNIVL_CHECK_ARG(n >= 1 && ns >= (baseline_kind == UNIVL_ADV_LOO ? 2 : 1), UNIVL_EINVAL,
+                    "univl_caption_advantage: n=%d ns=%d (n >= 1; ns >= 1, and >= 2 for the leave-one-out baseline)", n, ns);
+    hipLaunchKernelGGL(caption_advantage_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, reward, baseline, n, ns, baseline_kind, scale, weight,
+                       status);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
 
 extern "C" int univl_caption_overlap_sizeof(void) { return (int)sizeof(UnivlCaptionOverlap); }
 

@@ -18,6 +18,12 @@
 //   and stores it in the compute type: the matrix autograd calls dlogits, which the two existing backward products consume
 //   (dh = dlogits . E, dE += dlogits^T . h).  What K16 removes per step at 512 tokens: the 62 MB fp32 logits (written by the product, read
 //   by the loss kernel), the loss kernel's 31 MB dlogits write + the scale pass over them; what it adds: one more product.
+// Weighted (univl_vocab_ce_weighted_fwd / _bwd, WEIGHTED = true): caption c = row / seq_len carries one fp32 weight w.  The forward's tile
+//   kernel is the unweighted instantiation itself (lse is the same bits); vocab_ce_rows_weighted_kernel stores w * (lse - label logit) and
+//   vocab_ce_loss_kernel sums that, still divided by the number of counting rows.  The backward instantiation vocab_ce_kernel<T, true, false,
+//   WGN, true> loads w once per row of the tile (16 loads per thread, each lane of a row's 16-lane group the same address) and uses
+//   w * (gout / n_valid) where the unweighted code uses gout / n_valid: with w = 1.0f the same bits.  A row of weight 0 is stored as zeros
+//   like an ignored one.  No LDS, no barrier, no new tile walk; the unweighted instantiations do not see the weight.
 #pragma once
 #include "ranked.h"
 
@@ -35,6 +41,7 @@ struct VocabCeArgs {
     const float* gout;                  // device scalar or null (= 1)
     void* dl; long lddl;                // [rows, lddl] compute type (backward)
     int nx, ny;
+    const float* seq_weight; int seq_len;  // [rows / seq_len]  (WEIGHTED backward)
 };
 
 // One more (value, column) for a running maximum (m, c), offered in ASCENDING column order: the strict > keeps the lower column of equal
@@ -54,9 +61,10 @@ __device__ __forceinline__ void vocab_max_lanes(float& m, int& c) {
     }
 }
 
-template <typename T, bool BWD, bool TOP, int WGN>
+template <typename T, bool BWD, bool TOP, int WGN, bool WEIGHTED = false>
 __global__ __launch_bounds__(128 * WGN, 2) void vocab_ce_kernel(VocabCeArgs a) {
     static_assert(!(BWD && TOP), "the arg-max column belongs to the forward");
+    static_assert(BWD || !WEIGHTED, "the weighted forward is the unweighted tile kernel: the weight enters in the row fold");
     constexpr int BM = 128, BN = 128, WGM = 2, NC = 2;
     constexpr int WM = BM / WGM, WN = BN / WGN, MI = WM / 16, NI = WN / 16;
     int bx, by, bz;
@@ -139,8 +147,13 @@ __global__ __launch_bounds__(128 * WGN, 2) void vocab_ce_kernel(VocabCeArgs a) {
                 const int row = m0 + wm0 + 16 * ma + 4 * g + r;
                 if (row >= a.rows) continue;
                 const long lab = (long)a.labels[row];
-                const bool counts = lab != (long)a.ignore && nvalid > 0.0f;
-                const float sc = counts ? up / nvalid : 0.0f;
+                bool counts = lab != (long)a.ignore && nvalid > 0.0f;
+                float sc = counts ? up / nvalid : 0.0f;
+                if constexpr (WEIGHTED) {
+                    const float w = a.seq_weight[row / a.seq_len];
+                    counts = counts && w != 0.0f;              // a zero weight: the row is stored as an ignored one, exact zeros
+                    sc = counts ? w * sc : 0.0f;               // w * (gout / n_valid): at w = 1.0f the unweighted bits
+                }
                 const float l = counts ? a.lse[row] : 0.0f;
 #pragma unroll
                 for (int b = 0; b < NI; ++b) {
@@ -173,9 +186,10 @@ __device__ __forceinline__ void vocab_row_fold(const float* p, const int* pc, in
     for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
 }
 
-// a wave per row: lse[row]; rowloss[row] = lse - label logit (0 on ignored rows)
-__global__ __launch_bounds__(256) void vocab_ce_rows_kernel(const float* partial, int pitch, int slots, const float* label_logit, const int64_t* labels,
-                                                            int ignore, int rows, float* lse, float* rowloss) {
+// a wave per row: lse[row]; rowloss[row] = lse - label logit (0 on ignored rows); WEIGHTED: times seq_weight[row / seq_len]
+template <bool WEIGHTED>
+__device__ __forceinline__ void vocab_ce_rows_body(const float* partial, int pitch, int slots, const float* label_logit, const int64_t* labels, int ignore,
+                                                   int rows, float* lse, float* rowloss, const float* seq_weight, int seq_len) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     float m, s;
@@ -184,8 +198,23 @@ __global__ __launch_bounds__(256) void vocab_ce_rows_kernel(const float* partial
     if (lane == 0) {
         const float l = m + logf(s);
         lse[row] = l;
-        rowloss[row] = ((long)labels[row] != (long)ignore) ? l - label_logit[row] : 0.0f;
+        float nll = ((long)labels[row] != (long)ignore) ? l - label_logit[row] : 0.0f;
+        if constexpr (WEIGHTED) {
+            if ((long)labels[row] != (long)ignore) nll = seq_weight[row / seq_len] * nll;
+        }
+        rowloss[row] = nll;
     }
+}
+
+__global__ __launch_bounds__(256) void vocab_ce_rows_kernel(const float* partial, int pitch, int slots, const float* label_logit, const int64_t* labels,
+                                                            int ignore, int rows, float* lse, float* rowloss) {
+    vocab_ce_rows_body<false>(partial, pitch, slots, label_logit, labels, ignore, rows, lse, rowloss, nullptr, 1);
+}
+
+__global__ __launch_bounds__(256) void vocab_ce_rows_weighted_kernel(const float* partial, int pitch, int slots, const float* label_logit,
+                                                                     const int64_t* labels, int ignore, int rows, float* lse, float* rowloss,
+                                                                     const float* seq_weight, int seq_len) {
+    vocab_ce_rows_body<true>(partial, pitch, slots, label_logit, labels, ignore, rows, lse, rowloss, seq_weight, seq_len);
 }
 
 __device__ __forceinline__ float vocab_block_sum(float v, float* red) {      // 256 threads, fixed order
@@ -213,21 +242,22 @@ __global__ __launch_bounds__(256) void vocab_ce_loss_kernel(const float* rowloss
     }
 }
 
-template <typename T, bool BWD, bool TOP, int WGN>
+template <typename T, bool BWD, bool TOP, int WGN, bool WEIGHTED>
 static int vocab_ce_launch_as(const VocabCeArgs& a, hipStream_t stream) {
     constexpr int NC = 2, BK = NC * Mma<T>::CH, NT = 128 * WGN;
     constexpr size_t smem_k = 2 * (Tile<T, false, 128, BK, NT>::BYTES + Tile<T, false, 128, BK, NT>::BYTES);
     constexpr size_t smem_r = (size_t)WGN * 128 * (TOP ? 3 : 2) * sizeof(float);
     constexpr size_t smem = smem_k > smem_r ? smem_k : smem_r;
     static bool done[UNIVL_MAX_DEVICES] = {};
-    if (smem > 48 * 1024) univl_allow_lds(vocab_ce_kernel<T, BWD, TOP, WGN>, smem, done);
-    hipLaunchKernelGGL((vocab_ce_kernel<T, BWD, TOP, WGN>), dim3(a.nx * a.ny), dim3(NT), smem, stream, a);
+    if (smem > 48 * 1024) univl_allow_lds(vocab_ce_kernel<T, BWD, TOP, WGN, WEIGHTED>, smem, done);
+    hipLaunchKernelGGL((vocab_ce_kernel<T, BWD, TOP, WGN, WEIGHTED>), dim3(a.nx * a.ny), dim3(NT), smem, stream, a);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
 
-// the tile kernel of one form (training forward, backward, scoring forward) for the descriptor's dtype
-template <bool BWD, bool TOP>
+// the tile kernel of one form (training forward, backward, weighted backward, scoring forward) for the descriptor's dtype
+template <bool BWD, bool TOP, bool WEIGHTED = false>
 static int vocab_ce_launch(int dtype, const VocabCeArgs& a, hipStream_t stream) {
-    return dtype == UNIVL_BF16 ? vocab_ce_launch_as<__bf16, BWD, TOP, 4>(a, stream) : vocab_ce_launch_as<float, BWD, TOP, 2>(a, stream);
+    return dtype == UNIVL_BF16 ? vocab_ce_launch_as<__bf16, BWD, TOP, 4, WEIGHTED>(a, stream)
+                               : vocab_ce_launch_as<float, BWD, TOP, 2, WEIGHTED>(a, stream);
 }

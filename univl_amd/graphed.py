@@ -208,6 +208,9 @@ class GraphedTrainStep:
 
     # ------------------------------------------------------------------------------------------------- call
     def __call__(self, *args, **kw):
+        if kw.get("caption_weight") is not None or (len(args) > 12 and args[12] is not None):
+            raise NotImplementedError("GraphedTrainStep: the weighted caption step (caption_weight=...) has no graphed form; call the "
+                                      "model, loss.backward(), clip and optimizer.step() directly")
         self.calls += 1
         if self.calls <= self.warmup:
             return self._eager(args, kw)

@@ -674,7 +674,7 @@ class UniVL(UniVLPreTrainedModel):
         for n, _ in self.named_parameters():
             if n.startswith("bert.pooler") or n.startswith("visual.pooler"):
                 continue
-            if kind == "caption" and (n.startswith("cross.pooler") or n.startswith("similarity_dense")):
+            if kind in ("caption", "caption_weighted") and (n.startswith("cross.pooler") or n.startswith("similarity_dense")):
                 continue
             if kind == "align" and (n.startswith("decoder.") or n.startswith("cls")):
                 continue
@@ -684,14 +684,38 @@ class UniVL(UniVLPreTrainedModel):
         return out
 
     # ---------------------------------------------------------------------------------------- execution
-    def _get_step(self, kind, B, W, F):
-        key = (kind, B, W, F, self.training)
+    def _get_step(self, kind, B, W, F, n_cand=1, Wd=None):
+        """n_cand, Wd: the captions per video and their positions, part of a "caption_weighted" step's signature only."""
+        key = (kind, B, W, F, self.training) + ((n_cand, Wd) if kind == "caption_weighted" else ())
         st = self._steps.get(key)
         if st is None:
             from .steps import build_step
-            st = build_step(self, kind, B, W, F, self.training)
+            st = build_step(self, kind, B, W, F, self.training, n_cand=n_cand, Wd=Wd)
             self._steps[key] = st
         return st
+
+    def _caption_weighted_shape(self, B, input_caption_ids, decoder_mask, output_caption_ids, caption_weight):
+        """forward(caption_weight=...): (n_cand, Wd) of a reward-weighted caption batch, or ValueError -- host-side checks on shapes and
+        on the model's configuration only, before any device work."""
+        if self.decoder is None:
+            raise ValueError("UniVL.forward: caption_weight given, but this model was built without a decoder (stage one)")
+        if self.step_kind(True) != "caption":
+            raise ValueError("UniVL.forward: caption_weight is supported in stage-two caption mode only (stage_two with task_type "
+                             "'caption', no do_pretrain); this model's forward is %r" % (self.step_kind(True),))
+        if any(t is None for t in (input_caption_ids, decoder_mask, output_caption_ids)):
+            raise ValueError("UniVL.forward: caption_weight needs input_caption_ids, decoder_mask and output_caption_ids")
+        if caption_weight.dim() != 2 or caption_weight.shape[0] != B or caption_weight.shape[1] < 1:
+            raise ValueError("UniVL.forward: caption_weight of shape %s, expected [%d, n_cand] with n_cand >= 1 (one row per video)"
+                             % (tuple(caption_weight.shape), B))
+        n_cand = int(caption_weight.shape[1])
+        Wd = int(input_caption_ids.shape[-1])
+        for name, t in (("input_caption_ids", input_caption_ids), ("decoder_mask", decoder_mask), ("output_caption_ids", output_caption_ids)):
+            if tuple(t.shape) != (B, n_cand, Wd):
+                raise ValueError("UniVL.forward: %s of shape %s, expected [%d, %d, %d] (videos, captions per video as in caption_weight, "
+                                 "positions)" % (name, tuple(t.shape), B, n_cand, Wd))
+        if not 1 <= Wd <= self.decoder_config.max_target_embeddings:
+            raise ValueError("UniVL.forward: captions of %d positions, expected 1 .. %d" % (Wd, self.decoder_config.max_target_embeddings))
+        return n_cand, Wd
 
     AUTO_GRAPH_AFTER = 2
     GRAPH_SIGS = 4
@@ -750,19 +774,29 @@ class UniVL(UniVLPreTrainedModel):
 
     def forward(self, input_ids, token_type_ids, attention_mask, video, video_mask=None,
                 pairs_masked_text=None, pairs_token_labels=None, masked_video=None, video_labels_index=None,
-                input_caption_ids=None, decoder_mask=None, output_caption_ids=None):
-        """modeling.py:188-271.  Returns the scalar loss in training mode, None otherwise."""
+                input_caption_ids=None, decoder_mask=None, output_caption_ids=None, caption_weight=None):
+        """modeling.py:188-271.  Returns the scalar loss in training mode, None otherwise.
+        caption_weight [B, n_cand] (no counterpart in the reference): reward-weighted caption training.  The caption tensors are then
+        [B, n_cand, Wd] -- n_cand captions per video -- and the loss is sum_r w_r nll_r / n_valid over all their counting positions, w_r
+        the weight of the caption position r belongs to (the "caption_weighted" step, steps.build_step).  Single process only."""
         if not self.training:
             return None
         W, F = input_ids.shape[-1], video_mask.shape[-1]
         B = input_ids.numel() // W
         kind = self.step_kind(input_caption_ids is not None)
+        n_cand, Wd = 1, None
+        if caption_weight is not None:
+            n_cand, Wd = self._caption_weighted_shape(B, input_caption_ids, decoder_mask, output_caption_ids, caption_weight)
+            kind = "caption_weighted"
         if kind == "caption" and input_caption_ids is None:
             # modeling.py:238-254: without captions the caption task has no loss term at all (the reference returns the
             # float 0.0, whose .backward() fails in the script)
             raise RuntimeError("UniVL.forward: the caption path needs input_caption_ids / decoder_mask / output_caption_ids")
         if not self._dp_checked:
             self._auto_data_parallel()
+        if kind == "caption_weighted" and (self._reducer is not None or getattr(self._flat, "shard_reducer", None) is not None):
+            raise NotImplementedError("UniVL.forward(caption_weight=...): the weighted caption step is single-process only; data parallel "
+                                      "and the sharded optimizer are not supported for it")
         st, own = None, self._rider_update is None      # own: an update this forward applies is one it adopted itself
         try:
             self._adopt_pending_update()
@@ -773,13 +807,13 @@ class UniVL(UniVLPreTrainedModel):
             if getattr(fl, "shard_reducer", None) is not None:
                 fl.shard_reducer.join()            # the all-gather of the updated shadow must have landed
             fl.refresh_shadow()
-            st = self._get_step(kind, B, W, F)
+            st = self._get_step(kind, B, W, F, n_cand, Wd)
             st.enc.load(input_ids, token_type_ids, attention_mask, video, video_mask)
             if kind in ("pretrain", "pretrain_nocap"):
                 st.enc_m.load(pairs_masked_text, token_type_ids, attention_mask, masked_video, video_mask)
                 st.heads.load(pairs_token_labels, video_labels_index)
             if st.decoder is not None:
-                st.decoder.load(input_caption_ids, decoder_mask, output_caption_ids)
+                st.decoder.load(input_caption_ids, decoder_mask, output_caption_ids, caption_weight)
             anchor = fl.params[self.ANCHOR]
             st.calls += 1
             if upd is not None:

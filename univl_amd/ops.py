@@ -480,6 +480,23 @@ def consensus_pick(score):
     return pick, best
 
 
+def caption_advantage(reward, baseline=None, scale=1.0, status=None):
+    """reward: [n, ns] fp64 device tensor -> (weight [n, ns] fp32, status [1] int32), include/univl_hip.h: univl_caption_advantage.
+    baseline None: the leave-one-out mean of the video's other samples (ns >= 2); else [n] fp64 on the device.  status: an int32 device
+    word the non-finite flag is OR-ed into (default: a fresh zero).  Nothing is read on the host."""
+    _require_gpu(reward, baseline, status)
+    assert reward.dtype == torch.float64 and reward.dim() == 2 and reward.is_contiguous()
+    n, ns = reward.shape
+    assert baseline is None or (baseline.dtype == torch.float64 and baseline.is_contiguous() and baseline.numel() == n)
+    weight = torch.empty(n, ns, dtype=torch.float32, device=reward.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=reward.device)
+    assert status.dtype == torch.int32 and status.numel() == 1
+    _lib.check(_lib.lib().univl_caption_advantage(_p(reward), _p(baseline), n, ns, _lib.ADV_LOO if baseline is None else _lib.ADV_GIVEN,
+                                                  float(scale), _p(weight), _p(status), _stream()), "caption_advantage")
+    return weight, status
+
+
 def beam_backtrack(hist_parents, hist_tokens, scores, length, n_best):
     """Walk the n_best best beams of every instance back through the history (include/univl_hip.h: univl_beam_backtrack).
     Returns (hyp [n, n_best, Tmax] int32, -1 padded; hyp_scores [n, n_best] fp32)."""
@@ -722,6 +739,33 @@ def vocab_ce_fwd(desc):
 
 def vocab_ce_bwd(desc):
     _lib.check(_lib.lib().univl_vocab_ce_bwd(C.byref(desc), _stream()), "vocab_ce_bwd")
+
+
+def vocab_ce_weighted_desc(x, table, bias, labels, dlogits, V, seq_weight, seq_len, ignore_index=-1):
+    """Descriptor of the weighted form of K16 (include/univl_hip.h: UnivlVocabCEW) + the buffers it owns: vocab_ce_desc's operands plus
+    seq_weight [rows / seq_len] fp32 on the device, caption c owning rows [c * seq_len, (c + 1) * seq_len).  Returns (desc, buffers).
+    Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
+    _require_gpu(x, table, bias, labels, dlogits, seq_weight)
+    assert seq_weight.dtype == torch.float32 and seq_weight.is_contiguous()
+    assert seq_len < 1 or seq_weight.numel() * seq_len >= x.shape[0]
+    d = vocab_head_desc(_lib.VocabCEW, x, table, bias, labels, V, ignore_index)
+    rows, dev = d.rows, x.device
+    b = dict(partial=torch.empty(rows, max(d.slots, 1), 2, device=dev), label_logit=torch.zeros(rows, device=dev),
+             lse=torch.empty(rows, device=dev), rowloss=torch.empty(rows, device=dev), scratch=torch.zeros(2, device=dev),
+             loss=torch.zeros(1, device=dev), keep=(x, table, bias, labels, dlogits, seq_weight))
+    d.partial, d.label_logit, d.lse, d.rowloss = _p(b["partial"]), _p(b["label_logit"]), _p(b["lse"]), _p(b["rowloss"])
+    d.scratch2, d.loss, d.gout = _p(b["scratch"]), _p(b["loss"]), None
+    d.dlogits, d.lddl = _p(dlogits), dlogits.stride(0)
+    d.seq_weight, d.seq_len = _p(seq_weight), int(seq_len)
+    return d, b
+
+
+def vocab_ce_weighted_fwd(desc):
+    _lib.check(_lib.lib().univl_vocab_ce_weighted_fwd(C.byref(desc), _stream()), "vocab_ce_weighted_fwd")
+
+
+def vocab_ce_weighted_bwd(desc):
+    _lib.check(_lib.lib().univl_vocab_ce_weighted_bwd(C.byref(desc), _stream()), "vocab_ce_weighted_bwd")
 
 
 def vocab_score_desc(x, table, bias, labels, V, seq_len, ignore_index=-1, out=None):

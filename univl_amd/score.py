@@ -41,7 +41,8 @@ class CaptionScores:
 
 def beam_inputs_labels(tokens, lengths, bos, eos, pad, Wd):
     """Teacher-forcing inputs for the hypotheses of a decode.BeamResult, as tensor operations on the tensors' own device (no host
-    read).  tokens [n, n_best, Tmax] (-1 padded), lengths [n] (clamped to [0, Tmax]); Tmax <= Wd.  Per hypothesis, with
+    read).  tokens [n, n_best, Tmax] (-1 padded), lengths [n] -- or [n, n_best], one per hypothesis, as a sample.SampleResult has them --
+    (clamped to [0, Tmax]); Tmax <= Wd.  Per hypothesis, with
     cut = the position after the first eos inside the length, or the length when there is none:
       labels [n, n_best, Wd] int64   the hypothesis tokens at positions < cut, -1 after
       inputs [n, n_best, Wd] int64   [bos] + hyp[:-1] at positions < cut, pad after
@@ -54,7 +55,7 @@ def beam_inputs_labels(tokens, lengths, bos, eos, pad, Wd):
     if T < Wd:
         tok = torch.nn.functional.pad(tok, (0, Wd - T), value=-1)
     pos = torch.arange(Wd, device=tok.device)
-    length = lengths.to(torch.int64).clamp(0, T).view(n, 1, 1)
+    length = lengths.to(torch.int64).clamp(0, T).view(n, -1, 1)          # [n, 1, 1] or [n, n_best, 1]
     at_eos = (tok == int(eos)) & (pos < length) & (int(eos) >= 0)
     first = torch.where(at_eos, pos, torch.full_like(pos, Wd)).min(dim=-1, keepdim=True).values
     keep = pos < torch.minimum(first + 1, length)

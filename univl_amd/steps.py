@@ -4,6 +4,8 @@
     align     stage one, FT-Align (--train_sim_after_cross): encoders -> every (text, video) pair through the cross
               encoder -> pooler -> similarity_dense -> loss                                              (:341-375)
     caption   stage two, task_type "caption": encoders -> cross encoder -> decoder -> vocabulary CE      (:238-254)
+    caption_weighted   the caption path over n_cand captions per video, each with a weight of its own (reward-weighted training:
+              self-critical sequence training, minimum-risk training); no counterpart in the reference
     pretrain  stage two, do_pretrain: clean + masked encoder passes, cross encoder, MLM + MFM heads, joint
               similarity, decoder, cross-encoder alignment -- the five losses of :212-267
 
@@ -475,10 +477,13 @@ class VocabHead:
     """BertLMPredictionHead tied to BERT's word table + CrossEntropyLoss(ignore_index=-1)
     (module_bert.py:299-330 / module_decoder.py:156-183; modeling.py:252-254, 273-276)."""
 
-    def __init__(self, cx, prefix, T, stream=0, transform_only=False):
+    def __init__(self, cx, prefix, T, stream=0, transform_only=False, seq_len=None):
         """transform_only: the buffers of the transform and the labels alone -- no dlogits [T, V] and no backward workspace (score.CaptionScorer
-        feeds the transform's output to univl_vocab_score; build_transform is then the only builder to call)."""
+        feeds the transform's output to univl_vocab_score; build_transform is then the only builder to call).
+        seq_len: the weighted form (univl_vocab_ce_weighted_fwd / _bwd) -- rows are whole captions of seq_len positions and self.weight
+        [T / seq_len] holds one fp32 weight per caption."""
         self.cx, self.prefix, self.T, self.sm = cx, prefix, T, stream
+        self.seq_len, self.weight = seq_len, None
         e, ct, bf = cx.e, cx.ct, cx.bf
         V = cx.model.bert_config.vocab_size
         self.V, self.ldv = V, (V + 7) // 8 * 8
@@ -494,6 +499,9 @@ class VocabHead:
         self.dlogits = e(T, self.ldv, dtype=ct)
         self.loss, self.scratch = e(1), e(2)
         self.dh, self.dg, self.du = e(T, H), e(T, H), e(T, H, dtype=ct)
+        if seq_len is not None:
+            assert seq_len >= 1 and T % seq_len == 0, (T, seq_len)
+            self.weight = e(T // seq_len)
 
     @property
     def logits(self):
@@ -503,7 +511,9 @@ class VocabHead:
 
     def _k16_desc(self, x16, bias, table):
         e, T = self.cx.e, self.T
-        d = ops.vocab_head_desc(_lib.VocabCE, x16, table, bias, self.labels, self.V)
+        d = ops.vocab_head_desc(_lib.VocabCE if self.weight is None else _lib.VocabCEW, x16, table, bias, self.labels, self.V)
+        if self.weight is not None:
+            d.seq_weight, d.seq_len = self.weight.data_ptr(), self.seq_len
         self.k16 = k = dict(partial=e(T, d.slots, 2), label_logit=e(T), lse=e(T), rowloss=e(T))
         d.partial, d.label_logit, d.lse, d.rowloss = (k["partial"].data_ptr(), k["label_logit"].data_ptr(), k["lse"].data_ptr(),
                                                       k["rowloss"].data_ptr())
@@ -531,6 +541,12 @@ class VocabHead:
         cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
         W32 = fl.w32
         self.build_transform(fwd, x16)
+        if self.weight is not None:
+            if not (with_loss and _ab.get("vocab_ce")):
+                raise RuntimeError("VocabHead: per-caption weights exist only in K16 (univl_vocab_ce_weighted_fwd / _bwd); UNIVL_VOCAB_CE=0 "
+                                   "has no weighted form")
+            fwd.add("univl_vocab_ce_weighted_fwd", self._k16_desc(self.h16, W32(n["bias"]), fl.wop(n["emb"])), sm)
+            return
         if with_loss and _ab.get("vocab_ce"):
             # K16: the product's epilogue keeps the online log-softmax statistics; the [T, 30522] logits never exist (module_bert.py:327-330 +
             # modeling.py:253 / 275 in one entry point); the backward recomputes the product into dlogits
@@ -546,10 +562,10 @@ class VocabHead:
         cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
         W32, G = fl.w32, fl.g
         if self.k16 is not None:
-            db = _lib.VocabCE.from_buffer_copy(self.k16["desc"])      # the forward's descriptor + the upstream gradient of this loss term
+            db = type(self.k16["desc"]).from_buffer_copy(self.k16["desc"])      # the forward's descriptor + the upstream gradient of this loss term
             db.gout = gout.data_ptr()
             self.k16["gout"] = gout
-            bwd.add("univl_vocab_ce_bwd", db, sm)
+            bwd.add("univl_vocab_ce_bwd" if self.weight is None else "univl_vocab_ce_weighted_bwd", db, sm)
         else:
             bwd.add_callable(lambda: ops.scale_ct(self.dlogits, gout), sm)
         # dh = dlogits . E contracts over the 30522-word vocabulary with only (T / 64) x 12 output tiles: unsplit, each workgroup
@@ -599,7 +615,8 @@ class RowFeatures:
 class DecoderRun:
     """DecoderModel.forward (module_decoder.py:372-406) on top of a row-wise CrossRun + the caption CE (modeling.py:246-254)."""
 
-    def __init__(self, cx, run, Wd, with_loss=True):
+    def __init__(self, cx, run, Wd, with_loss=True, weighted=False):
+        """weighted: the head's loss carries one weight per caption (VocabHead(seq_len=Wd)); load() then takes caption_weight."""
         self.cx, self.run, self.Wd = cx, run, Wd
         B = run.P
         self.B, self.T = B, B * Wd
@@ -610,7 +627,7 @@ class DecoderRun:
         self.e0_16 = e(T, H, dtype=ct) if bf else self.e0_32
         L = cx.model.decoder_config.num_decoder_layers
         self.stack = DecoderStack(fl, L, B, Wd, run.S, self.dmask, run.cmask, cx.p, cx.seed_dev, cx.sites, stream=run.sm)
-        self.head = VocabHead(cx, "decoder.classifier.cls.predictions", T, stream=run.sm)
+        self.head = VocabHead(cx, "decoder.classifier.cls.predictions", T, stream=run.sm, seq_len=Wd if weighted else None)
         self.off = cx.sites.next()
         self.dout = e(T, H)
         self.with_loss = with_loss
@@ -619,11 +636,13 @@ class DecoderRun:
     N = dict(bw="bert.embeddings.word_embeddings.weight", bp="bert.embeddings.position_embeddings.weight",
              lg="decoder.embeddings.LayerNorm.weight", lb="decoder.embeddings.LayerNorm.bias")
 
-    def load(self, input_caption_ids, decoder_mask, output_caption_ids=None):
+    def load(self, input_caption_ids, decoder_mask, output_caption_ids=None, caption_weight=None):
         self.cap_ids.copy_(input_caption_ids.reshape(self.B, self.Wd), non_blocking=True)
         self.dmask.copy_(decoder_mask.reshape(self.B, self.Wd), non_blocking=True)
         if output_caption_ids is not None:
             self.head.labels.copy_(output_caption_ids.reshape(-1), non_blocking=True)
+        if self.head.weight is not None:
+            self.head.weight.copy_(caption_weight.reshape(-1), non_blocking=True)
 
     def build_forward(self, fwd):
         cx, n, fl, dt, sm = self.cx, self.N, self.cx.fl, self.cx.dt, self.run.sm
@@ -818,7 +837,8 @@ def _ddp_hook(cx, fl, model, kind):
     return hook, buckets, (sched, emit)
 
 
-def build_step(model, kind, B, W, F, training):
+def build_step(model, kind, B, W, F, training, n_cand=1, Wd=None):
+    """n_cand, Wd: the captions per video and their positions of kind "caption_weighted" (Wd None: W)."""
     cx = Ctx(model, training)
     fl, tc = cx.fl, cx.tc
     st = Step(cx)
@@ -834,9 +854,9 @@ def build_step(model, kind, B, W, F, training):
     # Round 5: the first layer of the cross encoder / the decoder is read after both encoder stacks; while an update rides, its chunks go
     # with the products of the text / video stack's LAST layer (which carry nothing otherwise) instead of a launch in front of the forward
     if _ab.get("tail_ride"):
-        if kind in ("align", "caption", "pretrain", "pretrain_nocap") and model.cross is not None:
+        if kind in ("align", "caption", "caption_weighted", "pretrain", "pretrain_nocap") and model.cross is not None:
             enc.text.tail_key = ("layer", "cross", 0)
-        if kind in ("caption", "pretrain") and model.decoder is not None:
+        if kind in ("caption", "caption_weighted", "pretrain") and model.decoder is not None:
             enc.vis.tail_key = ("layer", "decoder", 0)
     enc.build_forward(fwd)
     st.fwd_encoders_len = len(fwd)
@@ -860,6 +880,20 @@ def build_step(model, kind, B, W, F, training):
         st.run_rows = CrossRun(cx, enc, rows, rows)
         st.run_rows.build_forward(fwd)
         st.decoder = DecoderRun(cx, st.run_rows, W)
+        st.decoder.build_forward(fwd)
+        st.loss_terms.append(st.decoder.loss)
+    elif kind == "caption_weighted":
+        # n_cand captions per video, instance-major: the encoders run once per video, the cross encoder and the decoder once per
+        # caption (every row index repeated n_cand times; CrossRun's backward accumulates repeated indices into enc.dseq / enc.dvis as
+        # it does for the align pairs).  Single process only: no gradient exchange is planned for this kind.
+        if cx.red is not None:
+            raise NotImplementedError("the caption_weighted step is single-process only: data parallel and the sharded optimizer are not "
+                                      "supported for it")
+        st.n_cand = int(n_cand)
+        rows_rep = [i for i in range(B) for _ in range(st.n_cand)]
+        st.run_rows = CrossRun(cx, enc, rows_rep, rows_rep)
+        st.run_rows.build_forward(fwd)
+        st.decoder = DecoderRun(cx, st.run_rows, W if Wd is None else int(Wd), weighted=True)
         st.decoder.build_forward(fwd)
         st.loss_terms.append(st.decoder.loss)
     elif kind in ("pretrain", "pretrain_nocap"):
@@ -902,7 +936,8 @@ def build_step(model, kind, B, W, F, training):
         enc.sparse_word_grad = sparse
         # gradient norms from the wgrad epilogues: single-GPU only (after an all-reduce the local sums are not the
         # norms of the averaged gradients) and only where every matrix has one writer per backward
-        fuse = (cx.red is None and kind in ("joint", "align", "caption") and bool(_ab.get("fused_norms")))
+        # (caption_weighted: one cross run and one decoder run over all B * n_cand captions, so still one writer per matrix)
+        fuse = (cx.red is None and kind in ("joint", "align", "caption", "caption_weighted") and bool(_ab.get("fused_norms")))
         gs = GradState(fl, fresh, fuse_sumsq=fuse)
         hook, buckets, sched = _ddp_hook(cx, fl, model, kind)
         # A layer reports its gradient slice to the exchange schedule only after its LAST writer in this backward: the
