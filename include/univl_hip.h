@@ -540,6 +540,56 @@ int univl_consensus_pick(const double* score, int32_t n_inst, int32_t n_samp, in
 #define UNIVL_ADV_NONFINITE 1
 int univl_caption_advantage(const double* reward, const double* baseline, int32_t n, int32_t ns, int32_t baseline_kind, double scale,
                             float* weight, int32_t* status, hipStream_t stream);
+/* The document-frequency TABLES of UnivlCaptionOverlap, built on the device from token rows: no host read, no synchronisation,
+ * capturable.  The row table is UnivlCaptionOverlap's (sym [rows, ld] int32, len [rows], T <= UNIVL_OVERLAP_TMAX, symbols in
+ * [0, UNIVL_OVERLAP_SYM_MAX]).  A DOCUMENT i < items is the set of rows ref_rows[ref_begin[i] .. ref_begin[i + 1]); documents may
+ * share rows; an empty document contributes nothing.  With the n-gram keys of UnivlCaptionOverlap (n = 1 .. 4),
+ *   df(g) = the number of documents in which g occurs at least once, in any of the document's rows, at a position p with p + n <= len.
+ * Written:
+ *   df_keys [capacity] uint64   every key with df >= 1 exactly once, ascending as UNSIGNED 64-bit numbers (the four per-n tables one
+ *                               after the other: keys of a larger n are larger numbers)
+ *   df_cnt  [capacity] int32    the matching df
+ *   df_begin [5] int32          DEVICE words: the n-grams are entries df_begin[n-1] .. df_begin[n)
+ * Entries at and past df_begin[4] are left as they were.  The result is a function of the multiset of (document, key) pairs: integer
+ * atomics order the intermediate buffers, never the outputs, which are bit-reproducible.  No float arithmetic.
+ * LAUNCHES (csrc/ngram_df.hip), every grid sized from n_refs, T and capacity, the true counts read from device words:
+ *   emit   one wave per document: a row's n-gram is emitted unless an equal key stands earlier in the row or in an earlier row of
+ *          the document; one integer atomic on a device cursor per row hands out the slots
+ *   sort   LSD radix sort of the 64-bit keys, 8 passes of 8 bits: per-tile histogram, one scan over [256][tiles], a stable scatter
+ *          over tiles of UNIVL_NGRAM_DF_TILE keys
+ *   fold   head flags, the same scan, compaction to (key, run start), run lengths and the three lower-bound searches of df_begin
+ * CAPACITY: the caller's statement of df_keys' / df_cnt's length; n_refs * 4 T always suffices.  With more distinct keys than that,
+ * bit UNIVL_NGRAM_DF_OVERFLOW is OR-ed into *status, nothing is written at or past capacity, every df_begin entry is <= capacity, and
+ * the contents are otherwise unspecified.
+ * WORKSPACE: 64 + 16 N + 1024 ceil(N / UNIVL_NGRAM_DF_TILE) bytes with N = 4 T n_refs (the control words, two key buffers, the
+ * histograms), 16-byte aligned (UNIVL_EALIGN); univl_ngram_df_ws_bytes evaluates this on the host (-1 for arguments univl_ngram_df
+ * would refuse; N must stay below 2^31).
+ * RANGE: 1 <= T <= UNIVL_OVERLAP_TMAX, T <= ld, rows, items, n_refs, capacity >= 1, no NULL pointer, ws_bytes as above; otherwise
+ * UNIVL_EINVAL and nothing is launched.  DATA ON THE DEVICE is clamped and flagged as in univl_caption_overlap, with the same
+ * UNIVL_OVERLAP_BAD_LEN / _SYM / _ROW / _REFS bits OR-ed into *status (the caller clears it) and nothing read out of range; _REFS:
+ * a document's offsets leave [0, n_refs] or decrease (it is then the clamped range, empty when decreasing).  Offsets that are not
+ * monotone can make documents overlap and list more than n_refs rows in all: what no longer fits N keys is dropped and
+ * UNIVL_NGRAM_DF_OVERFLOW is set as well. */
+#define UNIVL_NGRAM_DF_OVERFLOW 16
+#define UNIVL_NGRAM_DF_TILE 4096
+typedef struct UnivlNgramDf {
+    const int32_t* sym; int64_t ld;  /* [rows, ld] int32 symbols                                                                  */
+    const int32_t* len;              /* [rows]                                                                                    */
+    int32_t rows, T, items, n_refs;
+    const int32_t* ref_begin;        /* [items + 1]                                                                               */
+    const int32_t* ref_rows;         /* [n_refs]                                                                                  */
+    uint64_t* df_keys;               /* [capacity] written                                                                        */
+    int32_t* df_cnt;                 /* [capacity] written                                                                        */
+    int32_t* df_begin;               /* [5] device words, written                                                                 */
+    int32_t* status;                 /* one word, bits OR-ed in                                                                   */
+    int32_t capacity, reserved;      /* reserved: 0                                                                               */
+    void* ws; int64_t ws_bytes;      /* see WORKSPACE                                                                             */
+} UnivlNgramDf;
+/* sizeof(UnivlNgramDf) (in neither numbered size table) and the scatter tile, for a binding's load-time check */
+int univl_ngram_df_sizeof(void);
+int univl_ngram_df_tile(void);
+int64_t univl_ngram_df_ws_bytes(int32_t n_refs, int32_t T);
+int univl_ngram_df(const UnivlNgramDf* d, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------- retrieval search
  * The k best gallery rows of every query row by inner product -- torch.matmul(text, video.t()) of modeling.py:389 followed by a
  * row-wise top-k -- WITHOUT the [Nq, Ng] score matrix: the 768-deep product's epilogue keeps a running top-k per query and never

@@ -104,6 +104,14 @@ class CaptionOverlap(C.Structure):
                 ("bleu", vp), ("status", vp)]
 
 
+class NgramDf(C.Structure):
+    """include/univl_hip.h: UnivlNgramDf.  Not in _STRUCTS: the library states its size through univl_ngram_df_sizeof (checked in
+    lib())."""
+    _fields_ = [("sym", vp), ("ld", i64), ("len", vp), ("rows", i32), ("T", i32), ("items", i32), ("n_refs", i32), ("ref_begin", vp),
+                ("ref_rows", vp), ("df_keys", vp), ("df_cnt", vp), ("df_begin", vp), ("status", vp), ("capacity", i32), ("reserved", i32),
+                ("ws", vp), ("ws_bytes", i64)]
+
+
 class VocabCEW(C.Structure):
     """include/univl_hip.h: UnivlVocabCEW -- VocabCE's fields, then the per-caption weights.  Not in _STRUCTS either: the library states
     its size through univl_vocab_ce_weighted_sizeof (checked in lib())."""
@@ -116,6 +124,7 @@ TOPK_MAX, TOPK_SLICES_MAX = 64, 256   # include/univl_hip.h: UNIVL_TOPK_MAX, UNI
 SAMPLE_KMAX, SAMPLE_SLICES = 64, 8    # include/univl_hip.h: UNIVL_SAMPLE_KMAX, UNIVL_SAMPLE_SLICES
 OVERLAP_TMAX, OVERLAP_SYM_MAX = 128, 65534   # include/univl_hip.h: UNIVL_OVERLAP_TMAX, UNIVL_OVERLAP_SYM_MAX
 OVERLAP_BAD_LEN, OVERLAP_BAD_SYM, OVERLAP_BAD_ROW, OVERLAP_BAD_REFS = 1, 2, 4, 8
+NGRAM_DF_OVERFLOW, NGRAM_DF_TILE = 16, 4096   # include/univl_hip.h: UNIVL_NGRAM_DF_OVERFLOW, UNIVL_NGRAM_DF_TILE
 
 _STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk, VocabScore, SampleStep]
 _lib = None
@@ -144,7 +153,7 @@ def lib():
     for name in ("univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_gemm", "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd",
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
                  "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score",
-                 "univl_sample_step", "univl_caption_overlap", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd"):
+                 "univl_sample_step", "univl_caption_overlap", "univl_ngram_df", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_caption_overlap_sizeof.argtypes = []
@@ -152,6 +161,16 @@ def lib():
     if L.univl_caption_overlap_sizeof() != C.sizeof(CaptionOverlap):
         raise RuntimeError("ABI mismatch for CaptionOverlap: library %d bytes, ctypes %d"
                            % (L.univl_caption_overlap_sizeof(), C.sizeof(CaptionOverlap)))
+    L.univl_ngram_df_sizeof.argtypes = []
+    L.univl_ngram_df_sizeof.restype = i32
+    if L.univl_ngram_df_sizeof() != C.sizeof(NgramDf):
+        raise RuntimeError("ABI mismatch for NgramDf: library %d bytes, ctypes %d" % (L.univl_ngram_df_sizeof(), C.sizeof(NgramDf)))
+    L.univl_ngram_df_tile.argtypes = []
+    L.univl_ngram_df_tile.restype = i32
+    if L.univl_ngram_df_tile() != NGRAM_DF_TILE:
+        raise RuntimeError("univl_ngram_df: the library's tile is %d keys, the binding's %d" % (L.univl_ngram_df_tile(), NGRAM_DF_TILE))
+    L.univl_ngram_df_ws_bytes.argtypes = [i32, i32]
+    L.univl_ngram_df_ws_bytes.restype = i64
     L.univl_vocab_ce_weighted_sizeof.argtypes = []
     L.univl_vocab_ce_weighted_sizeof.restype = i32
     if L.univl_vocab_ce_weighted_sizeof() != C.sizeof(VocabCEW):
@@ -245,7 +264,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_ce_weighted_sizeof", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

@@ -68,6 +68,80 @@ def document_frequency(sym, lens, ref_begin, ref_rows):
     return np.concatenate(keys), np.concatenate(cnts), begin
 
 
+class DocumentFrequency:
+    """CIDEr's document-frequency tables on the device, built there by ops.ngram_df (include/univl_hip.h: univl_ngram_df).  Owns keys
+    (int64 storage of the ascending uint64 keys), cnt (int32), begin (five HOST ints: the n-grams are entries begin[n-1] .. begin[n))
+    and n_docs; `.tables` is what ops.caption_overlap(tables=...) takes.  Building reads the five begin words and the status word on
+    the host, once; using the tables (rl.caption_rewards(metric="cider", df=...)) reads nothing."""
+
+    def __init__(self, keys, cnt, begin, n_docs):
+        self.keys, self.cnt, self.begin, self.n_docs = keys, cnt, [int(b) for b in begin], int(n_docs)
+
+    @property
+    def tables(self):
+        return (self.keys, self.cnt, self.begin, self.n_docs)
+
+    @property
+    def device(self):
+        return self.keys.device
+
+    @classmethod
+    def _build(cls, sym, lens, ref_begin, ref_rows, n_refs, n_docs):
+        """One ops.ngram_df launch, then the ONE host read: df_begin and the status word together."""
+        keys, cnt, begin_dev, status = ops.ngram_df(sym, lens, ref_begin, ref_rows, n_refs)
+        head = torch.cat([begin_dev, status]).cpu().tolist()
+        if head[5]:
+            raise RuntimeError("document frequency: the kernel flagged its input (status %d)" % head[5])
+        n = head[4]
+        return cls(keys[:n].clone(), cnt[:n].clone(), head[:5], n_docs)           # narrowed: the sufficient bound is not kept alive
+
+    @classmethod
+    def from_ids(cls, ref_ids, ref_len, device="cuda"):
+        """ref_ids [n, n_ref, T] / ref_len [n, n_ref] integer tensors, on the device or the host: one document per video, the layout
+        rl.caption_rewards takes its references in.  Positions past a length are not read."""
+        if ref_ids.dim() != 3 or min(ref_ids.shape) < 1 or tuple(ref_len.shape) != tuple(ref_ids.shape[:2]):
+            raise ValueError("document frequency: ref_ids of shape %s / ref_len of shape %s, expected [n, n_ref, T] / [n, n_ref], each "
+                             "dimension >= 1" % (tuple(ref_ids.shape), tuple(ref_len.shape)))
+        if ref_ids.is_floating_point() or ref_len.is_floating_point():
+            raise ValueError("document frequency: ref_ids / ref_len must be integer tensors")
+        n, n_ref, T = (int(v) for v in ref_ids.shape)
+        if T > OVERLAP_TMAX:
+            raise ValueError("document frequency: rows of %d positions; the kernel carries at most %d" % (T, OVERLAP_TMAX))
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("DocumentFrequency needs a HIP device (got %s, available: %s); there is no CPU fallback"
+                               % (dev, torch.cuda.is_available()))
+        with torch.cuda.device(dev):
+            sym = ref_ids.to(dev).reshape(n * n_ref, T).to(torch.int32).contiguous()
+            lens = ref_len.to(dev).reshape(n * n_ref).to(torch.int32).contiguous()
+            ref_begin = torch.arange(n + 1, dtype=torch.int32, device=dev) * n_ref
+            ref_rows = torch.arange(n * n_ref, dtype=torch.int32, device=dev)
+            return cls._build(sym, lens, ref_begin, ref_rows, n * n_ref, n)
+
+    @classmethod
+    def from_lists(cls, ref_lists, device="cuda"):
+        """ref_lists[i]: the integer rows of document i (Python lists; a document may be empty).  Packed as CaptionMetrics packs."""
+        if len(ref_lists) == 0:
+            raise ValueError("document frequency: at least one document is needed")
+        rows = [list(r) for refs in ref_lists for r in refs]
+        if not rows:
+            raise ValueError("document frequency: at least one row is needed")
+        sym, lens = _pack(rows)
+        ref_begin = np.zeros(len(ref_lists) + 1, dtype=np.int32)
+        ref_begin[1:] = np.cumsum([len(r) for r in ref_lists])
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("DocumentFrequency needs a HIP device (got %s, available: %s); there is no CPU fallback"
+                               % (dev, torch.cuda.is_available()))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        with torch.cuda.device(dev):
+            return cls._build(up(sym), up(lens), up(ref_begin), up(np.arange(len(rows), dtype=np.int32)), len(rows), len(ref_lists))
+
+    def to_host(self):
+        """(keys uint64 ascending, counts int32, begin [5]): document_frequency's form."""
+        return self.keys.cpu().numpy().view(np.uint64), self.cnt.cpu().numpy(), list(self.begin)
+
+
 def corpus_scores(guess, correct, hyp_len, ref_len, rouge_l, cider):
     """The corpus arithmetic, float64 on the host, from the per-item results (host arrays)."""
     out = {}
@@ -91,11 +165,16 @@ class CaptionMetrics:
     truncate: a row of more than 128 symbols is a ValueError by default; with truncate=True it is cut to its first 128 and a
     UserWarning says how many rows were cut (the launcher shim's stub asks for this: its call comes at the END of an evaluation epoch,
     after the whole test set was decoded, and one over-long caption must not cost the epoch).
+    df: "host" (the default) builds CIDEr's document-frequency tables with document_frequency (numpy), "device" with ops.ngram_df
+    (DocumentFrequency); the tables, and so the results, are the same.
     Arguments are validated on the host BEFORE a device is asked for, so malformed input is a ValueError with or without a GPU."""
 
-    def __init__(self, device="cuda", truncate=False, **nlgeval_keywords):
+    def __init__(self, device="cuda", truncate=False, df="host", **nlgeval_keywords):
+        if df not in ("host", "device"):
+            raise ValueError("CaptionMetrics: df=%r, expected 'host' (document_frequency, numpy) or 'device' (ops.ngram_df)" % (df,))
         self.device = torch.device(device)
         self.truncate = bool(truncate)
+        self.df = df
         self.last = None
 
     def compute_ids(self, hyp_ids, ref_ids):
@@ -121,13 +200,16 @@ class CaptionMetrics:
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("CaptionMetrics needs a HIP device (got %s, available: %s); there is no CPU fallback"
                                % (self.device, torch.cuda.is_available()))
-        keys, cnts, begin = document_frequency(sym, lens, ref_begin, ref_rows)
         dev = self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        tables = (up(keys.view(np.int64)), up(cnts), begin, items)
+        if self.df == "host":
+            keys, cnts, begin = document_frequency(sym, lens, ref_begin, ref_rows)
+            tables = (up(keys.view(np.int64)), up(cnts), begin, items)
         with torch.cuda.device(dev):
-            o = ops.caption_overlap(up(sym), up(lens), up(np.arange(items, dtype=np.int32)), up(ref_begin), up(ref_rows), n_refs,
-                                    tables=tables)
+            sym_d, lens_d, ref_begin_d, ref_rows_d = up(sym), up(lens), up(ref_begin), up(ref_rows)
+            if self.df == "device":
+                tables = DocumentFrequency._build(sym_d, lens_d, ref_begin_d, ref_rows_d, n_refs, items).tables
+            o = ops.caption_overlap(sym_d, lens_d, up(np.arange(items, dtype=np.int32)), ref_begin_d, ref_rows_d, n_refs, tables=tables)
         host = {k: v.cpu().numpy() for k, v in o.items() if v is not None}
         if int(host["status"][0]):
             raise RuntimeError("caption metrics: the kernel flagged its input (status %d)" % int(host["status"][0]))

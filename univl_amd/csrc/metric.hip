@@ -17,11 +17,12 @@
 // No float atomics (the one atomic is an integer OR into the status word), no dependence on the number of items.
 #include <math.h>
 #include "common.h"
+#include "ngram_rows.h"     // mask_n, stage_row: rows as packed n-gram words in LDS (shared with ngram_df.hip)
 #include "univl_hip.h"
 
 namespace {
 
-constexpr int MT = UNIVL_OVERLAP_TMAX;       // 128: two positions per lane
+constexpr int MT = NGRAM_MT;                 // 128: two positions per lane
 
 struct OverlapArgs {
     const int32_t* sym; long ld;
@@ -36,8 +37,6 @@ struct OverlapArgs {
     int32_t* status;
 };
 
-__device__ __forceinline__ uint64_t mask_n(int n) { return n == 4 ? ~0ULL : ((1ULL << (16 * n)) - 1ULL); }
-
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // a + b == b + a: every lane ends with the same bits
@@ -48,35 +47,6 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// Stages row `row` (clamped into the table) into s[0 .. MT + 3] (symbol + 1, 0 past the length) and k[0 .. MT) (packed words);
-// returns the clamped length.  Only positions below the length are read from memory.  Whole wave; ends with a barrier.
-__device__ __forceinline__ int stage_row(const OverlapArgs& a, int row, uint32_t* s, uint64_t* k, int lane, int& flags) {
-    if (row < 0 || row >= a.rows) { flags |= UNIVL_OVERLAP_BAD_ROW; row = row < 0 ? 0 : a.rows - 1; }
-    int L = a.len[row];
-    if (L < 0 || L > a.T) { flags |= UNIVL_OVERLAP_BAD_LEN; L = L < 0 ? 0 : a.T; }
-    const int32_t* x = a.sym + (long)row * a.ld;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int p = lane + 64 * h;
-        uint32_t v = 0;
-        if (p < L) {
-            int c = x[p];
-            if (c < 0 || c > UNIVL_OVERLAP_SYM_MAX) { flags |= UNIVL_OVERLAP_BAD_SYM; c = c < 0 ? 0 : UNIVL_OVERLAP_SYM_MAX; }
-            v = (uint32_t)c + 1u;
-        }
-        s[p] = v;
-    }
-    if (lane < 4) s[MT + lane] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int p = lane + 64 * h;
-        k[p] = (uint64_t)s[p] | ((uint64_t)s[p + 1] << 16) | ((uint64_t)s[p + 2] << 32) | ((uint64_t)s[p + 3] << 48);
-    }
-    __syncthreads();
-    return L;
 }
 
 // document frequency of an n-gram: binary search in the n-th segment of the sorted key table; 0 when absent

@@ -468,6 +468,38 @@ def caption_overlap(sym, length, hyp_row, ref_begin, ref_rows, n_refs, *, tables
     return out
 
 
+def ngram_df(sym, length, ref_begin, ref_rows, n_refs, *, capacity=None, status=None):
+    """The document-frequency tables of caption_overlap(tables=...) from token rows (include/univl_hip.h: univl_ngram_df); nothing is
+    read on the host.  sym: [rows, T] int32 (row stride >= T), length: [rows] int32; document i = rows ref_rows[ref_begin[i] ..
+    ref_begin[i + 1]); ref_begin [items + 1], ref_rows [n_refs] int32 device tensors; n_refs: the HOST's statement of ref_begin[items].
+    capacity: the length of the returned arrays (default n_refs * 4 T, which always suffices).  status: an int32 device word the flags
+    are OR-ed into (default: a fresh zero).  Returns (df_keys [capacity] int64 storage of the uint64 keys, df_cnt [capacity] int32,
+    df_begin [5] int32 ON THE DEVICE, status [1] int32); entries at and past df_begin[4] are not written."""
+    _require_gpu(sym, length, ref_begin, ref_rows, status)
+    assert sym.dtype == torch.int32 and sym.dim() == 2 and sym.stride(1) == 1
+    rows, T = sym.shape
+    items, dev, n_refs = ref_begin.numel() - 1, sym.device, int(n_refs)
+    for h, n in ((length, rows), (ref_begin, items + 1), (ref_rows, n_refs)):
+        assert h.dtype == torch.int32 and h.is_contiguous() and h.numel() == n
+    if capacity is None:
+        capacity = n_refs * 4 * T
+    need = int(_lib.lib().univl_ngram_df_ws_bytes(n_refs, T))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    df_keys = torch.empty(max(int(capacity), 0), dtype=torch.int64, device=dev)
+    df_cnt = torch.empty(max(int(capacity), 0), dtype=torch.int32, device=dev)
+    df_begin = torch.empty(5, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert status.dtype == torch.int32 and status.numel() == 1
+    d = _lib.NgramDf()
+    d.sym, d.ld, d.len, d.rows, d.T, d.items, d.n_refs = _p(sym), sym.stride(0), _p(length), rows, T, items, n_refs
+    d.ref_begin, d.ref_rows = _p(ref_begin), _p(ref_rows)
+    d.df_keys, d.df_cnt, d.df_begin, d.status, d.capacity = _p(df_keys), _p(df_cnt), _p(df_begin), _p(status), int(capacity)
+    d.ws, d.ws_bytes = _p(ws), ws.numel()
+    _lib.check(_lib.lib().univl_ngram_df(_BYREF(d), _stream()), "ngram_df")      # refuses what the workspace query refused, with its message
+    return df_keys, df_cnt, df_begin, status
+
+
 def consensus_pick(score):
     """score: [n_inst, n_samp] fp64 device tensor -> (pick [n_inst] int32, best [n_inst] fp64): the arg-max of every row, equal scores
     to the lower index (include/univl_hip.h: univl_consensus_pick)."""

@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from ._lib import OVERLAP_TMAX
+from .caption_metrics import DocumentFrequency
 from .score import beam_inputs_labels
 
 _LAYOUTS = {}
@@ -37,20 +38,31 @@ def _reward_layout(n, ns, n_ref, dev):
     return _LAYOUTS[key]
 
 
-def caption_rewards(sample_result, ref_ids, ref_len, eos, pad, metric="rouge_l", eos_dev=None, return_stats=False):
-    """The reward of every sampled caption: its ROUGE_L ("rouge_l") or sentence BLEU-4 ("bleu") against the references of its video,
-    [n, n_samp] fp64 on the device.  The samples are the rows of SampleResult.captions(eos, pad); ref_ids [n, n_ref, T] holds each
+def caption_rewards(sample_result, ref_ids, ref_len, eos, pad, metric="rouge_l", eos_dev=None, return_stats=False, df=None):
+    """The reward of every sampled caption: its ROUGE_L ("rouge_l"), sentence BLEU-4 ("bleu") or CIDEr-D ("cider") against the
+    references of its video, [n, n_samp] fp64 on the device.  The samples are the rows of SampleResult.captions(eos, pad); ref_ids [n, n_ref, T] holds each
     video's references and ref_len [n, n_ref] their lengths (integer tensors; positions past a length are not read).
 
     PIECE-level, as caption_metrics.consensus is: the symbols are piece ids after the cut, not words -- "##" continuation pieces count
     as symbols of their own -- so the numbers are not those of a word-level evaluation of the detokenised text.
 
+    metric="cider" needs df, a caption_metrics.DocumentFrequency on the samples' device (DocumentFrequency.from_ids over the training
+    set's references, built once): the kernel's clipped tf-idf with the Gaussian length penalty of sigma 6, idf from df.n_docs documents.
+    The values carry CIDEr's factor 10 -- `scale` of advantages / scst_step exists for that.  The other metrics ignore df.
+
     One ops.caption_overlap launch over the concatenated symbol matrix; nothing is read on the host (so the launch's status word is not
     looked at: piece ids above 65534 would be clamped).  return_stats: also the launch's whole output dictionary (guess / correct
     [n * n_samp, 4], hyp_len, ref_len, lcs, rouge_l, bleu, status)."""
-    if metric not in ("rouge_l", "bleu"):
-        raise ValueError("caption_rewards: metric=%r, expected 'rouge_l' or 'bleu'" % (metric,))
+    if metric not in ("rouge_l", "bleu", "cider"):
+        raise ValueError("caption_rewards: metric=%r, expected 'rouge_l', 'bleu' or 'cider'" % (metric,))
     tokens = sample_result.tokens
+    if metric == "cider":
+        if not isinstance(df, DocumentFrequency):
+            raise ValueError("caption_rewards: metric='cider' needs df, a caption_metrics.DocumentFrequency (got %s)" % type(df).__name__)
+        if df.n_docs < 1:
+            raise ValueError("caption_rewards: metric='cider' with a document-frequency table of %d documents" % df.n_docs)
+        if df.device != tokens.device:
+            raise ValueError("caption_rewards: metric='cider' with df on %s, the samples are on %s" % (df.device, tokens.device))
     if tokens.dim() != 3:
         raise ValueError("caption_rewards: sampled tokens of shape %s, expected [n, n_samp, Tmax]" % (tuple(tokens.shape),))
     n, ns, Tmax = tokens.shape
@@ -71,8 +83,9 @@ def caption_rewards(sample_result, ref_ids, ref_len, eos, pad, metric="rouge_l",
     sym[n * ns:, :T] = ref_ids.to(dev).reshape(n * n_ref, T)
     lens = torch.cat([cap_len.reshape(-1), ref_len.to(dev).reshape(-1).to(torch.int32)]).contiguous()
     hyp_row, ref_begin, ref_rows = _reward_layout(n, ns, n_ref, dev)
-    o = ops.caption_overlap(sym, lens, hyp_row, ref_begin, ref_rows, n * ns * n_ref, bleu=(metric == "bleu"))
-    r = (o["bleu"] if metric == "bleu" else o["rouge_l"]).view(n, ns)
+    o = ops.caption_overlap(sym, lens, hyp_row, ref_begin, ref_rows, n * ns * n_ref, bleu=(metric == "bleu"),
+                            tables=df.tables if metric == "cider" else None)
+    r = o[metric].view(n, ns)
     return (r, o) if return_stats else r
 
 
@@ -113,10 +126,10 @@ ScstResult.__doc__ = """What scst_step returns: loss (UniVL.forward's loss tenso
 is the sample.SampleResult they were computed from."""
 
 
-def scst_step(model, sampler, batch, ref_ids, ref_len, bos, eos, pad, seed, metric="rouge_l", baseline="loo", scale=1.0):
+def scst_step(model, sampler, batch, ref_ids, ref_len, bos, eos, pad, seed, metric="rouge_l", baseline="loo", scale=1.0, df=None):
     """One self-critical sequence-training step up to the loss.  batch: the five encoder inputs of UniVL.forward (a dict with
     input_ids, token_type_ids, attention_mask, video, video_mask, or that tuple); sampler: a sample.CaptionSampler of this model for
-    the batch's shape; ref_ids / ref_len as in caption_rewards; baseline / scale as in advantages.
+    the batch's shape; ref_ids / ref_len / metric / df as in caption_rewards (metric="cider" needs df); baseline / scale as in advantages.
 
       1. encoder features in evaluation form (UniVL.get_sequence_visual_output: no dropout; a pending optimizer update is applied first)
       2. sampler.sample(...): n_samp captions per video
@@ -144,7 +157,7 @@ def scst_step(model, sampler, batch, ref_ids, ref_len, bos, eos, pad, seed, metr
         vm = video_mask.reshape(B, video_mask.shape[-1])
         res = sampler.sample(seq, vis, am, vm, bos, eos, seed, n_active=None if B == sampler.n_inst else B)
         # ---- from here on: device work only
-        rewards = caption_rewards(res, ref_ids, ref_len, eos, pad, metric=metric, eos_dev=sampler.eos_dev)
+        rewards = caption_rewards(res, ref_ids, ref_len, eos, pad, metric=metric, eos_dev=sampler.eos_dev, df=df)
         adv = advantages(rewards, baseline=baseline, scale=scale)
         inputs, labels, mask = beam_inputs_labels(res.tokens, res.lengths, bos, eos, pad, res.tokens.shape[-1])
     loss = model(input_ids, token_type_ids, attention_mask, video, video_mask, input_caption_ids=inputs, decoder_mask=mask,
