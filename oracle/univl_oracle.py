@@ -284,7 +284,11 @@ def linear(x, P, prefix):
     return F.linear(x, P[prefix + ".weight"], P[prefix + ".bias"])
 
 
-def _drop(x, p, training):
+def _drop(x, p, training, drop=None, site=None):
+    """drop (optional): stands in for the dropout of every call site of a training forward -- drop(x, site) -> x with the caller's
+    own mask and scale applied (a test that knows the masks of another implementation); `site` names the call site.  None: torch's."""
+    if drop is not None:
+        return drop(x, site) if training else x
     return F.dropout(x, p, training) if (p > 0 and training) else x
 
 
@@ -294,7 +298,7 @@ def extended_mask(mask, dtype):
     return (1.0 - m) * -10000.0
 
 
-def attention_core(q, k, v, add_mask, nh, p_drop=0.0, training=False):
+def attention_core(q, k, v, add_mask, nh, p_drop=0.0, training=False, drop=None, site=None):
     """module_bert.py:166-197 (copies module_visual.py:165-181, module_cross.py:172-188,
     module_decoder.py:230-247): scores/sqrt(d) THEN + mask, softmax, dropout on probs, .V, merge heads."""
     B, Sq, H = q.shape
@@ -307,31 +311,31 @@ def attention_core(q, k, v, add_mask, nh, p_drop=0.0, training=False):
     scores = scores / math.sqrt(d)
     scores = scores + add_mask
     probs = torch.softmax(scores, dim=-1)
-    probs = _drop(probs, p_drop, training)
+    probs = _drop(probs, p_drop, training, drop, site)
     ctx = torch.matmul(probs, vl)
     return ctx.permute(0, 2, 1, 3).contiguous().view(B, Sq, H)
 
 
-def self_output(x, residual, P, prefix, p_drop, training):
+def self_output(x, residual, P, prefix, p_drop, training, drop=None):
     """module_bert.py:207-211: LN(dropout(dense(x)) + residual)."""
     h = linear(x, P, prefix + ".dense")
-    h = _drop(h, p_drop, training)
+    h = _drop(h, p_drop, training, drop, prefix)
     return layer_norm(h + residual, P[prefix + ".LayerNorm.weight"], P[prefix + ".LayerNorm.bias"])
 
 
-def encoder_layer(x, add_mask, P, prefix, cfg, training):
+def encoder_layer(x, add_mask, P, prefix, cfg, training, drop=None):
     """module_bert.py:253-264 (BertLayer) == VisualLayer == CrossLayer."""
     a = prefix + ".attention.self"
     q, k, v = linear(x, P, a + ".query"), linear(x, P, a + ".key"), linear(x, P, a + ".value")
-    ctx = attention_core(q, k, v, add_mask, cfg.num_attention_heads, cfg.dropout_prob, training)
-    att = self_output(ctx, x, P, prefix + ".attention.output", cfg.dropout_prob, training)
+    ctx = attention_core(q, k, v, add_mask, cfg.num_attention_heads, cfg.dropout_prob, training, drop, a + ".probs")
+    att = self_output(ctx, x, P, prefix + ".attention.output", cfg.dropout_prob, training, drop)
     inter = gelu(linear(att, P, prefix + ".intermediate.dense"))            # module_bert.py:233-236
-    return self_output(inter, att, P, prefix + ".output", cfg.dropout_prob, training)   # :246-250
+    return self_output(inter, att, P, prefix + ".output", cfg.dropout_prob, training, drop)   # :246-250
 
 
-def encoder(x, add_mask, P, prefix, n_layers, cfg, training):
+def encoder(x, add_mask, P, prefix, n_layers, cfg, training, drop=None):
     for i in range(n_layers):
-        x = encoder_layer(x, add_mask, P, f"{prefix}.encoder.layer.{i}", cfg, training)
+        x = encoder_layer(x, add_mask, P, f"{prefix}.encoder.layer.{i}", cfg, training, drop)
     return x
 
 
@@ -346,7 +350,7 @@ def normalize_video(video, P):
     return layer_norm(video, P["normalize_video.visual_norm2d.weight"], P["normalize_video.visual_norm2d.bias"])
 
 
-def bert_model(input_ids, token_type_ids, attention_mask, P, cfg, training):
+def bert_model(input_ids, token_type_ids, attention_mask, P, cfg, training, drop=None):
     """module_bert.py:417-447 + BertEmbeddings :132-146.  Pooler output is discarded by every caller
     (modeling.py:307) and is not computed here."""
     S = input_ids.size(1)
@@ -355,38 +359,38 @@ def bert_model(input_ids, token_type_ids, attention_mask, P, cfg, training):
          + P["bert.embeddings.position_embeddings.weight"][pos].unsqueeze(0)
          + P["bert.embeddings.token_type_embeddings.weight"][token_type_ids])
     e = layer_norm(e, P["bert.embeddings.LayerNorm.weight"], P["bert.embeddings.LayerNorm.bias"])
-    e = _drop(e, cfg.dropout_prob, training)
-    return encoder(e, extended_mask(attention_mask, e.dtype), P, "bert", cfg.text_num_hidden_layers, cfg, training)
+    e = _drop(e, cfg.dropout_prob, training, drop, "bert.embeddings")
+    return encoder(e, extended_mask(attention_mask, e.dtype), P, "bert", cfg.text_num_hidden_layers, cfg, training, drop)
 
 
-def visual_model(video, video_mask, P, cfg, training):
+def visual_model(video, video_mask, P, cfg, training, drop=None):
     """module_visual.py:397-425 + VisualEmbeddings :118-131."""
     S = video.size(1)
     e = linear(video, P, "visual.embeddings.word_embeddings")
     e = e + P["visual.embeddings.position_embeddings.weight"][torch.arange(S)].unsqueeze(0)
     e = layer_norm(e, P["visual.embeddings.LayerNorm.weight"], P["visual.embeddings.LayerNorm.bias"])
-    e = _drop(e, cfg.dropout_prob, training)
-    return encoder(e, extended_mask(video_mask, e.dtype), P, "visual", cfg.visual_num_hidden_layers, cfg, training)
+    e = _drop(e, cfg.dropout_prob, training, drop, "visual.embeddings")
+    return encoder(e, extended_mask(video_mask, e.dtype), P, "visual", cfg.visual_num_hidden_layers, cfg, training, drop)
 
 
-def cross_model(concat, concat_type, concat_mask, P, cfg, training):
+def cross_model(concat, concat_type, concat_mask, P, cfg, training, drop=None):
     """module_cross.py:364-394 + CrossEmbeddings :123-138 + CrossPooler :281-287 -> (last layer, pooled)."""
     S = concat.size(1)
     e = (concat + P["cross.embeddings.position_embeddings.weight"][torch.arange(S)].unsqueeze(0)
          + P["cross.embeddings.token_type_embeddings.weight"][concat_type])
     e = layer_norm(e, P["cross.embeddings.LayerNorm.weight"], P["cross.embeddings.LayerNorm.bias"])
-    e = _drop(e, cfg.dropout_prob, training)
-    out = encoder(e, extended_mask(concat_mask, e.dtype), P, "cross", cfg.cross_num_hidden_layers, cfg, training)
+    e = _drop(e, cfg.dropout_prob, training, drop, "cross.embeddings")
+    out = encoder(e, extended_mask(concat_mask, e.dtype), P, "cross", cfg.cross_num_hidden_layers, cfg, training, drop)
     pooled = torch.tanh(linear(out[:, 0], P, "cross.pooler.dense"))
     return out, pooled
 
 
-def get_cross_output(seq_out, vis_out, attention_mask, video_mask, P, cfg, training):
+def get_cross_output(seq_out, vis_out, attention_mask, video_mask, P, cfg, training, drop=None):
     """modeling.py:315-325."""
     concat = torch.cat((seq_out, vis_out), dim=1)
     cmask = torch.cat((attention_mask, video_mask), dim=1)
     ctype = torch.cat((torch.zeros_like(attention_mask), torch.ones_like(video_mask)), dim=1)
-    out, pooled = cross_model(concat, ctype, cmask, P, cfg, training)
+    out, pooled = cross_model(concat, ctype, cmask, P, cfg, training, drop)
     return out, pooled, cmask
 
 
@@ -400,13 +404,13 @@ def lm_head(x, P, prefix, tied_weight, transposed=False):
     return F.linear(h, tied_weight) + P[prefix + ".bias"]
 
 
-def decoder_model(input_ids, encoder_outs, answer_mask, encoder_mask, P, cfg, training):
+def decoder_model(input_ids, encoder_outs, answer_mask, encoder_mask, P, cfg, training, drop=None):
     """module_decoder.py:372-406 (+ embeddings :309-320, layer :287-292, attention :220-247, :274-277)."""
     S = input_ids.size(1)
     e = (P["bert.embeddings.word_embeddings.weight"][input_ids]
          + P["bert.embeddings.position_embeddings.weight"][torch.arange(S)].unsqueeze(0))
     e = layer_norm(e, P["decoder.embeddings.LayerNorm.weight"], P["decoder.embeddings.LayerNorm.bias"])
-    e = _drop(e, cfg.dropout_prob, training)
+    e = _drop(e, cfg.dropout_prob, training, drop, "decoder.embeddings")
     dt = e.dtype
     enc_add = extended_mask(encoder_mask, dt)
     ext_ans = answer_mask.unsqueeze(1).unsqueeze(2).to(dt)
@@ -418,14 +422,14 @@ def decoder_model(input_ids, encoder_outs, answer_mask, encoder_mask, P, cfg, tr
         p = f"decoder.decoder.layer.{i}"
         a = p + ".slf_attn.att"
         ctx = attention_core(linear(x, P, a + ".query"), linear(x, P, a + ".key"), linear(x, P, a + ".value"),
-                             slf, nh, cfg.dropout_prob, training)
-        s_out = self_output(ctx, x, P, p + ".slf_attn.output", cfg.dropout_prob, training)
+                             slf, nh, cfg.dropout_prob, training, drop, a + ".probs")
+        s_out = self_output(ctx, x, P, p + ".slf_attn.output", cfg.dropout_prob, training, drop)
         a = p + ".enc_attn.att"
         ctx = attention_core(linear(s_out, P, a + ".query"), linear(encoder_outs, P, a + ".key"),
-                             linear(encoder_outs, P, a + ".value"), enc_add, nh, cfg.dropout_prob, training)
-        d_out = self_output(ctx, s_out, P, p + ".enc_attn.output", cfg.dropout_prob, training)
+                             linear(encoder_outs, P, a + ".value"), enc_add, nh, cfg.dropout_prob, training, drop, a + ".probs")
+        d_out = self_output(ctx, s_out, P, p + ".enc_attn.output", cfg.dropout_prob, training, drop)
         inter = gelu(linear(d_out, P, p + ".intermediate.dense"))
-        x = self_output(inter, d_out, P, p + ".output", cfg.dropout_prob, training)
+        x = self_output(inter, d_out, P, p + ".output", cfg.dropout_prob, training, drop)
     return lm_head(x, P, "decoder.classifier.cls.predictions", P["bert.embeddings.word_embeddings.weight"])
 
 
@@ -444,7 +448,7 @@ def mean_pooling_for_similarity(seq_out, vis_out, attention_mask, video_mask):
     return text_out, video_out
 
 
-def cross_similarity(seq_out, vis_out, attention_mask, video_mask, P, cfg, training):
+def cross_similarity(seq_out, vis_out, attention_mask, video_mask, P, cfg, training, drop=None):
     """modeling.py:341-375: every (text, video) pair through the cross encoder, 5 text rows per chunk."""
     bt, st, h = seq_out.shape
     bv, sv, _ = vis_out.shape
@@ -457,15 +461,15 @@ def cross_similarity(seq_out, vis_out, attention_mask, video_mask, P, cfg, train
         ml = mrow.unsqueeze(1).repeat(1, bv, 1).view(-1, st)
         vr = vis_out.unsqueeze(0).repeat(n, 1, 1, 1).view(-1, sv, h)
         vmr = video_mask.unsqueeze(0).repeat(n, 1, 1).view(-1, sv)
-        _, pooled, _ = get_cross_output(sl, vr, ml, vmr, P, cfg, training)
+        _, pooled, _ = get_cross_output(sl, vr, ml, vmr, P, cfg, training, drop)
         rows.append(linear(pooled, P, "similarity_dense").squeeze(-1).view(n, bv))
     return torch.cat(rows, dim=0)
 
 
-def similarity_logits(seq_out, vis_out, attention_mask, video_mask, P, cfg, training, pretrain_joint=False):
+def similarity_logits(seq_out, vis_out, attention_mask, video_mask, P, cfg, training, pretrain_joint=False, drop=None):
     """modeling.py:377-391."""
     if (cfg.stage_two and not pretrain_joint) or cfg.sim_after_cross:
-        return cross_similarity(seq_out, vis_out, attention_mask, video_mask, P, cfg, training)
+        return cross_similarity(seq_out, vis_out, attention_mask, video_mask, P, cfg, training, drop)
     t, v = mean_pooling_for_similarity(seq_out, vis_out, attention_mask, video_mask)
     if not cfg.use_mil:
         t = F.normalize(t, dim=-1)
@@ -541,7 +545,7 @@ def mfm_loss(vis_cross_out, video, video_mask, video_labels_index, P):
 
 
 def get_sequence_visual_output(P, cfg, input_ids, token_type_ids, attention_mask, video, video_mask,
-                               training=False, shaped=False):
+                               training=False, shaped=False, drop=None):
     """modeling.py:299-313."""
     if not shaped:
         input_ids = input_ids.view(-1, input_ids.shape[-1])
@@ -549,28 +553,28 @@ def get_sequence_visual_output(P, cfg, input_ids, token_type_ids, attention_mask
         attention_mask = attention_mask.view(-1, attention_mask.shape[-1])
         video_mask = video_mask.view(-1, video_mask.shape[-1])
         video = normalize_video(video, P)
-    seq = bert_model(input_ids, token_type_ids, attention_mask, P, cfg, training)
-    vis = visual_model(video, video_mask, P, cfg, training)
+    seq = bert_model(input_ids, token_type_ids, attention_mask, P, cfg, training, drop)
+    vis = visual_model(video, video_mask, P, cfg, training, drop)
     return seq, vis
 
 
-def univl_forward(P, cfg: OracleConfig, batch, training=True, return_parts=False, sim_loss_fct=None):
+def univl_forward(P, cfg: OracleConfig, batch, training=True, return_parts=False, sim_loss_fct=None, drop=None):
     """modeling.py:188-271 -- returns the scalar training loss (all stages / losses).  sim_loss_fct: stands in for the reference's
     `self.loss_fct` (the loss on the similarity matrix, modeling.py:209 / :265) -- the cotangent fixtures of oracle/make_golden.py
-    replace it by sim -> (sim * W).sum()."""
+    replace it by sim -> (sim * W).sum().  drop: see _drop (None: torch's dropout at cfg.dropout_prob)."""
     v = lambda t: t.view(-1, t.shape[-1])
     input_ids, token_type_ids = v(batch["input_ids"]), v(batch["token_type_ids"])
     attention_mask, video_mask = v(batch["attention_mask"]), v(batch["video_mask"])
     video = normalize_video(batch["video"], P)
     seq, vis = get_sequence_visual_output(P, cfg, input_ids, token_type_ids, attention_mask, video, video_mask,
-                                          training, shaped=True)
+                                          training, shaped=True, drop=drop)
     parts = dict(sequence_output=seq, visual_output=vis)
     loss_fct, pretrain_sim_fct = _loss_fcts(cfg)
     if sim_loss_fct is not None:
         loss_fct = sim_loss_fct
     loss = 0.
     if cfg.stage_one:
-        sim = similarity_logits(seq, vis, attention_mask, video_mask, P, cfg, training)
+        sim = similarity_logits(seq, vis, attention_mask, video_mask, P, cfg, training, drop=drop)
         parts["sim_matrix"] = sim
         loss = loss + loss_fct(sim)
     if cfg.stage_two:
@@ -581,29 +585,29 @@ def univl_forward(P, cfg: OracleConfig, batch, training=True, return_parts=False
             masked_video = normalize_video(batch["masked_video"], P)
             vlabels = v(batch["video_labels_index"])
             seq_alm, vis_alm = get_sequence_visual_output(P, cfg, masked_text, token_type_ids, attention_mask,
-                                                          masked_video, video_mask, training, shaped=True)
-            cross_out, _, _ = get_cross_output(seq_alm, vis_alm, attention_mask, video_mask, P, cfg, training)
+                                                          masked_video, video_mask, training, shaped=True, drop=drop)
+            cross_out, _, _ = get_cross_output(seq_alm, vis_alm, attention_mask, video_mask, P, cfg, training, drop)
             seq_cross, vis_cross = torch.split(cross_out, [attention_mask.size(-1), video_mask.size(-1)], dim=1)
             alm_scores = lm_head(seq_cross, P, "cls.predictions", P["bert.embeddings.word_embeddings.weight"])
             parts["alm_loss"] = cross_entropy_ignore(alm_scores.view(-1, cfg.vocab_size), token_labels.view(-1))
             loss = loss + parts["alm_loss"]
             parts["nce_loss"] = mfm_loss(vis_cross, video, video_mask, vlabels, P)
             loss = loss + parts["nce_loss"]
-            sim_j = similarity_logits(seq, vis, attention_mask, video_mask, P, cfg, training, pretrain_joint=True)
+            sim_j = similarity_logits(seq, vis, attention_mask, video_mask, P, cfg, training, pretrain_joint=True, drop=drop)
             parts["sim_joint"] = sim_j
             loss = loss + pretrain_sim_fct(sim_j)
         if batch.get("input_caption_ids") is not None and (cfg.do_pretrain or cfg.task_type == "caption"):
             cap_in, dmask = v(batch["input_caption_ids"]), v(batch["decoder_mask"])
             s_in, v_in = (seq_alm, vis_alm) if cfg.do_pretrain else (seq, vis)
-            cross_out, _, cmask = get_cross_output(s_in, v_in, attention_mask, video_mask, P, cfg, training)
-            scores = decoder_model(cap_in, cross_out, dmask, cmask, P, cfg, training)
+            cross_out, _, cmask = get_cross_output(s_in, v_in, attention_mask, video_mask, P, cfg, training, drop)
+            scores = decoder_model(cap_in, cross_out, dmask, cmask, P, cfg, training, drop)
             parts["decoder_scores"] = scores
             cap_out = v(batch["output_caption_ids"])
             parts["decoder_loss"] = cross_entropy_ignore(scores.view(-1, cfg.vocab_size), cap_out.view(-1))
             loss = loss + parts["decoder_loss"]
         if cfg.do_pretrain or cfg.task_type == "retrieval":
             s_in, v_in = (seq_alm, vis_alm) if cfg.do_pretrain else (seq, vis)
-            sim_tv = similarity_logits(s_in, v_in, attention_mask, video_mask, P, cfg, training)
+            sim_tv = similarity_logits(s_in, v_in, attention_mask, video_mask, P, cfg, training, drop=drop)
             parts["sim_matrix"] = sim_tv
             loss = loss + loss_fct(sim_tv)
     if return_parts:

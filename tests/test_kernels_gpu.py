@@ -1233,6 +1233,29 @@ def test_attention_dropout_statistics():
     out2 = torch.zeros_like(out0)
     ops.attention_fwd(*a, out2, H * D, lse, p_drop=0.1, seed=7, offset=3)
     assert torch.equal(out1, out2)                      # same (seed, offset) -> same mask
+    # the forward's dropped probabilities, read out with V[b, key, h*64 + d] = (key == d): out[b, q, h*64 + key] = P_drop[b, h, q, key]
+    qkv_id = qkv.clone()
+    eye = torch.zeros(S, H, D, device=DEV)
+    eye[torch.arange(S), :, torch.arange(S)] = 1.0
+    qkv_id[:, 2 * H * D:] = eye.view(1, S, H * D).expand(B, S, H * D).reshape(B * S, H * D)
+    a_id = (_lib.DT_F32, B, H, S, S, (qkv_id, 0), 3 * H * D, (qkv_id, H * D), 3 * H * D, (qkv_id, 2 * H * D), 3 * H * D)
+    pd = torch.zeros_like(out0)
+    ops.attention_fwd(*a_id, pd, H * D, lse, p_drop=0.1, seed=7, offset=3)
+    pd = pd.view(B, S, H, D)[..., :S]                   # [b, q, h, key]
+    kept = float((pd != 0).float().mean())
+    assert abs(kept - 0.9) < 0.01, kept
+    # the backward regenerates the same mask: dV = P_drop^T dO with dO = 1 is, in every column d, the sum over q of P_drop[q, key]
+    ops.attention_fwd(*a, out1, H * D, lse, p_drop=0.1, seed=7, offset=3)
+    dqkv = torch.zeros_like(qkv)
+    ops.attention_bwd(*a, out1, H * D, lse, p_drop=0.1, seed=7, offset=3, dout=torch.ones_like(out1), lddo=H * D, dq=(dqkv, 0),
+                      lddq=3 * H * D, dk=(dqkv, H * D), lddk=3 * H * D, dv=(dqkv, 2 * H * D), lddv=3 * H * D)
+    dv = dqkv[:, 2 * H * D:].view(B, S, H, D)           # [b, key, h, d]
+    want = pd.sum(1).permute(0, 2, 1)                   # [b, key, h]
+    assert rel_err(dv, want[..., None].expand(B, S, H, D)) < tol(torch.float32)
+    # ... and not the mask of another stream offset
+    ops.attention_bwd(*a, out1, H * D, lse, p_drop=0.1, seed=7, offset=4, dout=torch.ones_like(out1), lddo=H * D, dq=(dqkv, 0),
+                      lddq=3 * H * D, dk=(dqkv, H * D), lddk=3 * H * D, dv=(dqkv, 2 * H * D), lddv=3 * H * D)
+    assert rel_err(dqkv[:, 2 * H * D:].view(B, S, H, D), want[..., None].expand(B, S, H, D)) > 10 * tol(torch.float32)
 
 
 # -------------------------------------------------------------------------------------------- embeddings

@@ -167,8 +167,10 @@ __device__ __forceinline__ float g256_gelu(float x) { float phi, E; g256_phi(x, 
 __device__ __forceinline__ float g256_gelu_grad(float x) { float phi, E; g256_phi(x, phi, E); return fmaf(x * 0.39894228040143267794f, E, phi); }
 
 // Counter-based RNG for dropout: one 32-bit draw per (seed, stream offset, element index); the same function
-// regenerates the mask in the backward pass.  (No bit-parity with torch's Philox stream is possible or required:
-// parity is checked at p = 0)
+// regenerates the mask in the backward pass.  (No bit-parity with torch's Philox stream is possible or required, SURVEY.md K18.  The
+// mask is a pure integer function of its three arguments, so the tests rebuild it on the host -- tests/dropout_ref.py restates mix32 and
+// dropout_scale -- and check every dropout path against fp64 at p > 0 under the identical mask: tests/test_dropout_parity_gpu.py.
+// Changing the hash, the keying or the threshold below changes that restatement with it.)
 __device__ __forceinline__ uint32_t mix32(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
     return (uint32_t)x;

@@ -694,7 +694,19 @@ class UniVL(UniVLPreTrainedModel):
             self._steps[key] = st
         return st
 
-    def _caption_weighted_shape(self, B, input_caption_ids, decoder_mask, output_caption_ids, caption_weight):
+    def dropout_offsets(self):
+        """{step key: {site name: dropout stream offset}} of the training steps built so far (steps.dropout_offsets): what a test needs,
+        with self._seed and self._seed_dev, to rebuild every dropout mask of a step on the host.  Read-only."""
+        from .steps import Step, dropout_offsets
+        return {key: dropout_offsets(st) for key, st in self._steps.items() if isinstance(st, Step) and st.cx.training}
+
+    def dropout_host_seeds(self):
+        """{step key: {site name: host seed}}: the seed each site's kernels add the device word self._seed_dev to (self._seed at the
+        embedding sites, 0 in the layer stacks -- steps._dropout_sites).  Read-only."""
+        from .steps import Step, dropout_host_seeds
+        return {key: dropout_host_seeds(st) for key, st in self._steps.items() if isinstance(st, Step) and st.cx.training}
+
+    def _caption_weighted_shape(self,B, input_caption_ids, decoder_mask, output_caption_ids, caption_weight):
         """forward(caption_weight=...): (n_cand, Wd) of a reward-weighted caption batch, or ValueError -- host-side checks on shapes and
         on the model's configuration only, before any device work."""
         if self.decoder is None:

@@ -804,6 +804,58 @@ class Step:
         return self.bwd[fresh]
 
 
+def _dropout_sites(st):
+    """{site name: (dropout stream offset, host seed)} of a built Step: the values its components drew from cx.sites (_SiteCounter)
+    and hand to the kernels, forward and backward -- read-only, for tests that rebuild the masks on the host.  Site names are the oracle's
+    (oracle/univl_oracle.py: _drop): "<stack>.encoder.layer.<l>.attention.self.probs" / ".attention.output" / ".output",
+    "decoder.decoder.layer.<l>.slf_attn.att.probs" / ".slf_attn.output" / ".enc_attn.att.probs" / ".enc_attn.output" / ".output",
+    "<bert|visual|cross|decoder>.embeddings".  A stack that runs more than once in the step has one set of sites per pass: the
+    masked-input encoder pass carries the suffix "@masked", the cross runs "@pairs" / "@rows" / "@heads" when there are several.
+    Host seed: the `seed` field of the site's kernel descriptors, to which the kernels add the device word cx.seed_dev.  The embedding
+    sites pass the model's seed; the layer stacks (engine.EncoderStack / DecoderStack) pass none, so their masks are keyed by the
+    device word alone."""
+    out = {}
+    seed = st.cx.seed
+
+    def stack(es, sfx):
+        for l, ws in enumerate(es.layers):
+            pre = "%s.encoder.layer.%d" % (es.prefix, l)
+            for name, off in zip((".attention.self.probs", ".attention.output", ".output"), ws["off"]):
+                out[pre + name + sfx] = (off, 0)
+
+    for enc, sfx in ((st.enc, ""), (st.enc_m, "@masked")):
+        if enc is None:
+            continue
+        if enc.text is not None:
+            stack(enc.text, sfx)
+            out["bert.embeddings" + sfx] = (enc.off_t, seed)
+        if enc.vis is not None:
+            stack(enc.vis, sfx)
+            out["visual.embeddings" + sfx] = (enc.off_v, seed)
+    runs = [(r, tag) for r, tag in ((st.run_pairs, "@pairs"), (st.run_rows, "@rows"), (st.run_heads, "@heads")) if r is not None]
+    for r, tag in runs:
+        sfx = tag if len(runs) > 1 else ""
+        stack(r.stack, sfx)
+        out["cross.embeddings" + sfx] = (r.off, seed)
+    if st.decoder is not None:
+        for l, ws in enumerate(st.decoder.stack.layers):
+            pre = "decoder.decoder.layer.%d" % l
+            for name, off in zip((".slf_attn.att.probs", ".slf_attn.output", ".enc_attn.att.probs", ".enc_attn.output", ".output"), ws["off"]):
+                out[pre + name] = (off, 0)
+        out["decoder.embeddings"] = (st.decoder.off, seed)
+    return out
+
+
+def dropout_offsets(st):
+    """{site name: dropout stream offset} (see _dropout_sites)."""
+    return {k: v[0] for k, v in _dropout_sites(st).items()}
+
+
+def dropout_host_seeds(st):
+    """{site name: host seed of the site's descriptors} (see _dropout_sites)."""
+    return {k: v[1] for k, v in _dropout_sites(st).items()}
+
+
 def _ddp_hook(cx, fl, model, kind):
     """Gradient exchange points for the data-parallel path (univl_amd.parallel): the hook is called by every encoder
     stack after each layer (backward order) and emits an eager all-reduce once UNIVL_BUCKET_MB of gradients are
