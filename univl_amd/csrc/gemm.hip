@@ -1053,9 +1053,12 @@ __global__ __launch_bounds__(256) void attn_bwd_odgrad_kernel(AttnFusedArgs a) {
 // forward.  A workgroup owns one (batch row, head): it multiplies the 64 x 192 block  x[rows of the sequence] . [W_q | W_k | W_v][head]^T
 // (+ bias), stores it to the qkv buffer the backward reads (same bf16 bits as the product's own epilogue), keeps it in the LDS images of
 // attn_fwd_body (FUSED) and runs the attention on it: the attention launch and its [tokens, 2304] read leave the forward chain.  The
-// launch carries BertAdam chunks like gemm_adam_kernel (workgroups behind the attention ones): the forward launches of a layer are
-// bound by the optimizer bytes that ride in them (16 us against 10 without), so the longer per-workgroup product (384 KB through
-// one compute unit instead of 192) hides behind them.  Eight waves (2 x 4: 32 x 48 outputs each) multiply, the first four attend.
+// launch carries BertAdam chunks like gemm_adam_kernel (workgroups behind the attention ones).  The longer per-workgroup product (384 KB
+// through one compute unit instead of 192) does NOT hide behind them: with ~216 chunks riding at 4 x 48 tokens the last rider ends
+// 14 - 15 us into the launch, and an attention workgroup that shares its unit with a rider ran 18.7 us (slowest 22.3; 11.6 / 15.0 us of
+// it the K loop, 8.0 without riders) -- the launch averaged 23.9 us in the step against 17.5 - 18.5 of the other carrying launches.
+// With the ring below (one workgroup per unit) the K loop is 9.4 / 10.0 us, the workgroup 17.2 / 17.9, the launch 19.4
+// (scripts/mb_trace_attn_fwd_qkv.py, profiles/r07a_*).  Eight waves (2 x 4: 32 x 48 outputs each) multiply, the first four attend.
 struct AttnFwdFusedArgs {
     UnivlAttention at;
     int Sk_pad;
@@ -1072,24 +1075,59 @@ struct AttnFwdFusedArgs {
 // workgroups per (batch row, head), one per block of 64 queries; each multiplies the 128 x 192 block of q | k | v of the WHOLE sequence (the
 // attention of its query block needs every key and value; the other block's q rows are recomputed -- at these sizes the product is a
 // latency chain, not MFMA time), stores the q | k | v rows of ITS OWN block to the qkv buffer (every row written once) and attends.
-template <bool NT, bool BIG>
-__global__ __launch_bounds__(512, 2) void attn_fwd_qkv_kernel(AttnFwdFusedArgs a, UnivlAdam ad, int c0, int c1) {
+//
+// NS = 2: two LDS stages, one computed on while the other is filled (64 KB; the 128-row form: 80 KB) -- two workgroups per compute unit.
+// NS = AttnFwdQkv::RING (64-row form only): the K loop is a RING of NS 64-deep stages (32 KB each) with counted waits: step t waits
+// until ITS stage has landed (`s_waitcnt vmcnt(n)`, n = the DMA instructions of the stages issued behind it), takes one raw barrier,
+// re-issues the slot step t - 1 has just read with stage t + NS - 1 and multiplies -- NS - 1 stages stay in flight across every barrier
+// instead of one.  Same tile images, same tile_mma walk over ascending 32-chunks, same accumulators: every output bit is the two-stage
+// loop's.  The ring's 128 KB are the request of EVERY workgroup of the launch: one workgroup per compute unit, riders included -- the
+// host takes the ring per launch, where that costs the riders less than it gives the product (univl_attention_fwd_fused).
+#ifndef UNIVL_ATTN_QKV_STAGES
+#define UNIVL_ATTN_QKV_STAGES 4      // A/B builds (univl_amd/build.py --variant): 2 = the two-stage loop everywhere; 3
+#endif
+struct AttnFwdQkv {
+    static constexpr int RING = UNIVL_ATTN_QKV_STAGES;
+    static constexpr int STAGE_BYTES = (64 + 192) * 64 * (int)sizeof(__bf16);
+    static constexpr int STAGE_BYTES_BIG = (128 + 192) * 64 * (int)sizeof(__bf16);
+    static constexpr int LOADS = STAGE_BYTES / 16 / 512;                 // LDS-DMA instructions of one stage, per wave
+    // dynamic LDS of the launch: the stages (the 128-row form: 80 KB -- the images of 128 positions, 57 KB, fit inside)
+    static constexpr size_t smem(bool big, int ns) { return (size_t)ns * (big ? STAGE_BYTES_BIG : STAGE_BYTES); }
+    // workgroups per compute unit the kernel is compiled for: what fits beside each other in 160 KB of LDS (the riders share the request)
+    static constexpr int wgs_per_cu(bool big, int ns) { return smem(big, ns) <= 80 * 1024 ? 2 : 1; }
+    static_assert(RING >= 2 && RING <= 4, "ring depth");
+};
+// every DMA instruction of this wave but the last n has landed; n is wave-uniform, a multiple of AttnFwdQkv::LOADS
+__device__ __forceinline__ void attn_qkv_wait_dma(const int n) {
+    static_assert(AttnFwdQkv::LOADS == 4 && AttnFwdQkv::RING <= 4, "the counted waits below: four DMA instructions per stage, at most two stages behind");
+    if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (n == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+template <bool NT, bool BIG, int NS>
+__global__ __launch_bounds__(512, AttnFwdQkv::wgs_per_cu(BIG, NS)) void attn_fwd_qkv_kernel(AttnFwdFusedArgs a, UnivlAdam ad, int c0, int c1) {
     const int w0 = blockIdx.x;
     if (w0 >= a.n_attn_pad) {
         const int nb = (int)gridDim.x - a.n_attn_pad;
+        UNIVL_TRACE_AT(0);
         for (int c = c0 + (w0 - a.n_attn_pad); c < c1; c += nb) adam_chunk<NT, 512>(ad, c);
+        UNIVL_TRACE_AT(3);
         return;
     }
     if (w0 >= a.n_attn) return;
     constexpr int ROWS = BIG ? 128 : 64, MI = ROWS / 32;
+    static_assert(NS == 2 || !BIG, "the 128-row form has two stages");
     using TileA = Tile<__bf16, false, ROWS, 64, 512>;
     using TileB = Tile<__bf16, false, 192, 64, 512>;
+    static_assert(TileA::PER_THREAD + TileB::PER_THREAD == AttnFwdQkv::LOADS || BIG, "DMA instructions per stage");
     const int bh = BIG ? (w0 >> 1) : w0, yblk = BIG ? (w0 & 1) : 0, b = bh / a.at.H, h = bh % a.at.H;
     const int HD3 = a.at.H * 64, Sq = a.at.Sq;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     const int wm0 = (wave >> 2) * (ROWS / 2), wn0 = (wave & 3) * 48;
+    UNIVL_TRACE_AT(0);
     unsigned char* sA = smem_raw;
-    unsigned char* sB = sA + 2 * TileA::BYTES;
+    unsigned char* sB = sA + NS * TileA::BYTES;
     f32x4_t acc[MI][3];
 #pragma unroll
     for (int ta = 0; ta < MI; ++ta)
@@ -1110,28 +1148,55 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_qkv_kernel(AttnFwdFusedArgs a
     int seg = 0, wrap = per;
     auto seg_x = [&](int s_) { return (a.X_lo != nullptr && s_ > 0 && s_ == nseg - 1) ? a.X_lo : a.X; };
     auto seg_w = [&](int s_) { return (a.W_lo != nullptr && s_ == 1) ? a.W_lo : a.W; };
-    TileA::issue(pa, sA, tid);
-    TileB::issue(pb, sB, tid);
-    TileA::advance(pa, 64);
-    TileB::advance(pb, 64);
-    __syncthreads();
-    for (int t = 0; t < nfull; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < nfull) {
-            if (t + 1 == wrap) {
-                TileA::advance(pa, (seg_x(seg + 1) - seg_x(seg)) - (long)a.K);
-                TileB::advance(pb, (seg_w(seg + 1) - seg_w(seg)) - (long)a.K);
-                ++seg;
-                wrap += per;
-            }
-            TileA::issue(pa, sA + (cur ^ 1) * TileA::BYTES, tid);
-            TileB::issue(pb, sB + (cur ^ 1) * TileB::BYTES, tid);
-            TileA::advance(pa, 64);
-            TileB::advance(pb, 64);
+    // stage s of the walk (s ascending: the pointers stand at it) into ring slot `slot`; a term boundary re-points the pointers first
+    auto issue_stage = [&](const int s, const int slot) {
+        if (s == wrap) {
+            TileA::advance(pa, (seg_x(seg + 1) - seg_x(seg)) - (long)a.K);
+            TileB::advance(pb, (seg_w(seg + 1) - seg_w(seg)) - (long)a.K);
+            ++seg;
+            wrap += per;
         }
-        tile_mma<__bf16, false, false, MI, 3, 2, TileA, TileB>(sA + cur * TileA::BYTES, sB + cur * TileB::BYTES, wm0, wn0, lane, acc);
+        TileA::issue(pa, sA + slot * TileA::BYTES, tid);
+        TileB::issue(pb, sB + slot * TileB::BYTES, tid);
+        TileA::advance(pa, 64);
+        TileB::advance(pb, 64);
+    };
+    if constexpr (NS == 2) {
+        issue_stage(0, 0);
         __syncthreads();
+        UNIVL_TRACE_AT(1);
+        for (int t = 0; t < nfull; ++t) {
+            const int cur = t & 1;
+            if (t + 1 < nfull) issue_stage(t + 1, cur ^ 1);
+            tile_mma<__bf16, false, false, MI, 3, 2, TileA, TileB>(sA + cur * TileA::BYTES, sB + cur * TileB::BYTES, wm0, wn0, lane, acc);
+            __syncthreads();
+        }
+    } else {
+        // prologue: the first NS - 1 stages (fewer where the walk is shorter than the ring)
+        int issued = 0;
+        for (; issued < NS - 1 && issued < nfull; ++issued) issue_stage(issued, issued);
+        int cur = 0, nxt = NS - 1;                              // ring slots of stage t and of stage t + NS - 1
+        for (int t = 0; t < nfull; ++t) {
+            // RAW: this wave's share of stage t has landed (the stages t + 1 .. issued - 1 may stay in flight), then the barrier: every
+            // wave's share has.  WAR: behind the same barrier every wave is done with step t - 1, whose slot stage t + NS - 1 takes.
+            // (lgkmcnt(0): the fragment reads of step t - 1 have returned, whatever the compiler moved behind the barrier)
+            attn_qkv_wait_dma((issued - 1 - t) * AttnFwdQkv::LOADS);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            if (t == 0) UNIVL_TRACE_AT(1);
+            if (issued < nfull) {
+                issue_stage(issued, nxt);
+                ++issued;
+            }
+            tile_mma<__bf16, false, false, MI, 3, 2, TileA, TileB>(sA + cur * TileA::BYTES, sB + cur * TileB::BYTES, wm0, wn0, lane, acc);
+            asm volatile("" ::: "memory");
+            cur = cur + 1 == NS ? 0 : cur + 1;
+            nxt = nxt + 1 == NS ? 0 : nxt + 1;
+        }
+        __syncthreads();            // every wave is done with the last stage (no DMA is in flight: the last wait was vmcnt(0))
     }
+    UNIVL_TRACE_AT(2);
     // epilogue: + bias -> bf16 -> the qkv buffer (rows of the sequence) and the LDS images of the attention body (rows beyond it: zero)
     const AttnFwdImages<__bf16> im(smem_raw, a.Sk_pad);
     using C = AttnCfg<__bf16>;
@@ -1154,6 +1219,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_qkv_kernel(AttnFwdFusedArgs a
             }
     }
     attn_fwd_body<__bf16, BIG ? 8 : 4, true>(a.at, a.Sk_pad, 0.125f, bh, yblk, smem_raw);
+    UNIVL_TRACE_AT(3);
 }
 
 // EXPERIMENTAL (UNIVL_ADAM_RIDE=1 with graphed.GraphedTrainStep(pipeline_optimizer=True)): a forward product and a range of BertAdam
@@ -1729,14 +1795,37 @@ extern "C" int univl_attention_bwd_fused(const UnivlAttention* at, const UnivlGe
 // [tokens, K] x [3 * H * 64, K] -> bf16 C16 with at->q / k / v = C16 + 0 / H * 64 / 2 * H * 64 and ldq = ldk = ldv = ldc, K a multiple
 // of 64, bias optional, no other epilogue.  Results (the qkv buffer, the attention output, the log-sum-exp) are bit-identical to
 // univl_gemm + univl_attention_fwd.  UNIVL_EUNSUPPORTED otherwise; adam may be NULL (chunk_count 0).
-static const size_t ATTN_FWD_FUSED_SMEM = 2 * (size_t)(64 + 192) * 64 * sizeof(__bf16);
-static const size_t ATTN_FWD_FUSED_SMEM_BIG = 2 * (size_t)(128 + 192) * 64 * sizeof(__bf16);      // 80 KB: the images of 128 positions (57 KB) fit inside
-static void attn_fwd_fused_allow_lds() {
-    static bool done_nt[UNIVL_MAX_DEVICES] = {}, done_t[UNIVL_MAX_DEVICES] = {}, done_ntb[UNIVL_MAX_DEVICES] = {}, done_tb[UNIVL_MAX_DEVICES] = {};
-    univl_allow_lds(attn_fwd_qkv_kernel<true, false>, ATTN_FWD_FUSED_SMEM, done_nt);
-    univl_allow_lds(attn_fwd_qkv_kernel<false, false>, ATTN_FWD_FUSED_SMEM, done_t);
-    univl_allow_lds(attn_fwd_qkv_kernel<true, true>, ATTN_FWD_FUSED_SMEM_BIG, done_ntb);
-    univl_allow_lds(attn_fwd_qkv_kernel<false, true>, ATTN_FWD_FUSED_SMEM_BIG, done_tb);
+//
+// One place for the form, the LDS size, the opt-in and the launch of an instantiation: AttnFwdQkv (beside the kernel) states the stages,
+// the kernel's launch bounds follow from the same numbers.  The ring's LDS request holds every workgroup of the launch -- the riders
+// too -- to one per compute unit.  It is taken where every attention workgroup gets a unit of its own and the riders pass in at most
+// two rounds over the units left (a rider workgroup takes ~8.5 us beside the others, an attention workgroup ~17): the step at 4 pairs,
+// 48 attention + ~216 rider workgroups on 256 units, 23.9 -> 19.4 us per launch.  A larger grid (16 pairs: 192 + 216) would queue the
+// riders behind the attention workgroups (measured: +0.8 % per step) and keeps the two-stage form, two workgroups per unit.
+template <bool NT, bool BIG, int NS> static void attn_fwd_qkv_allow_lds() {
+    static bool done[UNIVL_MAX_DEVICES] = {};
+    univl_allow_lds(attn_fwd_qkv_kernel<NT, BIG, NS>, AttnFwdQkv::smem(BIG, NS), done);
+}
+template <bool NT, bool BIG, int NS>
+static void attn_fwd_qkv_launch(const dim3 grid, hipStream_t stream, const AttnFwdFusedArgs& a, const AdamRange& r) {
+    attn_fwd_qkv_allow_lds<NT, BIG, NS>();
+    hipLaunchKernelGGL((attn_fwd_qkv_kernel<NT, BIG, NS>), grid, dim3(512), AttnFwdQkv::smem(BIG, NS), stream, a, r.adam, r.c0, r.c1);
+}
+static void attn_fwd_fused_allow_lds() {           // every instantiation (univl_gemm_rider_prime: outside any stream capture)
+    attn_fwd_qkv_allow_lds<true, false, 2>();
+    attn_fwd_qkv_allow_lds<false, false, 2>();
+    attn_fwd_qkv_allow_lds<true, false, AttnFwdQkv::RING>();
+    attn_fwd_qkv_allow_lds<false, false, AttnFwdQkv::RING>();
+    attn_fwd_qkv_allow_lds<true, true, 2>();
+    attn_fwd_qkv_allow_lds<false, true, 2>();
+}
+// compute units of the current device (0: unknown -- the ring is not taken)
+static int attn_fwd_fused_units() {
+    static int units[UNIVL_MAX_DEVICES] = {};
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= UNIVL_MAX_DEVICES) return 0;
+    if (units[dev] == 0 && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) units[dev] = n;
+    return units[dev];
 }
 
 extern "C" int univl_attention_fwd_fused(const UnivlAttention* at, const UnivlGemm* qkv, const UnivlAdam* adam, int32_t chunk_begin,
@@ -1773,12 +1862,14 @@ extern "C" int univl_attention_fwd_fused(const UnivlAttention* at, const UnivlGe
     a.n_attn = at->B * at->H * (big ? 2 : 1);
     a.n_attn_pad = (a.n_attn + 7) / 8 * 8;
     const AdamRange r = adam_range(adam, chunk_begin, chunk_count, max_blocks);
-    attn_fwd_fused_allow_lds();
     const dim3 grid(a.n_attn_pad + r.blocks);
+    const int free_units = attn_fwd_fused_units() - a.n_attn_pad;
+    const bool ring = !big && AttnFwdQkv::RING > 2 && free_units >= 0 && r.blocks <= 2 * free_units;
     adam_with_nt([&](auto nt) {
         constexpr bool NT = decltype(nt)::value;
-        if (big) hipLaunchKernelGGL((attn_fwd_qkv_kernel<NT, true>), grid, dim3(512), ATTN_FWD_FUSED_SMEM_BIG, stream, a, r.adam, r.c0, r.c1);
-        else hipLaunchKernelGGL((attn_fwd_qkv_kernel<NT, false>), grid, dim3(512), ATTN_FWD_FUSED_SMEM, stream, a, r.adam, r.c0, r.c1);
+        if (big) attn_fwd_qkv_launch<NT, true, 2>(grid, stream, a, r);
+        else if (ring) attn_fwd_qkv_launch<NT, false, AttnFwdQkv::RING>(grid, stream, a, r);
+        else attn_fwd_qkv_launch<NT, false, 2>(grid, stream, a, r);
     });
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
