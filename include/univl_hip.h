@@ -466,6 +466,61 @@ typedef struct UnivlSampleStep {
     void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch of >= R * UNIVL_SAMPLE_SLICES * (8 * k + 16) bytes                */
 } UnivlSampleStep;
 int univl_sample_step(const UnivlSampleStep* d, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- decoding constraints
+ * No repeated n-gram, a minimum length and a list of ids that are never emitted, applied to the score rows x [R, ld] fp32 of ONE
+ * position IN PLACE, entirely in device memory: one launch, no host involvement, no atomics, no workspace, capturable.  It goes
+ * between the launches that exist: behind univl_log_softmax_rows and in front of univl_beam_step (rows of log-probabilities), or
+ * behind the vocabulary classifier and in front of univl_sample_step (rows of raw logits).  One wave handles one row, its lanes
+ * stride over the prefix positions.  Every edit is x[r, v] = -inf by a plain vector store, so edits commute and there is no
+ * arithmetic to round; only columns v < V are ever written, columns V .. ld-1 are padding and stay bit-identical.
+ * PREFIX: p[0 .. t) are the tokens row r has emitted at positions 0 .. t-1 (the begin token is not among them), kept as rows of
+ * [R, Tmax] int32 arrays.  With last != NULL and t > 0 the launch first brings them up to date from the beam state
+ *   prefix_out[r, 0 .. t-1) = prefix_in[src[r], 0 .. t-1),   prefix_out[r, t-1] = (int32) last[r]
+ * (src: the row each beam continues from, what univl_beam_step writes and univl_gather_rows reads; NULL: the identity.  last: the
+ * tokens array of univl_beam_step.  A src entry outside [0, R) is clamped to that range, nothing is read out of it), and p is that
+ * row of prefix_out; the two arrays are used with alternating roles from position to position and must not overlap unless src ==
+ * NULL.  With last == NULL nothing is written to a prefix, prefix_out may be NULL and prefix_in must already hold t tokens per row:
+ * the tokens_out array of univl_sample_step is that array.
+ * A row with done[r / done_stride] != 0 keeps its row of x untouched; its prefix is still brought up to date, so that the buffers
+ * stay defined.  done_stride: n_bm for beams (done is per instance), 1 for the sampler (per row); done may be NULL (no row is done).
+ * Per live row, with n = ngram:
+ *   1. N-GRAM BLOCKING (n >= 1): for every j in [0, t-n+1) with p[j .. j+n-1) == p[t-n+1 .. t), x[r, p[j+n-1]] = -inf: a token that
+ *      would complete an n-gram the row already holds.  n == 1: every prefix token.  t < n-1: nothing.
+ *   2. MINIMUM LENGTH: if t < min_len and eos >= 0, x[r, eos] = -inf.
+ *   3. SUPPRESS LIST: x[r, v] = -inf for every v in suppress[0 .. n_suppress); duplicates are allowed.
+ * Ids outside [0, V) -- in a prefix, as eos, in the list -- are skipped, never written through.
+ * eos_dev: optional device word read INSTEAD of eos (as UnivlBeamStep.eos_dev).  params_dev: optional device words {ngram, min_len}
+ * read INSTEAD of the two fields, so that one captured hipGraph serves every setting of them (the pattern and the caveat of
+ * UnivlSampleStep.sampling_dev: the library cannot range-check device words, the caller does; an order outside
+ * [0, UNIVL_NGRAM_BLOCK_MAX] is clamped into it).
+ * The kernel does NOT check that a finite candidate remains: at least n_bm (univl_beam_step) or k (univl_sample_step) finite columns
+ * per live row are the caller's responsibility; otherwise the selection kernels' ordering of -inf applies and is meaningless.
+ * Range: R >= 1, 1 <= V <= ld, 0 <= t < Tmax, 0 <= ngram <= UNIVL_NGRAM_BLOCK_MAX, min_len >= 0, n_suppress >= 0, done_stride >= 1
+ * with done; x, prefix_in whenever a prefix is read (t > 0 and last, ngram or params_dev given), prefix_out whenever one is written
+ * (t > 0 and last given), suppress with n_suppress > 0 must not be NULL; prefix_in and prefix_out must not overlap while src is
+ * given; otherwise UNIVL_EINVAL and nothing is launched.  The struct is in neither numbered size table:
+ * univl_decode_constrain_sizeof states its size. */
+#define UNIVL_NGRAM_BLOCK_MAX 4
+typedef struct UnivlDecodeConstrain {
+    float* x; int64_t ld;            /* [R, ld] fp32 score rows, edited in place                                                  */
+    int32_t R, V;
+    int32_t t, Tmax;                 /* the position whose token is about to be chosen; columns of the prefix arrays              */
+    const int32_t* prefix_in;        /* [R, Tmax] int32                                                                           */
+    int32_t* prefix_out;             /* [R, Tmax] int32, columns 0 .. t-1 written when last is given                              */
+    const int32_t* src;              /* optional [R]: the row of prefix_in each row continues from (NULL: the identity)           */
+    const int64_t* last;             /* optional [R]: the token each row emitted at position t-1 (NULL: prefix_in is up to date)  */
+    const uint8_t* done;             /* optional [ceil(R / done_stride)]                                                          */
+    int32_t done_stride;
+    int32_t ngram;                   /* 0: off; 1 .. UNIVL_NGRAM_BLOCK_MAX: the blocked order                                     */
+    int32_t min_len;                 /* 0: off                                                                                    */
+    int32_t eos;                     /* the end token of the minimum length (negative: none)                                      */
+    const int32_t* eos_dev;          /* optional device word read INSTEAD of eos                                                  */
+    const int32_t* params_dev;       /* optional device {ngram, min_len} read INSTEAD of the two fields                           */
+    const int32_t* suppress;         /* [n_suppress] int32 ids on the device                                                      */
+    int32_t n_suppress, reserved;    /* reserved: 0                                                                               */
+} UnivlDecodeConstrain;
+int univl_decode_constrain_sizeof(void);
+int univl_decode_constrain(const UnivlDecodeConstrain* d, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------- caption metrics
  * N-gram overlap statistics of token rows, per item, in one launch with no host involvement (capturable): the integers BLEU is made
  * of, the longest common subsequences and ROUGE_L, and, given document-frequency tables, CIDEr.  An ITEM is one hypothesis row and a

@@ -118,6 +118,14 @@ class VocabCEW(C.Structure):
     _fields_ = VocabCE._fields_ + [("seq_weight", vp), ("seq_len", i32), ("reserved", i32)]
 
 
+class DecodeConstrain(C.Structure):
+    """include/univl_hip.h: UnivlDecodeConstrain.  Not in _STRUCTS: the library states its size through univl_decode_constrain_sizeof
+    (checked in lib())."""
+    _fields_ = [("x", vp), ("ld", i64), ("R", i32), ("V", i32), ("t", i32), ("Tmax", i32), ("prefix_in", vp), ("prefix_out", vp),
+                ("src", vp), ("last", vp), ("done", vp), ("done_stride", i32), ("ngram", i32), ("min_len", i32), ("eos", i32),
+                ("eos_dev", vp), ("params_dev", vp), ("suppress", vp), ("n_suppress", i32), ("reserved", i32)]
+
+
 ADV_LOO, ADV_GIVEN, ADV_NONFINITE = 0, 1, 1     # include/univl_hip.h: UNIVL_ADV_LOO, UNIVL_ADV_GIVEN, UNIVL_ADV_NONFINITE
 BEAM_MAX, BEAM_SLICES = 8, 8       # include/univl_hip.h: UNIVL_BEAM_MAX, UNIVL_BEAM_SLICES
 TOPK_MAX, TOPK_SLICES_MAX = 64, 256   # include/univl_hip.h: UNIVL_TOPK_MAX, UNIVL_TOPK_SLICES_MAX
@@ -125,6 +133,7 @@ SAMPLE_KMAX, SAMPLE_SLICES = 64, 8    # include/univl_hip.h: UNIVL_SAMPLE_KMAX, 
 OVERLAP_TMAX, OVERLAP_SYM_MAX = 128, 65534   # include/univl_hip.h: UNIVL_OVERLAP_TMAX, UNIVL_OVERLAP_SYM_MAX
 OVERLAP_BAD_LEN, OVERLAP_BAD_SYM, OVERLAP_BAD_ROW, OVERLAP_BAD_REFS = 1, 2, 4, 8
 NGRAM_DF_OVERFLOW, NGRAM_DF_TILE = 16, 4096   # include/univl_hip.h: UNIVL_NGRAM_DF_OVERFLOW, UNIVL_NGRAM_DF_TILE
+NGRAM_BLOCK_MAX = 4                # include/univl_hip.h: UNIVL_NGRAM_BLOCK_MAX
 
 _STRUCTS = [Gemm, LayerNorm, Attention, EmbedText, Pool, Seg, Adam, VocabCE, BeamStep, SimTopk, VocabScore, SampleStep]
 _lib = None
@@ -153,7 +162,8 @@ def lib():
     for name in ("univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_gemm", "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd",
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
                  "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score",
-                 "univl_sample_step", "univl_caption_overlap", "univl_ngram_df", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd"):
+                 "univl_sample_step", "univl_caption_overlap", "univl_ngram_df", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd",
+                 "univl_decode_constrain"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_caption_overlap_sizeof.argtypes = []
@@ -176,6 +186,11 @@ def lib():
     if L.univl_vocab_ce_weighted_sizeof() != C.sizeof(VocabCEW):
         raise RuntimeError("ABI mismatch for VocabCEW: library %d bytes, ctypes %d"
                            % (L.univl_vocab_ce_weighted_sizeof(), C.sizeof(VocabCEW)))
+    L.univl_decode_constrain_sizeof.argtypes = []
+    L.univl_decode_constrain_sizeof.restype = i32
+    if L.univl_decode_constrain_sizeof() != C.sizeof(DecodeConstrain):
+        raise RuntimeError("ABI mismatch for DecodeConstrain: library %d bytes, ctypes %d"
+                           % (L.univl_decode_constrain_sizeof(), C.sizeof(DecodeConstrain)))
     L.univl_caption_advantage.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, vp, vp]
     L.univl_caption_advantage.restype = i32
     L.univl_consensus_pick.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -264,7 +279,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_decode_constrain_sizeof", "univl_decode_constrain", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_ce_weighted_sizeof", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

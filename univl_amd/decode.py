@@ -79,9 +79,15 @@ class CaptionBeamSearch:
 
     NH = 12
 
-    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None):
+    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None, constraints=None):
         """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
-        None: the UNIVL_AB key `beam_step` (default device)."""
+        None: the UNIVL_AB key `beam_step` (default device).
+        constraints: a constrain.DecodeConstraints (no repeated n-gram, a minimum length, suppressed ids) or None.  The session binds
+        a copy (self.constraints) and adds ONE launch, univl_decode_constrain, to every position's plan between the log-softmax and
+        the beam step, so both beam_step modes decode under the same constraints, and step_logprobs returns constrained rows PROVIDED
+        positions are visited in order from 0 with `parents` given (the launch keeps each row's prefix up to date from them).  The
+        minimum length counts against the `eos` of decode().  Every live row must keep n_bm finite columns: the caller's condition.
+        None adds no launch, no buffer and no plan entry."""
         if model.decoder is None:
             raise RuntimeError("CaptionBeamSearch: this model was built without a decoder (stage one)")
         if beam_step is None:
@@ -93,6 +99,9 @@ class CaptionBeamSearch:
         self.use_graphs = bool(use_graphs)     # each step plan (one per position) is captured once into a hipGraph
         self.Tmax = Tmax = int(max_len or model.task_config.max_words)
         assert Tmax <= model.decoder_config.max_target_embeddings
+        if constraints is not None:          # validated against this session before any device work
+            constraints = constraints.bind(model.bert_config.vocab_size, Tmax, next(model.parameters()).device)
+        self.constraints = constraints
         model.flat.refresh_shadow()
         self.R = R = n_inst * n_bm
         self.V = V = model.bert_config.vocab_size
@@ -187,8 +196,22 @@ class CaptionBeamSearch:
     def _reorders(self, form):
         return True
 
+    def _prefix_buffers(self):
+        """Each row's emitted tokens, two [R, Tmax] int32 buffers used with parity t % 2 like self.cache (rows change places between
+        positions).  Allocated when the first plan that reorders rows is built -- plans are built outside any capture -- so a session
+        that never builds one (CaptionSampler's "sample" form reads its own tokens_out) has none.  Zero-filled: the rows of idle slots
+        are copied along, from defined memory."""
+        if not hasattr(self, "prefix"):
+            self.prefix = [torch.zeros(self.R, self.Tmax, dtype=torch.int32, device=self.cx.dev) for _ in range(2)]
+        return self.prefix
+
     def _plan_tail(self, pl, t, beam):
         pl.add_callable(lambda: ops.log_softmax_rows(self.head.logits, self.V))
+        if self.constraints is not None:
+            c, prefix = self.constraints, self._prefix_buffers()
+            pl.add("univl_decode_constrain", ops.decode_constrain_desc(
+                self.head.logits, self.V, t, prefix_in=prefix[(t + 1) % 2], prefix_out=prefix[t % 2], src=self.src, last=self.ids,
+                done=self.done, done_stride=self.n_bm, eos_dev=self.eos_dev, params_dev=c.params_dev, suppress=c.suppress_dev))
         if beam:
             pl.add("univl_beam_step", ops.beam_step_desc(
                 self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done, length=self.length,
@@ -196,10 +219,22 @@ class CaptionBeamSearch:
                 ws=self.beam_ws, eos_dev=self.eos_dev))
 
     # ------------------------------------------------------------------------------------------------- run
+    def set_constraints(self, ngram=None, min_len=None):
+        """Rewrite the blocked n-gram order and / or the minimum length of a session built with constraints (None: keep).  They are
+        device words that the captured launches read: nothing is captured again.  The suppress list is fixed for the session's life
+        (its length is baked into the captures); another list is another session."""
+        if self.constraints is None:
+            raise ValueError("set_constraints: this session was built with constraints=None; its plans carry no constraint launch")
+        self.constraints.set(ngram=ngram, min_len=min_len)
+
     @torch.no_grad()
     def step_logprobs(self, t, last_tokens, parents=None):
         """One cached decoder step: log-probabilities [R, V] of the token after position t, given each beam's token at
-        position t and (t > 0) the cache row it continues from.  Exposed for the parity tests."""
+        position t and (t > 0) the cache row it continues from.  Exposed for the parity tests.  In a session with constraints the
+        rows are the constrained ones when positions are visited in order from 0 with `parents` given (class __init__), under the
+        session's state AS IT STANDS: the launch reads self.done (a finished instance's rows come back unconstrained) and self.eos_dev
+        (the end token of the minimum length), which decode() sets and leaves as its last batch ended.  A caller that drives this
+        method itself sets them first: `session.done.zero_(); session.eos_dev.fill_(eos)`."""
         self.ids.copy_(last_tokens.reshape(-1))
         if t > 0:
             self.src.copy_(parents.reshape(-1).to(torch.int32))

@@ -131,14 +131,19 @@ class CaptionEvalResult:
 
 @torch.no_grad()
 def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, session=None, output_dir=None, nlg_eval=None,
-                 device="cuda"):
+                 device="cuda", constraints=None):
     """Caption evaluation over a loader (main_task_caption.py:490-618).  batches: the reference loader's 12-tuples (:504-506);
     tokenizer: any object with vocab["[CLS]"], vocab["[SEP]"], vocab["[PAD]"] and convert_ids_to_tokens.  One CaptionBeamSearch,
     sized by the first batch (or the `session` passed in), decodes every batch; a smaller batch runs with n_active, a larger one is
     a ValueError.  max_len: positions decoded per batch (default: the model's max_words, the reference's bound).  output_dir:
     hyp.txt and ref.txt are written there as :588-597 writes them.  nlg_eval: optional metric object (NLGEval).
+    constraints: a constrain.DecodeConstraints for the session this call builds; together with a `session` it is a ValueError, because
+    a session owns the constraints it was built with.
     Returns a CaptionEvalResult; for a stage-one model an empty one (float() == 0.0, :495) without decoding anything."""
     from .decode import CaptionBeamSearch
+    if session is not None and constraints is not None:
+        raise ValueError("eval_caption: constraints= with a supplied session; the session already owns its constraints "
+                         "(CaptionBeamSearch(..., constraints=))")
     if model._stage_one:
         return CaptionEvalResult([], [], [], torch.zeros(0, n_best), torch.zeros(0, dtype=torch.int32), None, None)
     bos, eos, pad = tokenizer.vocab["[CLS]"], tokenizer.vocab["[SEP]"], tokenizer.vocab["[PAD]"]
@@ -151,7 +156,7 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
             so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
             n = int(so.shape[0])
             if session is None:
-                session = CaptionBeamSearch(model, n, so.shape[1], vo.shape[1], n_bm=n_bm, max_len=max_len)
+                session = CaptionBeamSearch(model, n, so.shape[1], vo.shape[1], n_bm=n_bm, max_len=max_len, constraints=constraints)
             if n > session.n_inst:
                 raise ValueError("eval_caption: a batch of %d items does not fit the decoding session's %d instances"
                                  % (n, session.n_inst))

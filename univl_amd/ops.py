@@ -431,6 +431,42 @@ def sample_step(*a, **kw):
     _lib.check(_lib.lib().univl_sample_step(_BYREF(d), _stream()), "sample_step")
 
 
+def decode_constrain_desc(x, V, t, *, prefix_in=None, prefix_out=None, src=None, last=None, done=None, done_stride=1, ngram=0, min_len=0,
+                          eos=-1, eos_dev=None, params_dev=None, suppress=None, Tmax=None):
+    """x: [R, ld] fp32 view of one position's score rows (row stride ld >= V), edited in place; the rest as in include/univl_hip.h:
+    UnivlDecodeConstrain.  prefix_in / prefix_out: [R, Tmax] int32; src: int32 [R]; last: int64 [R]; done: uint8 [ceil(R / done_stride)];
+    params_dev: int32 [2] device {ngram, min_len}; eos_dev: int32 device word; suppress: int32 device ids (None: an empty list).  Tmax
+    is taken from the prefix arrays (give it when there are none).  Shapes and dtypes are checked here; the argument RANGE is the
+    library's to refuse."""
+    _require_gpu(x, prefix_in, prefix_out, src, last, done, eos_dev, params_dev, suppress)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    R = x.shape[0]
+    for h in (prefix_in, prefix_out):
+        if h is not None:
+            assert h.dtype == torch.int32 and h.dim() == 2 and h.is_contiguous() and h.shape[0] == R
+            assert Tmax is None or Tmax == h.shape[1]
+            Tmax = h.shape[1]
+    assert Tmax is not None, "decode_constrain: Tmax is needed without prefix arrays"
+    assert src is None or (src.dtype == torch.int32 and src.numel() == R and src.is_contiguous())
+    assert last is None or (last.dtype == torch.int64 and last.numel() == R and last.is_contiguous())
+    assert done is None or (done.dtype in (torch.uint8, torch.bool) and done_stride >= 1 and done.numel() * done_stride >= R)
+    assert eos_dev is None or eos_dev.dtype == torch.int32
+    assert params_dev is None or (params_dev.dtype == torch.int32 and params_dev.numel() == 2 and params_dev.is_contiguous())
+    assert suppress is None or (suppress.dtype == torch.int32 and suppress.dim() == 1 and suppress.is_contiguous())
+    d = _lib.DecodeConstrain()
+    d.x, d.ld, d.R, d.V, d.t, d.Tmax = _p(x), x.stride(0), R, V, t, Tmax
+    d.prefix_in, d.prefix_out, d.src, d.last = _p(prefix_in), _p(prefix_out), _p(src), _p(last)
+    d.done, d.done_stride, d.ngram, d.min_len, d.eos = _p(done), int(done_stride), int(ngram), int(min_len), int(eos)
+    d.eos_dev, d.params_dev = _p(eos_dev), _p(params_dev)
+    d.suppress, d.n_suppress = (_p(suppress), suppress.numel()) if suppress is not None and suppress.numel() else (None, 0)
+    return d
+
+
+def decode_constrain(*a, **kw):
+    d = decode_constrain_desc(*a, **kw)
+    _lib.check(_lib.lib().univl_decode_constrain(_BYREF(d), _stream()), "decode_constrain")
+
+
 def caption_overlap(sym, length, hyp_row, ref_begin, ref_rows, n_refs, *, tables=None, bleu=False, status=None):
     """N-gram overlap statistics per item (include/univl_hip.h: univl_caption_overlap), one launch, nothing read on the host.
     sym: [rows, T] int32 (row stride >= T), length: [rows] int32; hyp_row [items], ref_begin [items + 1], ref_rows [n_refs] int32 device

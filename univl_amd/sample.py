@@ -56,7 +56,12 @@ class CaptionSampler(CaptionBeamSearch):
     here are the defaults of sample(); they, the seed and the end token live in device words and never force a new capture.
     Partial batches: n_active as in CaptionBeamSearch; the rows of idle slots have `done` preset to 1."""
 
-    def __init__(self, model, n_inst, W, F, n_samp=5, max_len=None, top_k=50, temperature=1.0, top_p=1.0, use_graphs=True):
+    def __init__(self, model, n_inst, W, F, n_samp=5, max_len=None, top_k=50, temperature=1.0, top_p=1.0, use_graphs=True, constraints=None):
+        """constraints: a constrain.DecodeConstraints or None.  With one, univl_decode_constrain runs on the RAW logits between the
+        vocabulary classifier and univl_sample_step (each row's prefix is its row of tokens_out), so the draw is from the masked
+        distribution and tok_logprob / seq_logprob are log-probabilities UNDER THE MASKED LOGITS (renormalised over the unbanned columns),
+        not the unconstrained model's.  top_k <= the number of unbanned columns of every live row is the caller's condition.  step_logits
+        stays the unconstrained classifier output.  None adds no launch."""
         if not 1 <= int(n_samp) <= 8:
             raise ValueError("CaptionSampler: n_samp=%r, expected 1 .. 8" % (n_samp,))
         V = model.bert_config.vocab_size
@@ -66,7 +71,8 @@ class CaptionSampler(CaptionBeamSearch):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("CaptionSampler needs a model on a HIP device (got %s); there is no CPU fallback" % dev)
-        super().__init__(model, n_inst, W, F, n_bm=int(n_samp), max_len=max_len, use_graphs=use_graphs, beam_step="device")
+        super().__init__(model, n_inst, W, F, n_bm=int(n_samp), max_len=max_len, use_graphs=use_graphs, beam_step="device",
+                         constraints=constraints)
         self.n_samp, self.top_k, self.temperature, self.top_p = int(n_samp), int(top_k), float(temperature), float(top_p)
         R, Tmax, dev = self.R, self.Tmax, self.cx.dev
         # ---- sampling state (read and written by univl_sample_step), all per ROW
@@ -99,6 +105,11 @@ class CaptionSampler(CaptionBeamSearch):
             return
         if form != "sample":
             return super()._plan_tail(pl, t, form)
+        if self.constraints is not None:
+            c = self.constraints
+            pl.add("univl_decode_constrain", ops.decode_constrain_desc(
+                self.head.logits, self.V, t, prefix_in=self.tokens_out, done=self.row_done, done_stride=1, eos_dev=self.eos_dev,
+                params_dev=c.params_dev, suppress=c.suppress_dev))
         pl.add("univl_sample_step", ops.sample_step_desc(
             self.head.logits, self.V, self.top_k, t, done=self.row_done, length=self.row_length, ids=self.ids,
             tokens_out=self.tokens_out, tok_logprob=self.tok_lp, q_logprob=self.q_lp, seq_logprob=self.seq_lp,
