@@ -766,6 +766,55 @@ typedef struct UnivlVocabCEW {
 int univl_vocab_ce_weighted_sizeof(void);
 int univl_vocab_ce_weighted_fwd(const UnivlVocabCEW* desc, hipStream_t stream);
 int univl_vocab_ce_weighted_bwd(const UnivlVocabCEW* desc, hipStream_t stream);
+/* K16 smoothed form: torch.nn.CrossEntropyLoss(ignore_index, label_smoothing = eps) on x . table^T + bias, with the optional fp32 weight
+ * per caption of the weighted form -- the target of a counting row is (1 - eps) on its label plus eps / V on every one of the V columns.
+ * seq_weight may be NULL: seq_len is then ignored and every weight is 1.  With w_r = seq_weight[r / seq_len] (or 1), S_r = the sum of the
+ * row's V logits and nll_r = lse_r - logit_r[label_r] on counting rows:
+ *   univl_vocab_ce_smooth_fwd:
+ *     lse[rows], label_logit[rows]  as univl_vocab_ce_fwd: the same bits on the same operands (the tile epilogue's (max, sum exp) path and
+ *                    the row fold are the unsmoothed ones);
+ *     partial_sum[r][column tile] = the tile's share of S_r (columns >= V add 0): per lane over its ascending columns, the 16-lane xor
+ *                    steps, the column waves in ascending order; the row fold sums the slots lane-strided, then the xor steps;
+ *     rowloss[r]   = w_r * fma(1 - eps, nll_r, eps * (lse_r - S_r / V)) in fp32: S_r / V, the difference, the product with eps and
+ *                    1 - eps are each rounded, the sum of the two terms is one fused multiply-add, the weight multiplies last;
+ *                    0 on ignored rows;
+ *     scratch2[0]  = n_valid, independent of weights and eps;  scratch2[1] = the sum of rowloss;
+ *     loss         = (sum_r rowloss[r]) / n_valid in the fixed order of the unsmoothed loss kernel; NaN when no row counts.
+ *   univl_vocab_ce_smooth_bwd:
+ *     dlogits[r, col] = (exp(logit - lse_r) - (1 - eps) * [col == label_r] - eps / V) * (w_r * (gout / n_valid)) in the compute type; ignored
+ *     rows and rows whose weight is 0.0f are exact zeros; columns >= V stay untouched.  Call after the smoothed forward with the same
+ *     descriptor.  The two backward products that consume dlogits are the ones of univl_vocab_ce_bwd.
+ * With smoothing == 0 both entry points ARE the unsmoothed ones -- univl_vocab_ce_fwd / _bwd without weights, univl_vocab_ce_weighted_fwd /
+ * _bwd with them: the same launches on the same arguments, every output (loss, lse, rowloss, scratch2, dlogits) bit-identical, partial_sum
+ * neither read nor written.  Every reduction is in fixed order, there are no atomics: bit-reproducible in every mode, and a row's outputs
+ * do not depend on how many rows the problem has.
+ * Range: as univl_vocab_ce_fwd / _bwd, plus smoothing finite in [0, 1), partial_sum != NULL when smoothing > 0 (rows * slots floats), and
+ * with seq_weight != NULL a seq_len >= 1 dividing rows; otherwise UNIVL_EINVAL.
+ * The struct is in neither numbered size table: univl_vocab_ce_smooth_sizeof states its size. */
+typedef struct UnivlVocabCES {
+    int32_t dtype, rows, V, K;
+    const void* x; int64_t ldx;
+    const void* table; int64_t ldt;
+    const float* bias;             /* [V] or null */
+    const int64_t* labels;         /* [rows] */
+    int32_t ignore_index, slots;
+    float* partial;                /* [rows, slots, 2] */
+    float* label_logit;            /* [rows] */
+    float* lse;                    /* [rows] */
+    float* rowloss;                /* [rows] */
+    float* scratch2;               /* [0] n_valid, [1] sum of the row losses */
+    float* loss;                   /* [1] */
+    const float* gout;             /* backward: upstream gradient of the loss, one float on the device; null = 1 */
+    void* dlogits; int64_t lddl;   /* backward output */
+    const float* seq_weight;       /* [rows / seq_len] fp32, on the device; null = every weight 1 */
+    int32_t seq_len, reserved;     /* reserved: 0 */
+    float smoothing;               /* eps in [0, 1) */
+    int32_t reserved2;             /* 0 */
+    float* partial_sum;            /* [rows, slots]; may be null when smoothing == 0 */
+} UnivlVocabCES;
+int univl_vocab_ce_smooth_sizeof(void);
+int univl_vocab_ce_smooth_fwd(const UnivlVocabCES* desc, hipStream_t stream);
+int univl_vocab_ce_smooth_bwd(const UnivlVocabCES* desc, hipStream_t stream);
 /* K16 scoring form: teacher-forced SCORING on the tied vocabulary classifier -- the forward of K16 with the questions an evaluation asks of the
  * logits answered in the product's epilogue: for x [rows, K] . table [V, K]^T + bias (module_bert.py:327-330, decoder copy
  * module_decoder.py:180-183) and labels [rows], what log_softmax + gather + arg-max over the [rows, V] logits would give

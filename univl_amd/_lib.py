@@ -118,6 +118,12 @@ class VocabCEW(C.Structure):
     _fields_ = VocabCE._fields_ + [("seq_weight", vp), ("seq_len", i32), ("reserved", i32)]
 
 
+class VocabCES(C.Structure):
+    """include/univl_hip.h: UnivlVocabCES -- VocabCEW's fields, then the label smoothing and the per-tile row sums.  Not in _STRUCTS: the
+    library states its size through univl_vocab_ce_smooth_sizeof (checked in lib())."""
+    _fields_ = VocabCEW._fields_ + [("smoothing", f32), ("reserved2", i32), ("partial_sum", vp)]
+
+
 class DecodeConstrain(C.Structure):
     """include/univl_hip.h: UnivlDecodeConstrain.  Not in _STRUCTS: the library states its size through univl_decode_constrain_sizeof
     (checked in lib())."""
@@ -163,7 +169,7 @@ def lib():
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
                  "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score",
                  "univl_sample_step", "univl_caption_overlap", "univl_ngram_df", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd",
-                 "univl_decode_constrain"):
+                 "univl_decode_constrain", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_caption_overlap_sizeof.argtypes = []
@@ -186,6 +192,11 @@ def lib():
     if L.univl_vocab_ce_weighted_sizeof() != C.sizeof(VocabCEW):
         raise RuntimeError("ABI mismatch for VocabCEW: library %d bytes, ctypes %d"
                            % (L.univl_vocab_ce_weighted_sizeof(), C.sizeof(VocabCEW)))
+    L.univl_vocab_ce_smooth_sizeof.argtypes = []
+    L.univl_vocab_ce_smooth_sizeof.restype = i32
+    if L.univl_vocab_ce_smooth_sizeof() != C.sizeof(VocabCES):
+        raise RuntimeError("ABI mismatch for VocabCES: library %d bytes, ctypes %d"
+                           % (L.univl_vocab_ce_smooth_sizeof(), C.sizeof(VocabCES)))
     L.univl_decode_constrain_sizeof.argtypes = []
     L.univl_decode_constrain_sizeof.restype = i32
     if L.univl_decode_constrain_sizeof() != C.sizeof(DecodeConstrain):
@@ -280,7 +291,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
             "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_sample_step", "univl_decode_constrain_sizeof", "univl_decode_constrain", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
-            "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_ce_weighted_sizeof", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
+            "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_ce_weighted_sizeof", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "univl_vocab_ce_smooth_sizeof", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 
 

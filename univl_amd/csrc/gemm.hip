@@ -2138,7 +2138,7 @@ static int vocab_head_operands(const D* d, VocabCeArgs& a, const char* who) {
     return UNIVL_OK;
 }
 
-// D: UnivlVocabCE or UnivlVocabCEW (the same fields under the same names; the weighted form's own two are checked by its entry points)
+// D: UnivlVocabCE, UnivlVocabCEW or UnivlVocabCES (the same fields under the same names; what a form adds is checked by its entry points)
 template <typename D>
 static int vocab_ce_prepare(const D* d, VocabCeArgs& a, const char* who, bool bwd) {
     int rc = vocab_head_shape(d, who);
@@ -2152,10 +2152,12 @@ static int vocab_ce_prepare(const D* d, VocabCeArgs& a, const char* who, bool bw
     return UNIVL_OK;
 }
 
-extern "C" int univl_vocab_ce_fwd(const UnivlVocabCE* d, hipStream_t stream) {
-    UNIVL_ON_STREAM_DEVICE(stream);
+// The plain and the weighted form, stated once for every descriptor that leads with their fields (the smoothed form at eps = 0 IS one of
+// them: the same launches on the same arguments, so the same bits).
+template <typename D>
+static int vocab_ce_plain_fwd(const D* d, const char* who, hipStream_t stream) {
     VocabCeArgs a;
-    const int rc = vocab_ce_prepare(d, a, "univl_vocab_ce_fwd", false);
+    const int rc = vocab_ce_prepare(d, a, who, false);
     if (rc != UNIVL_OK) return rc;
     const int r2 = vocab_ce_launch<false, false>(d->dtype, a, stream);
     if (r2 != UNIVL_OK) return r2;
@@ -2166,18 +2168,29 @@ extern "C" int univl_vocab_ce_fwd(const UnivlVocabCE* d, hipStream_t stream) {
     return UNIVL_OK;
 }
 
-extern "C" int univl_vocab_ce_bwd(const UnivlVocabCE* d, hipStream_t stream) {
-    UNIVL_ON_STREAM_DEVICE(stream);
+template <typename D>
+static int vocab_ce_plain_bwd(const D* d, const char* who, hipStream_t stream) {
     VocabCeArgs a;
-    const int rc = vocab_ce_prepare(d, a, "univl_vocab_ce_bwd", true);
+    const int rc = vocab_ce_prepare(d, a, who, true);
     if (rc != UNIVL_OK) return rc;
     return vocab_ce_launch<true, false>(d->dtype, a, stream);
 }
 
+extern "C" int univl_vocab_ce_fwd(const UnivlVocabCE* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    return vocab_ce_plain_fwd(d, "univl_vocab_ce_fwd", stream);
+}
+
+extern "C" int univl_vocab_ce_bwd(const UnivlVocabCE* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    return vocab_ce_plain_bwd(d, "univl_vocab_ce_bwd", stream);
+}
+
 extern "C" int univl_vocab_ce_weighted_sizeof(void) { return (int)sizeof(UnivlVocabCEW); }
 
-// the weighted form's own checks + fields, after vocab_ce_prepare
-static int vocab_ce_weighted_prepare(const UnivlVocabCEW* d, VocabCeArgs& a, const char* who, bool bwd) {
+// the weighted form's own checks + fields, after vocab_ce_prepare (D: UnivlVocabCEW, or UnivlVocabCES with weights)
+template <typename D>
+static int vocab_ce_weighted_prepare(const D* d, VocabCeArgs& a, const char* who, bool bwd) {
     const int rc = vocab_ce_prepare(d, a, who, bwd);
     if (rc != UNIVL_OK) return rc;
     UNIVL_CHECK_ARG(d->seq_len >= 1 && d->rows % d->seq_len == 0, UNIVL_EINVAL, "%s: rows %d are not whole captions of seq_len %d", who, d->rows,
@@ -2187,10 +2200,10 @@ static int vocab_ce_weighted_prepare(const UnivlVocabCEW* d, VocabCeArgs& a, con
     return UNIVL_OK;
 }
 
-extern "C" int univl_vocab_ce_weighted_fwd(const UnivlVocabCEW* d, hipStream_t stream) {
-    UNIVL_ON_STREAM_DEVICE(stream);
+template <typename D>
+static int vocab_ce_weighted_fwd(const D* d, const char* who, hipStream_t stream) {
     VocabCeArgs a;
-    const int rc = vocab_ce_weighted_prepare(d, a, "univl_vocab_ce_weighted_fwd", false);
+    const int rc = vocab_ce_weighted_prepare(d, a, who, false);
     if (rc != UNIVL_OK) return rc;
     const int r2 = vocab_ce_launch<false, false>(d->dtype, a, stream);          // the unweighted tile kernel: the weight enters in the row fold
     if (r2 != UNIVL_OK) return r2;
@@ -2201,12 +2214,72 @@ extern "C" int univl_vocab_ce_weighted_fwd(const UnivlVocabCEW* d, hipStream_t s
     return UNIVL_OK;
 }
 
-extern "C" int univl_vocab_ce_weighted_bwd(const UnivlVocabCEW* d, hipStream_t stream) {
-    UNIVL_ON_STREAM_DEVICE(stream);
+template <typename D>
+static int vocab_ce_weighted_bwd(const D* d, const char* who, hipStream_t stream) {
     VocabCeArgs a;
-    const int rc = vocab_ce_weighted_prepare(d, a, "univl_vocab_ce_weighted_bwd", true);
+    const int rc = vocab_ce_weighted_prepare(d, a, who, true);
     if (rc != UNIVL_OK) return rc;
     return vocab_ce_launch<true, false, true>(d->dtype, a, stream);
+}
+
+extern "C" int univl_vocab_ce_weighted_fwd(const UnivlVocabCEW* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    return vocab_ce_weighted_fwd(d, "univl_vocab_ce_weighted_fwd", stream);
+}
+
+extern "C" int univl_vocab_ce_weighted_bwd(const UnivlVocabCEW* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    return vocab_ce_weighted_bwd(d, "univl_vocab_ce_weighted_bwd", stream);
+}
+
+extern "C" int univl_vocab_ce_smooth_sizeof(void) { return (int)sizeof(UnivlVocabCES); }
+
+// the smoothed form's own range, ahead of everything else; eps = 0 leaves the descriptor to the plain / the weighted form
+static int vocab_ce_smooth_range(const UnivlVocabCES* d, const char* who) {
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
+    UNIVL_CHECK_ARG(d->smoothing >= 0.0f && d->smoothing < 1.0f, UNIVL_EINVAL, "%s: smoothing %g is not in [0, 1)", who, (double)d->smoothing);
+    UNIVL_CHECK_ARG(d->smoothing == 0.0f || d->partial_sum != nullptr, UNIVL_EINVAL, "%s: null partial_sum with smoothing %g", who,
+                    (double)d->smoothing);
+    return UNIVL_OK;
+}
+
+// eps > 0: the checks of the form the weights select, then the smoothed form's own fields
+static int vocab_ce_smooth_prepare(const UnivlVocabCES* d, VocabCeArgs& a, const char* who, bool bwd) {
+    const int rc = d->seq_weight ? vocab_ce_weighted_prepare(d, a, who, bwd) : vocab_ce_prepare(d, a, who, bwd);
+    if (rc != UNIVL_OK) return rc;
+    if (!d->seq_weight) a.seq_len = 1;                    // never divided by: the weight is 1
+    a.partial_sum = d->partial_sum; a.smoothing = d->smoothing;
+    return UNIVL_OK;
+}
+
+extern "C" int univl_vocab_ce_smooth_fwd(const UnivlVocabCES* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    const char* who = "univl_vocab_ce_smooth_fwd";
+    int rc = vocab_ce_smooth_range(d, who);
+    if (rc != UNIVL_OK) return rc;
+    if (d->smoothing == 0.0f) return d->seq_weight ? vocab_ce_weighted_fwd(d, who, stream) : vocab_ce_plain_fwd(d, who, stream);
+    VocabCeArgs a;
+    rc = vocab_ce_smooth_prepare(d, a, who, false);
+    if (rc != UNIVL_OK) return rc;
+    rc = vocab_ce_launch<false, false, false, true>(d->dtype, a, stream);
+    if (rc != UNIVL_OK) return rc;
+    hipLaunchKernelGGL(vocab_ce_rows_smooth_kernel, dim3((d->rows + 3) / 4), dim3(256), 0, stream, d->partial, d->partial_sum, d->slots, a.nx,
+                       d->label_logit, d->labels, d->ignore_index, d->rows, d->V, d->smoothing, d->lse, d->rowloss, d->seq_weight, a.seq_len);
+    hipLaunchKernelGGL(vocab_ce_loss_kernel, dim3(1), dim3(256), 0, stream, d->rowloss, d->labels, d->ignore_index, d->rows, d->scratch2, d->loss);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_vocab_ce_smooth_bwd(const UnivlVocabCES* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    const char* who = "univl_vocab_ce_smooth_bwd";
+    int rc = vocab_ce_smooth_range(d, who);
+    if (rc != UNIVL_OK) return rc;
+    if (d->smoothing == 0.0f) return d->seq_weight ? vocab_ce_weighted_bwd(d, who, stream) : vocab_ce_plain_bwd(d, who, stream);
+    VocabCeArgs a;
+    rc = vocab_ce_smooth_prepare(d, a, who, true);
+    if (rc != UNIVL_OK) return rc;
+    return vocab_ce_launch<true, false, true, true>(d->dtype, a, stream);
 }
 
 extern "C" int univl_vocab_score(const UnivlVocabScore* d, hipStream_t stream) {

@@ -219,7 +219,8 @@ def eval_caption_loss(model, batches, *, session=None, device="cuda"):
     input_caption_ids, decoder_mask and output_caption_ids are elements 9, 10 and 11, labels of -1 do not count (modeling.py:253).
     One CaptionScorer, sized by the first batch (or the `session` passed in, n_cand = 1), scores every batch; a smaller batch runs
     with n_active, a larger one is a ValueError.  Each batch's three per-item results come to the host in one copy.
-    Returns a CaptionLossResult; for a stage-one model an empty one (loss NaN) without a launch."""
+    Returns a CaptionLossResult; for a stage-one model an empty one (loss NaN) without a launch.
+    The loss is the UNSMOOTHED likelihood whatever model.caption_label_smoothing is: the property shapes the training loss only."""
     from .score import CaptionScorer
     if model._stage_one:
         return CaptionLossResult([], [], [], None)

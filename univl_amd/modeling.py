@@ -403,6 +403,7 @@ class UniVL(UniVLPreTrainedModel):
         self.dp_capture = bool(_ab.get("dp_capture"))      # RCCL exchange captured into the step graph (False: host-issued collectives)
         self.auto_ride = _ab.get("adam_ride") != "0"       # optimizer.step() leaves its launch to the next forward (bf16, one process)
         self._operand_pairs = str(_ab.get("pairs"))        # see the `operand_pairs` property
+        self._caption_label_smoothing = 0.0                # see the `caption_label_smoothing` property
         self._stage_one, self._stage_two = True, False
         if _check_attr("stage_two", tc):
             self._stage_one, self._stage_two = False, tc.stage_two
@@ -604,6 +605,32 @@ class UniVL(UniVLPreTrainedModel):
                 self._flat.operand_pairs = value
                 self._steps = {}
 
+    SMOOTHED_KINDS = ("caption", "caption_weighted", "pretrain")      # the step kinds whose decoder loss takes caption_label_smoothing
+
+    @property
+    def caption_label_smoothing(self):
+        """Label smoothing eps of the caption decoder's cross entropy (torch.nn.CrossEntropyLoss(label_smoothing=eps); no counterpart in
+        the reference, which trains on hard targets): 0.0 (default) or 0 < eps < 1.  It applies to the training loss of the `caption`,
+        `caption_weighted` and `pretrain` steps -- in `pretrain` to the decoder term only, never to the MLM head -- through the smoothed
+        form of K16 (include/univl_hip.h: univl_vocab_ce_smooth_fwd / _bwd); at 0 the plans are the unsmoothed ones, launch for launch.
+        eval.eval_caption_loss and score.CaptionScorer report the unsmoothed likelihood whatever this is.  Setting it rebuilds the plans
+        on the next forward."""
+        return self._caption_label_smoothing
+
+    @caption_label_smoothing.setter
+    def caption_label_smoothing(self, value):
+        try:
+            value = float(value)
+        except (TypeError, ValueError):
+            raise ValueError("caption_label_smoothing: a number with 0 <= eps < 1 (got %r)" % (value,)) from None
+        if not 0.0 <= value < 1.0:                         # NaN fails both comparisons
+            raise ValueError("caption_label_smoothing: 0 <= eps < 1 (got %r)" % (value,))
+        if value != self._caption_label_smoothing:
+            self._flush_pending()
+            self._caption_label_smoothing = value
+            if self._flat is not None:
+                self._steps = {}
+
     def enable_data_parallel(self, process_group=None, broadcast=True, loopback=False, force=False, shard_optimizer=None):
         """Re-homes the reference's DDP wrap (main_task_retrieval.py:197-198) onto per-layer RCCL all-reduces of
         the flat gradient buffer, overlapped with backward (univl_amd.parallel).  Call after model.to(device) and
@@ -684,9 +711,17 @@ class UniVL(UniVLPreTrainedModel):
         return out
 
     # ---------------------------------------------------------------------------------------- execution
+    def _step_key(self, kind, B, W, F, n_cand=1, Wd=None):
+        """n_cand, Wd: part of a "caption_weighted" step's signature only.  A non-zero caption_label_smoothing is the last element of the
+        key of the kinds it applies to; at 0 the keys are the ones they were without the property."""
+        key = (kind, B, W, F, self.training) + ((n_cand, Wd) if kind == "caption_weighted" else ())
+        if kind in self.SMOOTHED_KINDS and self._caption_label_smoothing > 0:
+            key += (("smoothing", self._caption_label_smoothing),)
+        return key
+
     def _get_step(self, kind, B, W, F, n_cand=1, Wd=None):
         """n_cand, Wd: the captions per video and their positions, part of a "caption_weighted" step's signature only."""
-        key = (kind, B, W, F, self.training) + ((n_cand, Wd) if kind == "caption_weighted" else ())
+        key = self._step_key(kind, B, W, F, n_cand, Wd)
         st = self._steps.get(key)
         if st is None:
             from .steps import build_step

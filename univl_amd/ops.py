@@ -836,6 +836,36 @@ def vocab_ce_weighted_bwd(desc):
     _lib.check(_lib.lib().univl_vocab_ce_weighted_bwd(C.byref(desc), _stream()), "vocab_ce_weighted_bwd")
 
 
+def vocab_ce_smooth_desc(x, table, bias, labels, dlogits, V, smoothing, seq_weight=None, seq_len=None, ignore_index=-1):
+    """Descriptor of the smoothed form of K16 (include/univl_hip.h: UnivlVocabCES) + the buffers it owns: vocab_ce_desc's operands, the
+    label smoothing eps and, optionally, vocab_ce_weighted_desc's seq_weight [rows / seq_len] (None: every weight 1, seq_len is not
+    looked at).  partial_sum [rows, slots] is allocated whatever eps is.  Returns (desc, buffers).  Shapes and dtypes are checked here;
+    the argument RANGE -- eps in [0, 1) included -- is the library's to refuse."""
+    _require_gpu(x, table, bias, labels, dlogits, seq_weight)
+    if seq_weight is not None:
+        assert seq_weight.dtype == torch.float32 and seq_weight.is_contiguous()
+        assert seq_len is not None and (seq_len < 1 or seq_weight.numel() * seq_len >= x.shape[0])
+    d = vocab_head_desc(_lib.VocabCES, x, table, bias, labels, V, ignore_index)
+    rows, dev = d.rows, x.device
+    b = dict(partial=torch.empty(rows, max(d.slots, 1), 2, device=dev), partial_sum=torch.empty(rows, max(d.slots, 1), device=dev),
+             label_logit=torch.zeros(rows, device=dev), lse=torch.empty(rows, device=dev), rowloss=torch.empty(rows, device=dev),
+             scratch=torch.zeros(2, device=dev), loss=torch.zeros(1, device=dev), keep=(x, table, bias, labels, dlogits, seq_weight))
+    d.partial, d.label_logit, d.lse, d.rowloss = _p(b["partial"]), _p(b["label_logit"]), _p(b["lse"]), _p(b["rowloss"])
+    d.scratch2, d.loss, d.gout = _p(b["scratch"]), _p(b["loss"]), None
+    d.dlogits, d.lddl = _p(dlogits), dlogits.stride(0)
+    d.seq_weight, d.seq_len = _p(seq_weight), int(seq_len) if seq_weight is not None else 0
+    d.smoothing, d.partial_sum = float(smoothing), _p(b["partial_sum"])
+    return d, b
+
+
+def vocab_ce_smooth_fwd(desc):
+    _lib.check(_lib.lib().univl_vocab_ce_smooth_fwd(C.byref(desc), _stream()), "vocab_ce_smooth_fwd")
+
+
+def vocab_ce_smooth_bwd(desc):
+    _lib.check(_lib.lib().univl_vocab_ce_smooth_bwd(C.byref(desc), _stream()), "vocab_ce_smooth_bwd")
+
+
 def vocab_score_desc(x, table, bias, labels, V, seq_len, ignore_index=-1, out=None):
     """Descriptor of the scoring form of K16 (include/univl_hip.h: UnivlVocabScore) + the buffers it owns: x [rows, K], table [V(+pad), K]
     in the compute type, bias [V] fp32 or None, labels [rows] int64; rows = n_seq * seq_len.  out: optional dict of caller-owned output

@@ -72,7 +72,10 @@ class CaptionScorer:
     instances.  Slots [n_active, n_inst) are IDLE: their labels are set to -1 and their decoder masks and input ids to 0, the feature
     and mask slots are zero-filled once at construction and afterwards keep what an earlier batch left in them.  The launch shapes do
     not change, so a loader's short last batch replays the plan and hipGraph of the full ones.  No launch reduces across instances
-    or captions, so the active results do not depend on idle contents.  The result holds the first n_active instances only."""
+    or captions, so the active results do not depend on idle contents.  The result holds the first n_active instances only.
+
+    The scores are the model's UNSMOOTHED log-probabilities: model.caption_label_smoothing shapes the training loss only and is not
+    looked at here."""
 
     def __init__(self, model, n_inst, W, F, Wd, n_cand=1, use_graphs=True):
         if model.decoder is None:

@@ -477,13 +477,16 @@ class VocabHead:
     """BertLMPredictionHead tied to BERT's word table + CrossEntropyLoss(ignore_index=-1)
     (module_bert.py:299-330 / module_decoder.py:156-183; modeling.py:252-254, 273-276)."""
 
-    def __init__(self, cx, prefix, T, stream=0, transform_only=False, seq_len=None):
+    def __init__(self, cx, prefix, T, stream=0, transform_only=False, seq_len=None, smoothing=0.0):
         """transform_only: the buffers of the transform and the labels alone -- no dlogits [T, V] and no backward workspace (score.CaptionScorer
         feeds the transform's output to univl_vocab_score; build_transform is then the only builder to call).
         seq_len: the weighted form (univl_vocab_ce_weighted_fwd / _bwd) -- rows are whole captions of seq_len positions and self.weight
-        [T / seq_len] holds one fp32 weight per caption."""
+        [T / seq_len] holds one fp32 weight per caption.
+        smoothing: label smoothing eps of the loss; > 0 selects the smoothed form (univl_vocab_ce_smooth_fwd / _bwd), with or without
+        weights; 0 leaves the plans exactly as they are without it."""
         self.cx, self.prefix, self.T, self.sm = cx, prefix, T, stream
-        self.seq_len, self.weight = seq_len, None
+        self.seq_len, self.weight, self.smoothing = seq_len, None, float(smoothing)
+        assert 0.0 <= self.smoothing < 1.0, smoothing
         e, ct, bf = cx.e, cx.ct, cx.bf
         V = cx.model.bert_config.vocab_size
         self.V, self.ldv = V, (V + 7) // 8 * 8
@@ -511,10 +514,14 @@ class VocabHead:
 
     def _k16_desc(self, x16, bias, table):
         e, T = self.cx.e, self.T
-        d = ops.vocab_head_desc(_lib.VocabCE if self.weight is None else _lib.VocabCEW, x16, table, bias, self.labels, self.V)
+        cls = _lib.VocabCES if self.smoothing > 0 else (_lib.VocabCE if self.weight is None else _lib.VocabCEW)
+        d = ops.vocab_head_desc(cls, x16, table, bias, self.labels, self.V)
         if self.weight is not None:
             d.seq_weight, d.seq_len = self.weight.data_ptr(), self.seq_len
         self.k16 = k = dict(partial=e(T, d.slots, 2), label_logit=e(T), lse=e(T), rowloss=e(T))
+        if self.smoothing > 0:
+            k["partial_sum"] = e(T, d.slots)                 # a row's sum of logits, per 128-column tile
+            d.smoothing, d.partial_sum = self.smoothing, k["partial_sum"].data_ptr()
         d.partial, d.label_logit, d.lse, d.rowloss = (k["partial"].data_ptr(), k["label_logit"].data_ptr(), k["lse"].data_ptr(),
                                                       k["rowloss"].data_ptr())
         d.scratch2, d.loss = self.scratch.data_ptr(), self.loss.data_ptr()
@@ -541,6 +548,12 @@ class VocabHead:
         cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
         W32 = fl.w32
         self.build_transform(fwd, x16)
+        if self.smoothing > 0:
+            if not (with_loss and _ab.get("vocab_ce")):
+                raise RuntimeError("VocabHead: label smoothing exists only in K16 (univl_vocab_ce_smooth_fwd / _bwd); UNIVL_VOCAB_CE=0 "
+                                   "has no smoothed form")
+            fwd.add("univl_vocab_ce_smooth_fwd", self._k16_desc(self.h16, W32(n["bias"]), fl.wop(n["emb"])), sm)
+            return
         if self.weight is not None:
             if not (with_loss and _ab.get("vocab_ce")):
                 raise RuntimeError("VocabHead: per-caption weights exist only in K16 (univl_vocab_ce_weighted_fwd / _bwd); UNIVL_VOCAB_CE=0 "
@@ -565,7 +578,8 @@ class VocabHead:
             db = type(self.k16["desc"]).from_buffer_copy(self.k16["desc"])      # the forward's descriptor + the upstream gradient of this loss term
             db.gout = gout.data_ptr()
             self.k16["gout"] = gout
-            bwd.add("univl_vocab_ce_bwd" if self.weight is None else "univl_vocab_ce_weighted_bwd", db, sm)
+            bwd.add("univl_vocab_ce_smooth_bwd" if self.smoothing > 0 else
+                    ("univl_vocab_ce_bwd" if self.weight is None else "univl_vocab_ce_weighted_bwd"), db, sm)
         else:
             bwd.add_callable(lambda: ops.scale_ct(self.dlogits, gout), sm)
         # dh = dlogits . E contracts over the 30522-word vocabulary with only (T / 64) x 12 output tiles: unsplit, each workgroup
@@ -615,8 +629,9 @@ class RowFeatures:
 class DecoderRun:
     """DecoderModel.forward (module_decoder.py:372-406) on top of a row-wise CrossRun + the caption CE (modeling.py:246-254)."""
 
-    def __init__(self, cx, run, Wd, with_loss=True, weighted=False):
-        """weighted: the head's loss carries one weight per caption (VocabHead(seq_len=Wd)); load() then takes caption_weight."""
+    def __init__(self, cx, run, Wd, with_loss=True, weighted=False, smoothing=0.0):
+        """weighted: the head's loss carries one weight per caption (VocabHead(seq_len=Wd)); load() then takes caption_weight.
+        smoothing: label smoothing of the caption loss (VocabHead(smoothing=))."""
         self.cx, self.run, self.Wd = cx, run, Wd
         B = run.P
         self.B, self.T = B, B * Wd
@@ -627,7 +642,8 @@ class DecoderRun:
         self.e0_16 = e(T, H, dtype=ct) if bf else self.e0_32
         L = cx.model.decoder_config.num_decoder_layers
         self.stack = DecoderStack(fl, L, B, Wd, run.S, self.dmask, run.cmask, cx.p, cx.seed_dev, cx.sites, stream=run.sm)
-        self.head = VocabHead(cx, "decoder.classifier.cls.predictions", T, stream=run.sm, seq_len=Wd if weighted else None)
+        self.head = VocabHead(cx, "decoder.classifier.cls.predictions", T, stream=run.sm, seq_len=Wd if weighted else None,
+                              smoothing=smoothing)
         self.off = cx.sites.next()
         self.dout = e(T, H)
         self.with_loss = with_loss
@@ -931,7 +947,7 @@ def build_step(model, kind, B, W, F, training, n_cand=1, Wd=None):
     elif kind == "caption":
         st.run_rows = CrossRun(cx, enc, rows, rows)
         st.run_rows.build_forward(fwd)
-        st.decoder = DecoderRun(cx, st.run_rows, W)
+        st.decoder = DecoderRun(cx, st.run_rows, W, smoothing=model.caption_label_smoothing)
         st.decoder.build_forward(fwd)
         st.loss_terms.append(st.decoder.loss)
     elif kind == "caption_weighted":
@@ -945,7 +961,8 @@ def build_step(model, kind, B, W, F, training, n_cand=1, Wd=None):
         rows_rep = [i for i in range(B) for _ in range(st.n_cand)]
         st.run_rows = CrossRun(cx, enc, rows_rep, rows_rep)
         st.run_rows.build_forward(fwd)
-        st.decoder = DecoderRun(cx, st.run_rows, W if Wd is None else int(Wd), weighted=True)
+        st.decoder = DecoderRun(cx, st.run_rows, W if Wd is None else int(Wd), weighted=True,
+                                smoothing=model.caption_label_smoothing)
         st.decoder.build_forward(fwd)
         st.loss_terms.append(st.decoder.loss)
     elif kind in ("pretrain", "pretrain_nocap"):
@@ -962,7 +979,7 @@ def build_step(model, kind, B, W, F, training, n_cand=1, Wd=None):
         if kind == "pretrain":                                   # modeling.py:238-254: only when captions are given
             st.run_rows = CrossRun(cx, enc_m, rows, rows)        # _get_decoder_score re-runs the cross encoder (:404)
             st.run_rows.build_forward(fwd)
-            st.decoder = DecoderRun(cx, st.run_rows, W)
+            st.decoder = DecoderRun(cx, st.run_rows, W, smoothing=model.caption_label_smoothing)   # the decoder term only: never the MLM head
             st.decoder.build_forward(fwd)
             st.loss_terms.append(st.decoder.loss)
         st.run_pairs = CrossRun(cx, enc_m, [a for a, _ in pairs], [b for _, b in pairs])   # alignment (:258-267)
