@@ -265,12 +265,14 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float* logits, long l
     }
     const float mx = block_max(m, red);
     s = block_sum(m == -INFINITY ? 0.f : s * expf(m - mx), red);
-    const float lse = mx + logf(s);
+    // log_softmax as (x - mx) - log(s), not x - (mx + log(s)): that sum rounds at the magnitude of mx, and a row whose label holds
+    // nearly all the mass (softmax - 1 near 0) loses the leading digits of its gradient to it
+    const float ls = logf(s);
     const float inv = 1.0f / nvalid;
     for (int j = threadIdx.x; j < nv; j += 256) {
         const float4 v = x4[j];
         const int j0 = 4 * j;
-        float r[4] = {expf(v.x - lse), expf(v.y - lse), expf(v.z - lse), expf(v.w - lse)};
+        float r[4] = {expf((v.x - mx) - ls), expf((v.y - mx) - ls), expf((v.z - mx) - ls), expf((v.w - mx) - ls)};
         if (lab >= j0 && lab < j0 + 4) r[lab - j0] -= 1.0f;
         if (sizeof(T) == 2) {
             bf16x4_t w;
@@ -281,10 +283,10 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float* logits, long l
         }
     }
     for (int j = nv * 4 + threadIdx.x; j < V; j += 256)
-        d[j] = from_f32<T>((expf(x[j] - lse) - (j == lab ? 1.0f : 0.0f)) * inv);
+        d[j] = from_f32<T>((expf((x[j] - mx) - ls) - (j == lab ? 1.0f : 0.0f)) * inv);
     if (threadIdx.x == 0) {
-        if (rowloss) rowloss[row] = (lse - x[lab]) * inv;
-        else unsafeAtomicAdd(scal + 1, (lse - x[lab]) * inv);
+        if (rowloss) rowloss[row] = (ls - (x[lab] - mx)) * inv;
+        else unsafeAtomicAdd(scal + 1, (ls - (x[lab] - mx)) * inv);
     }
 }
 
@@ -322,16 +324,18 @@ __global__ __launch_bounds__(256) void mfm_kernel(const float* logits, long ld, 
     float s = 0.f;
     for (int j = threadIdx.x; j < n; j += 256) s += expf(x[j] + (1.0f - mi * (float)vmask[j]) * -1e8f - mx);
     s = block_sum(s, red);
-    const float lse = mx + logf(s);
+    // log_softmax as (v - mx) - log(s), never through mx + log(s): in a row whose own frame is padded every entry sits near -1e8,
+    // where the fp32 spacing is 8 and the sum would swallow log(s)
+    const float ls = logf(s);
     const float inv = 1.0f / nvalid;
     for (int j = threadIdx.x; j < n; j += 256) {
         const float v = x[j] + (1.0f - mi * (float)vmask[j]) * -1e8f;
-        d[j] = (expf(v - lse) - (j == i ? 1.0f : 0.0f)) * inv;
+        d[j] = (expf((v - mx) - ls) - (j == i ? 1.0f : 0.0f)) * inv;
     }
     if (threadIdx.x == 0) {
         const float vii = xii + (1.0f - mi * mi) * -1e8f;
-        if (rowloss) rowloss[i] = (lse - vii) * inv;
-        else unsafeAtomicAdd(scal + 1, (lse - vii) * inv);
+        if (rowloss) rowloss[i] = (ls - (vii - mx)) * inv;
+        else unsafeAtomicAdd(scal + 1, (ls - (vii - mx)) * inv);
     }
 }
 

@@ -185,13 +185,13 @@ __global__ __launch_bounds__(256) void pool_pair_bwd_kernel(UnivlPool a, UnivlPo
 }
 
 // ----------------------------------------------------------------------------------------------- losses
+// The diagonal collects minus the weight of every active hinge of its row (first relu) and of its column (second relu).  Thread i
+// walks row i and column i in index order after the main pass: a fixed order, so the weighted form (two distinct non-integer weights)
+// gives the same bits every run in either mode.  (LDS float atomics summed it in arrival order before.)
 __global__ __launch_bounds__(256) void maxmargin_kernel(const float* x, int n, int ld, float margin, const float* w,
                                                         float* loss, float* dx) {
-    extern __shared__ float diag_acc[];   // [n] gradient accumulated on the diagonal
     __shared__ float red[4];
     const float inv = 1.0f / ((float)n * (float)n);
-    for (int i = threadIdx.x; i < n; i += 256) diag_acc[i] = 0.f;
-    __syncthreads();
     float acc = 0.f;
     for (int e = threadIdx.x; e < n * n; e += 256) {
         const int i = e / n, j = e % n;
@@ -199,14 +199,24 @@ __global__ __launch_bounds__(256) void maxmargin_kernel(const float* x, int n, i
         const float a = margin + v - x[(long)i * ld + i];     // relu(margin + x - d.view(-1,1))
         const float b = margin + v - x[(long)j * ld + j];     // relu(margin + x - d.view(1,-1))
         float g = 0.f;
-        if (a > 0.f) { acc += wi * a; g += wi; atomicAdd(&diag_acc[i], -wi); }
-        if (b > 0.f) { acc += wi * b; g += wi; atomicAdd(&diag_acc[j], -wi); }
+        if (a > 0.f) { acc += wi * a; g += wi; }
+        if (b > 0.f) { acc += wi * b; g += wi; }
         dx[(long)i * ld + j] = g * inv;
     }
     const float total = block_sum(acc, red);
     if (threadIdx.x == 0) loss[0] = total * inv;
     __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 256) dx[(long)i * ld + i] += diag_acc[i] * inv;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float d = x[(long)i * ld + i];
+        float s = 0.f;
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const float wr = w ? w[(long)i * n + j] : 1.0f, wc = w ? w[(long)j * n + i] : 1.0f;
+            if (margin + x[(long)i * ld + j] - d > 0.f) s += wr;
+            if (margin + x[(long)j * ld + i] - d > 0.f) s += wc;
+        }
+        dx[(long)i * ld + i] -= s * inv;
+    }
 }
 
 __global__ __launch_bounds__(256) void crossen_kernel(const float* x, int n, int ld, float* loss, float* dx) {
@@ -238,20 +248,22 @@ __global__ __launch_bounds__(256) void milnce_kernel(const float* x, int bs, int
     for (int bb = 0; bb < bs; ++bb) {
         const int i = bb * np + np / 2;
         const int lo = bb * np, hi = lo + np;
-        float mx = -INFINITY;
+        // the numerator's block has a maximum of its own: with un-normalised similarities its entries can lie more than 100 below
+        // the row's maximum, where expf(. - mx) is 0 and the logarithm of their sum would be -inf
+        float mx = -INFINITY, mxn = -INFINITY;
         for (int j = threadIdx.x; j < 2 * n; j += 256) {
             float v;
-            if (j < n) v = x[(long)j * ld + i];
+            if (j < n) { v = x[(long)j * ld + i]; if (j >= lo && j < hi) mxn = fmaxf(mxn, v); }
             else { const int jj = j - n; v = (jj >= lo && jj < hi) ? -INFINITY : x[(long)i * ld + jj]; }
             mx = fmaxf(mx, v);
         }
         mx = block_max(mx, red);
+        mxn = block_max(mxn, red);
         float sden = 0.f, snum = 0.f;
         for (int j = threadIdx.x; j < 2 * n; j += 256) {
             if (j < n) {
-                const float e = expf(x[(long)j * ld + i] - mx);
-                sden += e;
-                if (j >= lo && j < hi) snum += e;
+                sden += expf(x[(long)j * ld + i] - mx);
+                if (j >= lo && j < hi) snum += expf(x[(long)j * ld + i] - mxn);
             } else {
                 const int jj = j - n;
                 if (!(jj >= lo && jj < hi)) sden += expf(x[(long)i * ld + jj] - mx);
@@ -259,14 +271,14 @@ __global__ __launch_bounds__(256) void milnce_kernel(const float* x, int bs, int
         }
         sden = block_sum(sden, red);
         snum = block_sum(snum, red);
-        total += logf(sden) - logf(snum);
+        total += (mx + logf(sden)) - (mxn + logf(snum));
         const float wgt = 1.0f / (float)bs;
         __syncthreads();
         for (int j = threadIdx.x; j < 2 * n; j += 256) {
             if (j < n) {
-                const float e = expf(x[(long)j * ld + i] - mx);
-                float g = e / sden;
-                if (j >= lo && j < hi) g -= e / snum;
+                const float v = x[(long)j * ld + i];
+                float g = expf(v - mx) / sden;
+                if (j >= lo && j < hi) g -= expf(v - mxn) / snum;
                 dx[(long)j * ld + i] += wgt * g;
             }
         }
@@ -373,7 +385,7 @@ extern "C" int univl_maxmargin_loss(const float* sim, int32_t n, int32_t ld, flo
                                     float* dsim, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     UNIVL_CHECK_ARG(sim && loss && dsim && n > 0 && n <= 8192 && ld >= n, UNIVL_EINVAL, "univl_maxmargin_loss: bad argument");
-    hipLaunchKernelGGL(maxmargin_kernel, dim3(1), dim3(256), n * sizeof(float), stream, sim, n, ld, margin, weight, loss, dsim);
+    hipLaunchKernelGGL(maxmargin_kernel, dim3(1), dim3(256), 0, stream, sim, n, ld, margin, weight, loss, dsim);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
