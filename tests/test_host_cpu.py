@@ -752,3 +752,68 @@ def test_plan_ops_still_read_by_position_like_the_tuples_they_replace():
     assert isinstance(pln[0], G * 2) and pln[1] is ln and pln[2] is ctr and len(pln) == 3
     with pytest.raises(IndexError):
         ops_[0][5]
+
+
+def test_head_transform_and_loss_forms_are_stated_once():
+    """steps.HeadTransform serves the MLM head and the visual head of the pretrain step: the two transform launches of the forward and the
+    transform's backward tail (LayerNorm backward, gelu_bwd, weight gradient with its dbias, dgrad) carry the same names and, pointers
+    and the row count apart, the same descriptor fields in both heads -- M / N / K, the flags, the ld* fields, which optional pointers
+    are null -- except `accumulate` on the last dgrad.  steps.VocabHead.FORMS: each loss form's plans hold exactly one launch of its
+    forward and one of its backward entry point, the latter on a descriptor of the table's class."""
+    import ctypes as C
+    from univl_amd.steps import HeadTransform, VocabHead, build_step
+
+    def step(kind, smoothing=0.0, **kw):
+        m, _ = _model("bf16", text_num_hidden_layers=1, cross_num_hidden_layers=1, decoder_num_hidden_layers=1, stage_two=True,
+                      **(dict(do_pretrain=True, use_mil=True) if kind == "pretrain" else dict(task_type="caption")))
+        m._flat, m._seed_dev = FlatParams(list(m.named_parameters()), "cpu", torch.bfloat16), torch.zeros(1, dtype=torch.int64)
+        m.train()
+        m.caption_label_smoothing = smoothing
+        st = build_step(m, kind, 2, 16, 16, True, **kw)
+        return st, st.fwd, st.backward_plan(True)
+
+    def fields(d, T, last_dgrad=False):
+        """the descriptor without its pointer values (null or not stays) and with the row count named, not numbered"""
+        out = []
+        for name, ctype in d._fields_:
+            v = getattr(d, name)
+            if ctype is C.c_void_p:
+                v = v is None
+            elif name in ("M", "N", "K", "rows") and v == T:
+                v = "T"
+            elif name == "flags" and last_dgrad:
+                v &= ~_lib.GEMM_ACCUM
+            out.append((name, v))
+        return type(d).__name__, out
+
+    def transform_launches(tr, fwd, bwd):
+        assert isinstance(tr, HeadTransform)
+        f = [i for i, op in enumerate(fwd.ops) if op.descs and getattr(op.descs[0], "C32", None) == tr.hy.data_ptr()]
+        b = [i for i, op in enumerate(bwd.ops) if op.name == "univl_layernorm_bwd" and op.descs[0].dout == tr.dh.data_ptr()]
+        assert len(f) == 1 and len(b) == 1
+        f, b = fwd.ops[f[0]:f[0] + 2], bwd.ops[b[0]:b[0] + 4]
+        assert f[1].descs[0].x == f[1].descs[0].y == tr.hy.data_ptr() and b[2].descs[0].A == b[3].descs[0].A == tr.du.data_ptr()
+        return ([(op.name, fields(op.descs[0], tr.T)) for op in f],
+                [(op.name, fields(op.descs[0], tr.T, op is b[-1]) if op.descs else None) for op in b])
+
+    st, fwd, bwd = step("pretrain")
+    mlm, vis = st.heads.mlm.transform, st.heads.vtransform
+    assert st.heads.mlm.h16 is mlm.h16 and st.heads.mlm.h32 is mlm.h32
+    f_mlm, b_mlm = transform_launches(mlm, fwd, bwd)
+    f_vis, b_vis = transform_launches(vis, fwd, bwd)
+    assert [n for n, _ in f_mlm] == ["univl_gemm", "univl_layernorm_fwd"] and f_mlm == f_vis
+    assert [n for n, _ in b_mlm] == ["univl_layernorm_bwd", "<lambda>", "univl_gemm", "univl_gemm"] and b_mlm == b_vis
+    assert dict(f_mlm[0][1][1])["M"] == "T" and dict(b_mlm[2][1][1])["K"] == "T" and dict(b_mlm[3][1][1])["M"] == "T"
+
+    assert st.heads.mlm.form == "plain" and set(VocabHead.FORMS) == {"plain", "weighted", "smoothed"}
+    builds = dict(plain=("caption", 0.0, {}), weighted=("caption_weighted", 0.0, dict(n_cand=3, Wd=16)), smoothed=("caption", 0.1, {}))
+    entries = [e for form in VocabHead.FORMS.values() for e in form[1:3]]
+    assert len(set(entries)) == 6
+    for form, (cls, fwd_entry, bwd_entry, _, _) in VocabHead.FORMS.items():
+        kind, smoothing, kw = builds[form]
+        st, fwd, bwd = step(kind, smoothing, **kw)
+        assert st.decoder.head.form == form
+        names = [op.name for op in fwd.ops] + [op.name for op in bwd.ops]
+        assert [n for n in names if n in entries] == [fwd_entry, bwd_entry]
+        db = [op.descs[0] for op in bwd.ops if op.name == bwd_entry]
+        assert len(db) == 1 and type(db[0]) is cls and type(st.decoder.head.k16["desc"]) is cls

@@ -390,13 +390,30 @@ class Launch(Op):
 
 class _Carrier(Launch):
     """A launch that does other work beside its dense contractions (optimizer chunks, a LayerNorm, the attention around a projection):
-    replayed as the contractions alone.  `gemms`: where among args their descriptors sit."""
+    replayed as the contractions alone.  `gemms`: where among args their descriptors sit.  A form's entry point (`entry`) takes (*args,
+    *chunks, dry_run, stream): args as pack builds them from its descriptors, chunks only where it can carry some (`idle`: none ride)."""
     __slots__ = ()
-    gemms = slice(0, 1)
+    gemms, idle = slice(0, 1), ()
 
-    def part(self, riders):
-        """(first, count) of the optimizer chunks this launch carries in this run, or None."""
-        return None if riders is None or self.key is None else riders.take(self.key, self.slot, self.nslots)
+    def __init__(self, kind, stream, descs, args, key=None, slot=0, nslots=1):
+        Launch.__init__(self, kind, self.entry, stream, descs, args, key, slot, nslots)
+
+    def whole(self, h, chunks=None):
+        """The launch with everything it carries but the chunks, or with `chunks`."""
+        return self.fn(*self.args, *(chunks or self.idle), 0, h)
+
+    def enqueue(self, h, riders=None):
+        return self.whole(h, self.chunks(riders))
+
+    @classmethod
+    def accepts(cls, *descs):
+        """Does the library carry this form for these descriptors (pack's arguments)?  The entry point's dry run: nothing is enqueued."""
+        return getattr(_lib.lib(), cls.entry)(*cls.pack(*descs), *cls.idle, 1, None) == 0
+
+    def chunks(self, riders):
+        """(update, first, count, max_blocks) of the optimizer chunks this launch carries in this run, or None."""
+        part = None if riders is None or self.key is None else riders.take(self.key, self.slot, self.nslots)
+        return part and (riders.ref, part[0], part[1], riders.max_blocks)
 
     def dense(self, h):
         """The dense contraction alone: what the launch falls back to without the work it carries, and what it is replayed as."""
@@ -407,56 +424,49 @@ class _Carrier(Launch):
         return self.dense, self.descs
 
 
-class _Rider(_Carrier):           # args: (product,)
+class _Rider(_Carrier):           # (univl_gemm_rider takes no dry_run: fits is its probe; without chunks the plain product goes out)
     __slots__ = ()
+    entry = "univl_gemm_rider"
+    fits = staticmethod(lambda desc: _lib.lib().univl_gemm_rider_fits(C.byref(desc)) == 1)
 
     def enqueue(self, h, riders=None):
-        part = self.part(riders)
-        if part is None:
-            return self.dense(h)
-        return self.fn(self.args[0], riders.ref, part[0], part[1], riders.max_blocks, h)
+        ad = self.chunks(riders)
+        return self.dense(h) if ad is None else self.fn(*self.args, *ad, h)
+
+
+class _Pair(_Carrier):            # (a dgrad product and the weight-gradient product fed by the same upstream gradient: replayed as it ran)
+    __slots__ = ()
+    entry, gemms = "univl_gemm_pair", slice(0, 2)
+    pack = staticmethod(lambda dgrad, wgrad: (C.byref(dgrad), C.byref(wgrad)))
 
 
 class _LnFold(_Carrier):
-    """... that finishes the LayerNorm `ln` behind its product: folded(h) is the launch with it and without chunks."""
+    """... that finishes the LayerNorm `ln` behind its product: whole(h) is the launch with it and without chunks; `ln_entry` runs the
+    LayerNorm alone, on the argument that follows the products."""
     __slots__ = ("ln",)
 
+    def enqueue(self, h, riders=None):
+        ad = self.chunks(riders)
+        rc = self.whole(h, ad)
+        if rc == _lib.EUNSUPPORTED:      # deterministic mode (or a shape the fold does not carry): the two launches
+            rc = self.dense(h) if ad is None else _lib.lib().univl_gemm_rider(self.args[0], *ad, h)
+            rc = rc or getattr(_lib.lib(), self.ln_entry)(self.args[self.gemms.stop], h)
+        return rc
+
     def replay(self, carried):    # carried: with its LayerNorm, whose descriptor then ends the list
-        return (self.folded, self.descs + [self.ln]) if carried else (self.dense, self.descs)
+        return (self.whole, self.descs + [self.ln]) if carried else (self.dense, self.descs)
 
 
-class _GemmLn(_LnFold):           # args: (product, LayerNorm, counters)
+class _GemmLn(_LnFold):
     __slots__ = ()
-
-    def folded(self, h, ad=(None, 0, 0, 0)):
-        return self.fn(*self.args, *ad, 0, h)
-
-    def enqueue(self, h, riders=None):
-        part = self.part(riders)
-        if part is None:
-            rc = self.folded(h)
-            if rc == _lib.EUNSUPPORTED:      # deterministic mode (or a shape the fold does not carry): the two launches
-                rc = self.dense(h) or _lib.lib().univl_layernorm_fwd(self.args[1], h)
-        else:
-            ad = (riders.ref, part[0], part[1], riders.max_blocks)
-            rc = self.folded(h, ad)
-            if rc == _lib.EUNSUPPORTED:
-                rc = _lib.lib().univl_gemm_rider(self.args[0], *ad, h) or _lib.lib().univl_layernorm_fwd(self.args[1], h)
-        return rc
+    entry, ln_entry, idle = "univl_gemm_ln", "univl_layernorm_fwd", (None, 0, 0, 0)
+    pack = staticmethod(lambda desc, ln_desc, counters: (C.byref(desc), C.byref(ln_desc), C.c_void_p(counters.data_ptr())))
 
 
-class _PairLn(_LnFold):           # args: (dgrad, wgrad, LayerNorm, counters, 0)
+class _PairLn(_LnFold):
     __slots__ = ()
-    gemms = slice(0, 2)
-
-    def folded(self, h):
-        return self.fn(*self.args, h)
-
-    def enqueue(self, h, riders=None):
-        rc = self.folded(h)
-        if rc == _lib.EUNSUPPORTED:
-            rc = self.dense(h) or _lib.lib().univl_layernorm_bwd(self.args[2], h)
-        return rc
+    entry, ln_entry, gemms = "univl_gemm_pair_ln", "univl_layernorm_bwd", slice(0, 2)
+    pack = staticmethod(lambda dgrad, wgrad, ln_desc, counters: (C.byref(dgrad), C.byref(wgrad), C.byref(ln_desc), C.c_void_p(counters.data_ptr())))
 
 
 class _FusedAttn(_Carrier):
@@ -468,20 +478,16 @@ class _FusedAttn(_Carrier):
         return prefix == "univl_gemm"
 
 
-class _AttnFwdFused(_FusedAttn):  # args: (attention, q | k | v projection)
+class _AttnFwdFused(_FusedAttn):
     __slots__ = ("attn",)
-    gemms = slice(1, 2)
-
-    def enqueue(self, h, riders=None):
-        part = self.part(riders)
-        if part is None:
-            return self.fn(*self.args, None, 0, 0, 0, 0, h)
-        return self.fn(*self.args, riders.ref, part[0], part[1], riders.max_blocks, 0, h)
+    entry, gemms, idle = "univl_attention_fwd_fused", slice(1, 2), (None, 0, 0, 0)
+    pack = staticmethod(lambda attn, qkv: (C.byref(attn), C.byref(qkv)))
 
 
-class _AttnBwdFused(_FusedAttn):  # args: (attention, attention-output dgrad, its weight gradient or None, 0)
+class _AttnBwdFused(_FusedAttn):  # (owgrad: the attention-output weight gradient that rides, or None)
     __slots__ = ()
-    gemms = slice(1, 3)
+    entry, gemms = "univl_attention_bwd_fused", slice(1, 3)
+    pack = staticmethod(lambda attn, odgrad, owgrad: (C.byref(attn), C.byref(odgrad), owgrad if owgrad is None else C.byref(owgrad)))
 
 
 class Plan:
@@ -517,15 +523,14 @@ class Plan:
     def add_gemm_rider(self, desc, key, slot, nslots, stream=0):
         """A forward product that, while self.riders names a chunk range for `key`, also carries
         the slot-th of nslots parts of that range of a prepared BertAdam update (univl_gemm_rider); otherwise a plain univl_gemm."""
-        self._launch(_Rider("rider", "univl_gemm_rider", stream, [desc], (C.byref(desc),), key, slot, nslots), [desc], (desc, key, int(slot), int(nslots)))
+        self._launch(_Rider("rider", stream, [desc], (C.byref(desc),), key, slot, nslots), [desc], (desc, key, int(slot), int(nslots)))
 
     def add_gemm_ln(self, desc, ln_desc, counters, key=None, slot=0, nslots=1, stream=0):
         """A forward product AND the LayerNorm that consumes its fp32 output in one launch (univl_gemm_ln: the last workgroups to
         contribute to a 64-row block normalise it); with `key` it also carries optimizer chunks like add_gemm_rider.  `counters`: the
         call site's int32 arrival counters (zeroed at allocation, left zero by every launch)."""
-        args = (C.byref(desc), C.byref(ln_desc), C.c_void_p(counters.data_ptr()))
         was = (desc, ln_desc, counters, key, int(slot), int(nslots))
-        self._launch(_GemmLn("gemm_ln", "univl_gemm_ln", stream, [desc], args, key, slot, nslots), was[:3], was).ln = ln_desc
+        self._launch(_GemmLn("gemm_ln", stream, [desc], _GemmLn.pack(*was[:3]), key, slot, nslots), was[:3], was).ln = ln_desc
 
     def add(self, fn_name, desc, stream=0):
         ref = C.byref(desc)
@@ -552,28 +557,26 @@ class Plan:
         """A dgrad product and the weight-gradient product fed by the same upstream gradient as
         ONE launch (univl_gemm_pair) -- the weight-gradient tiles fill the compute units the latency-bound dgrad leaves idle."""
         arr = (_lib.Gemm * 2)(dgrad, wgrad)
-        self._launch(Launch("pair", "univl_gemm_pair", stream, [dgrad, wgrad], (C.byref(arr[0]), C.byref(arr[1]), 0)), [arr], arr)
+        self._launch(_Pair("pair", stream, [dgrad, wgrad], _Pair.pack(arr[0], arr[1])), [arr], arr)
 
     def add_attn_fwd_fused(self, attn, qkv, key=None, slot=0, nslots=1, stream=0):
         """The attention forward with the q | k | v projection computed inside the launch (univl_attention_fwd_fused); with `key` it
         also carries optimizer chunks like add_gemm_rider."""
-        args = (C.byref(attn), C.byref(qkv))
-        self._launch(_AttnFwdFused("attn_fwd_fused", "univl_attention_fwd_fused", stream, [qkv], args, key, slot, nslots), [attn, qkv],
+        self._launch(_AttnFwdFused("attn_fwd_fused", stream, [qkv], _AttnFwdFused.pack(attn, qkv), key, slot, nslots), [attn, qkv],
                      (attn, qkv, key, int(slot), int(nslots))).attn = attn
 
     def add_attn_bwd_fused(self, attn, odgrad, owgrad, stream=0):
         """The attention backward with the attention-output dgrad that feeds it computed inside the launch, the weight gradient of
         that projection riding as extra workgroups (univl_attention_bwd_fused; owgrad may be None)."""
-        args = (C.byref(attn), C.byref(odgrad), C.byref(owgrad) if owgrad is not None else None, 0)
-        descs = [odgrad] + ([owgrad] if owgrad is not None else [])
-        self._launch(_AttnBwdFused("attn_fused", "univl_attention_bwd_fused", stream, descs, args), [attn, odgrad, owgrad], (attn, odgrad, owgrad))
+        was, descs = (attn, odgrad, owgrad), [odgrad] + ([owgrad] if owgrad is not None else [])
+        self._launch(_AttnBwdFused("attn_fused", stream, descs, _AttnBwdFused.pack(*was)), list(was), was)
 
     def add_gemm_pair_ln(self, dgrad, wgrad, ln_desc, counters, stream=0):
         """add_gemm_pair with the LayerNorm BACKWARD that consumes the dgrad's fp32 output finished inside the launch
         (univl_gemm_pair_ln); falls back to the two launches at run time where the library refuses (deterministic mode)."""
         arr = (_lib.Gemm * 2)(dgrad, wgrad)
-        args = (C.byref(arr[0]), C.byref(arr[1]), C.byref(ln_desc), C.c_void_p(counters.data_ptr()), 0)
-        self._launch(_PairLn("pair_ln", "univl_gemm_pair_ln", stream, [dgrad, wgrad], args), [arr, ln_desc, counters], (arr, ln_desc, counters)).ln = ln_desc
+        args, was = _PairLn.pack(arr[0], arr[1], ln_desc, counters), (arr, ln_desc, counters)
+        self._launch(_PairLn("pair_ln", stream, [dgrad, wgrad], args), list(was), was).ln = ln_desc
 
     def add_zeros(self, tensors, stream=0):
         """Clear several buffers with one launch (univl_zero_many)."""
@@ -1028,13 +1031,13 @@ class EncoderStack:
             carriers, nslots = None, 4
             fused_fwd = (self.bf and T <= int(_ab.get("attn_fuse_fwd_max_rows")) and bool(_ab.get("attn_fuse_fwd")) and
                          S <= int(_ab.get("attn_fuse_fwd_max_seq")) and
-                         _lib.lib().univl_attention_fwd_fused(C.byref(attn_f), C.byref(qkv_desc), None, 0, 0, 0, 1, None) == 0)
+                         _AttnFwdFused.accepts(attn_f, qkv_desc))
             # what the products of layer l carry: the chunks of the stack's next layer; behind its LAST layer those of `tail_key` (steps.
             # build_step: the first layer of the stack that runs after this one -- cross encoder / decoder -- instead of a launch in front
             # of the whole forward)
             nkey = (("layer", self.prefix, l + 1) if l + 1 < self.L else self.tail_key) if self.adam_ride else None
             if nkey is not None and T >= 1536:
-                fits = [_lib.lib().univl_gemm_rider_fits(C.byref(d)) == 1 for d in (qkv_desc, o_desc, f1_desc, f2_desc)]
+                fits = [_Rider.fits(d) for d in (qkv_desc, o_desc, f1_desc, f2_desc)]
                 fits[0] = fits[0] or fused_fwd           # the fused attention forward carries chunks whatever tile the projection would take
                 if not any(fits):
                     fits[2] = True               # nothing carries: the FFN1 product is followed by the whole range
@@ -1069,8 +1072,7 @@ class EncoderStack:
             def gemm_ln(desc, lnd, site, _l=l, _slot=slot, _key=nkey):
                 """a forward product and the LayerNorm behind it: one launch where the library carries the pair (ln_fold), else two"""
                 ctr = self.ln_ctr[_l, site] if self.ln_fold else None
-                if (ctr is not None and not self.probe_no_ln and
-                        _lib.lib().univl_gemm_ln(C.byref(desc), C.byref(lnd), C.c_void_p(ctr.data_ptr()), None, 0, 0, 0, 1, None) == 0):
+                if ctr is not None and not self.probe_no_ln and _GemmLn.accepts(desc, lnd, ctr):
                     key = _key
                     plan.add_gemm_ln(desc, lnd, ctr, key, _slot[0], 4, sm)
                     _slot[0] += 1 if key is not None else 0
@@ -1159,11 +1161,10 @@ class EncoderStack:
                 if pair_square:
                     dgrad.tile = 64          # A/B switch UNIVL_PAIR_FORM=square: an explicit tile keeps the 64 x 64 form of the pair launch
                 if (lnd is not None and self.ride and self.ln_fold_bwd and not self.probe_no_ln and
-                        _lib.lib().univl_gemm_pair_ln(C.byref(dgrad), C.byref(wgrad), C.byref(lnd),
-                                                      C.c_void_p(self.ln_ctr_b[_l, site].data_ptr()), 1, None) == 0):
+                        _PairLn.accepts(dgrad, wgrad, lnd, self.ln_ctr_b[_l, site])):
                     plan.add_gemm_pair_ln(dgrad, wgrad, lnd, self.ln_ctr_b[_l, site], sm)
                     return True
-                if self.ride and _lib.lib().univl_gemm_pair(C.byref(dgrad), C.byref(wgrad), 1, None) == 0:
+                if self.ride and _Pair.accepts(dgrad, wgrad):
                     plan.add_gemm_pair(dgrad, wgrad, sm)
                 else:
                     plan.add("univl_gemm", dgrad, sm)
@@ -1203,7 +1204,7 @@ class EncoderStack:
             #  11.87 vs 11.32 ms per step at 128 pairs; 2.26 vs 2.31 at 4 pairs, 3.37 vs 3.43 at 16: profiles/r05p_ab_attn_fuse_bwd.txt)
             w_ride = w_o if self.ride else None
             if (self.bf and T <= int(_ab.get("attn_fuse_bwd_max_rows")) and bool(_ab.get("attn_fuse_bwd")) and
-                    _lib.lib().univl_attention_bwd_fused(C.byref(attn_b), C.byref(o_dgrad), C.byref(w_ride) if w_ride is not None else None, 1, None) == 0):
+                    _AttnBwdFused.accepts(attn_b, o_dgrad, w_ride)):
                 plan.add_attn_bwd_fused(attn_b, o_dgrad, w_ride, sm)
                 if w_ride is None:
                     wgrads.append(w_o)
@@ -1388,7 +1389,7 @@ class DecoderStack:
                 and fl.compute_dtype == torch.bfloat16)
 
         def emit(wgrad, dgrad):
-            if ride and _lib.lib().univl_gemm_pair(C.byref(dgrad), C.byref(wgrad), 1, None) == 0:
+            if ride and _Pair.accepts(dgrad, wgrad):
                 plan.add_gemm_pair(dgrad, wgrad, sm)
             else:
                 plan.add("univl_gemm", wgrad, sm)

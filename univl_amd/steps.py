@@ -473,9 +473,45 @@ class PoolerSim:
                                          accumulate=True), run.sm)
 
 
+class HeadTransform:
+    """BertPredictionHeadTransform (dense + GELU + LayerNorm, module_bert.py:299-311, module_visual.py:298-305) over T rows: x16 -> h32 / h16,
+    and its backward from the gradient the owner writes to dh (backward=False: forward buffers alone).  names: tw / tb / lg / lb."""
+
+    def __init__(self, cx, names, T, stream, backward=True):
+        self.cx, self.n, self.T, self.sm = cx, names, T, stream
+        e, ct = cx.e, cx.ct
+        self.u, self.hy, self.hst, self.h32 = e(T, H, dtype=ct), e(T, H), e(T, 2), e(T, H)
+        self.h16 = e(T, H, dtype=ct) if cx.bf else self.h32
+        if backward:
+            self.dh, self.dg, self.du = e(T, H), e(T, H), e(T, H, dtype=ct)
+
+    def build_forward(self, plan, x16):
+        cx, fl, dt, n, T, sm, W32 = self.cx, self.cx.fl, self.cx.dt, self.n, self.T, self.sm, self.cx.fl.w32
+        plan.add("univl_gemm", _gemm_desc(dt, x16, H, fl.wop(n["tw"]), H, T, H, H, out32=self.hy, ldc=H, bias=W32(n["tb"]),
+                                          aux=self.u, ldaux=H, gelu="fwd"), sm)
+        plan.add("univl_layernorm_fwd", ops.layernorm_desc(dt, T, H, x=self.hy, gamma=W32(n["lg"]), beta=W32(n["lb"]), y=self.hy,
+                                                           stats=self.hst, out32=self.h32, out16=self.h16 if cx.bf else None), sm)
+
+    def build_backward(self, plan, gs, x16, dx32, accumulate_dx):
+        """dx32 receives the gradient wrt the input x16 (accumulated if accumulate_dx)."""
+        fl, dt, n, T, sm, G = self.cx.fl, self.cx.dt, self.n, self.T, self.sm, self.cx.fl.g
+        plan.add("univl_layernorm_bwd", ops.layernorm_desc(dt, T, H, gamma=fl.w32(n["lg"]), y=self.hy, stats=self.hst, dout=self.dh,
+                                                           dx32=self.dg, dgamma=G(n["lg"]), dbeta=G(n["lb"])), sm)
+        plan.add_callable(lambda: ops.gelu_bwd(self.dg, self.u, self.du), sm)
+        plan.add("univl_gemm", _gemm_desc(dt, self.du, H, x16, H, H, H, T, trans_a=1, trans_b=1, out32=G(n["tw"]), ldc=H,
+                                          accumulate=gs.acc(n["tw"]), dbias=G(n["tb"])), sm)
+        plan.add("univl_gemm", _gemm_desc(dt, self.du, H, fl.wop(n["tw"]), H, T, H, H, trans_b=1, out32=dx32, ldc=H,
+                                          accumulate=accumulate_dx), sm)
+
+
 class VocabHead:
     """BertLMPredictionHead tied to BERT's word table + CrossEntropyLoss(ignore_index=-1)
     (module_bert.py:299-330 / module_decoder.py:156-183; modeling.py:252-254, 273-276)."""
+
+    # loss form -> (descriptor class, forward entry, backward entry, what it adds to the plain form + verb, its adjective), all of K16
+    FORMS = dict(plain=(_lib.VocabCE, "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", None, None),
+                 weighted=(_lib.VocabCEW, "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "per-caption weights exist", "weighted"),
+                 smoothed=(_lib.VocabCES, "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "label smoothing exists", "smoothed"))
 
     def __init__(self, cx, prefix, T, stream=0, transform_only=False, seq_len=None, smoothing=0.0):
         """transform_only: the buffers of the transform and the labels alone -- no dlogits [T, V] and no backward workspace (score.CaptionScorer
@@ -487,12 +523,12 @@ class VocabHead:
         self.cx, self.prefix, self.T, self.sm = cx, prefix, T, stream
         self.seq_len, self.weight, self.smoothing = seq_len, None, float(smoothing)
         assert 0.0 <= self.smoothing < 1.0, smoothing
-        e, ct, bf = cx.e, cx.ct, cx.bf
+        self.form = "smoothed" if self.smoothing > 0 else ("plain" if seq_len is None else "weighted")
+        e, ct = cx.e, cx.ct
         V = cx.model.bert_config.vocab_size
         self.V, self.ldv = V, (V + 7) // 8 * 8
-        self.u, self.hy, self.hst = e(T, H, dtype=ct), e(T, H), e(T, 2)
-        self.h32 = e(T, H)
-        self.h16 = e(T, H, dtype=ct) if bf else self.h32
+        self.transform = tr = HeadTransform(cx, self.names(), T, stream, backward=not transform_only)
+        self.h32, self.h16 = tr.h32, tr.h16
         self._logits = None                      # materialised only where somebody reads them (evaluation / decoding, vocab_ce=0)
         self.labels = e(T, dtype=torch.int64)
         # K16 (univl_vocab_ce_fwd / _bwd): per-row (max, sum exp) pairs of the 128-column tiles, the label's logit, the row's log-sum-exp
@@ -501,7 +537,6 @@ class VocabHead:
             return
         self.dlogits = e(T, self.ldv, dtype=ct)
         self.loss, self.scratch = e(1), e(2)
-        self.dh, self.dg, self.du = e(T, H), e(T, H), e(T, H, dtype=ct)
         if seq_len is not None:
             assert seq_len >= 1 and T % seq_len == 0, (T, seq_len)
             self.weight = e(T // seq_len)
@@ -514,8 +549,7 @@ class VocabHead:
 
     def _k16_desc(self, x16, bias, table):
         e, T = self.cx.e, self.T
-        cls = _lib.VocabCES if self.smoothing > 0 else (_lib.VocabCE if self.weight is None else _lib.VocabCEW)
-        d = ops.vocab_head_desc(cls, x16, table, bias, self.labels, self.V)
+        d = ops.vocab_head_desc(self.FORMS[self.form][0], x16, table, bias, self.labels, self.V)
         if self.weight is not None:
             d.seq_weight, d.seq_len = self.weight.data_ptr(), self.seq_len
         self.k16 = k = dict(partial=e(T, d.slots, 2), label_logit=e(T), lse=e(T), rowloss=e(T))
@@ -535,36 +569,21 @@ class VocabHead:
         return dict(tw=p + ".transform.dense.weight", tb=p + ".transform.dense.bias", lg=p + ".transform.LayerNorm.weight",
                     lb=p + ".transform.LayerNorm.bias", bias=p + ".bias", emb="bert.embeddings.word_embeddings.weight")
 
-    def build_transform(self, fwd, x16):
-        """BertPredictionHeadTransform (dense + GELU + LayerNorm, module_bert.py:299-311): x16 -> self.h16"""
-        cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
-        W32 = fl.w32
-        fwd.add("univl_gemm", _gemm_desc(dt, x16, H, fl.wop(n["tw"]), H, T, H, H, out32=self.hy, ldc=H, bias=W32(n["tb"]),
-                                         aux=self.u, ldaux=H, gelu="fwd"), sm)
-        fwd.add("univl_layernorm_fwd", ops.layernorm_desc(dt, T, H, x=self.hy, gamma=W32(n["lg"]), beta=W32(n["lb"]), y=self.hy,
-                                                          stats=self.hst, out32=self.h32, out16=self.h16 if cx.bf else None), sm)
+    def build_transform(self, fwd, x16):         # x16 -> self.h16
+        self.transform.build_forward(fwd, x16)
 
     def build_forward(self, fwd, x16, with_loss=True):
         cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
         W32 = fl.w32
         self.build_transform(fwd, x16)
-        if self.smoothing > 0:
-            if not (with_loss and _ab.get("vocab_ce")):
-                raise RuntimeError("VocabHead: label smoothing exists only in K16 (univl_vocab_ce_smooth_fwd / _bwd); UNIVL_VOCAB_CE=0 "
-                                   "has no smoothed form")
-            fwd.add("univl_vocab_ce_smooth_fwd", self._k16_desc(self.h16, W32(n["bias"]), fl.wop(n["emb"])), sm)
-            return
-        if self.weight is not None:
-            if not (with_loss and _ab.get("vocab_ce")):
-                raise RuntimeError("VocabHead: per-caption weights exist only in K16 (univl_vocab_ce_weighted_fwd / _bwd); UNIVL_VOCAB_CE=0 "
-                                   "has no weighted form")
-            fwd.add("univl_vocab_ce_weighted_fwd", self._k16_desc(self.h16, W32(n["bias"]), fl.wop(n["emb"])), sm)
-            return
+        _, entry, _, adds, adj = self.FORMS[self.form]
         if with_loss and _ab.get("vocab_ce"):
             # K16: the product's epilogue keeps the online log-softmax statistics; the [T, 30522] logits never exist (module_bert.py:327-330 +
             # modeling.py:253 / 275 in one entry point); the backward recomputes the product into dlogits
-            fwd.add("univl_vocab_ce_fwd", self._k16_desc(self.h16, W32(n["bias"]), fl.wop(n["emb"])), sm)
+            fwd.add(entry, self._k16_desc(self.h16, W32(n["bias"]), fl.wop(n["emb"])), sm)
             return
+        if adds:
+            raise RuntimeError("VocabHead: %s only in K16 (%s / _bwd); UNIVL_VOCAB_CE=0 has no %s form" % (adds, entry, adj))
         fwd.add("univl_gemm", _gemm_desc(dt, self.h16, H, fl.wop(n["emb"]), H, T, self.V, H, out32=self.logits, ldc=self.ldv,
                                          bias=W32(n["bias"])), sm)
         if with_loss:
@@ -572,14 +591,12 @@ class VocabHead:
 
     def build_backward(self, bwd, gs, gout, x16, dx32, accumulate_dx):
         """dx32 receives the gradient wrt the head input (accumulated if accumulate_dx)."""
-        cx, fl, dt, n, T, sm = self.cx, self.cx.fl, self.cx.dt, self.names(), self.T, self.sm
-        W32, G = fl.w32, fl.g
+        fl, dt, n, T, sm, dh = self.cx.fl, self.cx.dt, self.names(), self.T, self.sm, self.transform.dh
         if self.k16 is not None:
             db = type(self.k16["desc"]).from_buffer_copy(self.k16["desc"])      # the forward's descriptor + the upstream gradient of this loss term
             db.gout = gout.data_ptr()
             self.k16["gout"] = gout
-            bwd.add("univl_vocab_ce_smooth_bwd" if self.smoothing > 0 else
-                    ("univl_vocab_ce_bwd" if self.weight is None else "univl_vocab_ce_weighted_bwd"), db, sm)
+            bwd.add(self.FORMS[self.form][2], db, sm)
         else:
             bwd.add_callable(lambda: ops.scale_ct(self.dlogits, gout), sm)
         # dh = dlogits . E contracts over the 30522-word vocabulary with only (T / 64) x 12 output tiles: unsplit, each workgroup
@@ -589,18 +606,12 @@ class VocabHead:
         if _ab.get("vocab_dgrad_split"):
             ks = max(1, min(16, 512 // max(1, ((T + 63) // 64) * (H // 64))))
         if ks > 1:
-            bwd.add_zeros([self.dh], sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.dlogits, self.ldv, fl.wop(n["emb"]), H, T, H, self.V, trans_b=1, out32=self.dh, ldc=H,
+            bwd.add_zeros([dh], sm)
+        bwd.add("univl_gemm", _gemm_desc(dt, self.dlogits, self.ldv, fl.wop(n["emb"]), H, T, H, self.V, trans_b=1, out32=dh, ldc=H,
                                          ksplit=ks), sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.dlogits, self.ldv, self.h16, H, self.V, H, T, trans_a=1, trans_b=1, out32=G(n["emb"]),
-                                         ldc=H, accumulate=True, dbias=G(n["bias"])), sm)
-        bwd.add("univl_layernorm_bwd", ops.layernorm_desc(dt, T, H, gamma=W32(n["lg"]), y=self.hy, stats=self.hst, dout=self.dh,
-                                                          dx32=self.dg, dgamma=G(n["lg"]), dbeta=G(n["lb"])), sm)
-        bwd.add_callable(lambda: ops.gelu_bwd(self.dg, self.u, self.du), sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.du, H, x16, H, H, H, T, trans_a=1, trans_b=1, out32=G(n["tw"]), ldc=H,
-                                         accumulate=gs.acc(n["tw"]), dbias=G(n["tb"])), sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.du, H, fl.wop(n["tw"]), H, T, H, H, trans_b=1, out32=dx32, ldc=H,
-                                         accumulate=accumulate_dx), sm)
+        bwd.add("univl_gemm", _gemm_desc(dt, self.dlogits, self.ldv, self.h16, H, self.V, H, T, trans_a=1, trans_b=1, out32=fl.g(n["emb"]),
+                                         ldc=H, accumulate=True, dbias=fl.g(n["bias"])), sm)
+        self.transform.build_backward(bwd, gs, x16, dx32, accumulate_dx)
 
 
 class RowFeatures:
@@ -697,15 +708,12 @@ class PretrainHeads:
         self.vpart16 = e(Tv, H, dtype=ct) if bf else self.vpart
         self.dtpart, self.dvpart = e(Tt, H), e(Tv, H)
         self.mlm = VocabHead(cx, "cls.predictions", Tt, stream=run.sm)
-        # visual head
-        self.u, self.hy, self.hst, self.h32 = e(Tv, H, dtype=ct), e(Tv, H), e(Tv, 2), e(Tv, H)
-        self.h16 = e(Tv, H, dtype=ct) if bf else self.h32
+        self.vtransform = HeadTransform(cx, self.VN, Tv, run.sm)         # visual head
         self.scores = e(Tv, D, dtype=ct)
         self.ldl = (Tv + 7) // 8 * 8
         self.logits = e(Tv, self.ldl)
         self.dlogits_ct = e(Tv, self.ldl, dtype=ct) if bf else self.logits
         self.dscores = e(Tv, D, dtype=ct)
-        self.dh, self.dg, self.du = e(Tv, H), e(Tv, H), e(Tv, H, dtype=ct)
         self.vlabels = e(Tv, dtype=torch.int64)
         self.nce_loss, self.scratch = e(1), e(2)
 
@@ -718,8 +726,7 @@ class PretrainHeads:
         self.vlabels.copy_(video_labels_index.reshape(-1), non_blocking=True)
 
     def build_forward(self, fwd):
-        cx, run, fl, dt, n, sm = self.cx, self.run, self.cx.fl, self.cx.dt, self.VN, self.run.sm
-        W32 = fl.w32
+        cx, run, fl, dt, n, sm, tr, W32 = self.cx, self.run, self.cx.fl, self.cx.dt, self.VN, self.run.sm, self.vtransform, self.cx.fl.w32
         B, W, F, Tv, D = self.B, self.W, self.F, self.Tv, self.D
         # torch.split(cross_output, [W, F], dim=1)  (modeling.py:225)
         fwd.add_callable(self.tpart.zero_, sm)
@@ -730,11 +737,8 @@ class PretrainHeads:
             fwd.add_callable(lambda: ops.cast_bf16(self.vpart, self.vpart16), sm)
         self.mlm.build_forward(fwd, self.tpart16)
         # VisualLMPredictionHead (module_visual.py:298-311): LN(gelu(dense(x))) . W_vis[768,1024] + bias
-        fwd.add("univl_gemm", _gemm_desc(dt, self.vpart16, H, fl.wop(n["tw"]), H, Tv, H, H, out32=self.hy, ldc=H, bias=W32(n["tb"]),
-                                         aux=self.u, ldaux=H, gelu="fwd"), sm)
-        fwd.add("univl_layernorm_fwd", ops.layernorm_desc(dt, Tv, H, x=self.hy, gamma=W32(n["lg"]), beta=W32(n["lb"]), y=self.hy,
-                                                          stats=self.hst, out32=self.h32, out16=self.h16 if cx.bf else None), sm)
-        fwd.add("univl_gemm", _gemm_desc(dt, self.h16, H, fl.wop(n["vw"]), D, Tv, D, H, trans_b=1, out16=self.scores, ldc=D,
+        tr.build_forward(fwd, self.vpart16)
+        fwd.add("univl_gemm", _gemm_desc(dt, tr.h16, H, fl.wop(n["vw"]), D, Tv, D, H, trans_b=1, out16=self.scores, ldc=D,
                                          bias=W32(n["bias"])), sm)
         # logits_matrix = afm_scores . video^T against all normalised CLEAN frames of the batch (modeling.py:282-285)
         fwd.add("univl_gemm", _gemm_desc(dt, self.scores, D, self.clean.vn_op, D, Tv, Tv, D, out32=self.logits, ldc=self.ldl), sm)
@@ -744,8 +748,7 @@ class PretrainHeads:
             fwd.add_callable(lambda: ops.cast_bf16(self.logits, self.dlogits_ct), sm)
 
     def build_backward(self, bwd, gs, gout):
-        cx, run, fl, dt, n, sm = self.cx, self.run, self.cx.fl, self.cx.dt, self.VN, self.run.sm
-        W32, G = fl.w32, fl.g
+        cx, run, fl, dt, n, sm, tr, G = self.cx, self.run, self.cx.fl, self.cx.dt, self.VN, self.run.sm, self.vtransform, self.cx.fl.g
         B, W, F, Tv, D, ldl = self.B, self.W, self.F, self.Tv, self.D, self.ldl
         dl = self.dlogits_ct
         bwd.add_callable(lambda: ops.scale_ct(dl, gout), sm)
@@ -755,15 +758,10 @@ class PretrainHeads:
                                          accumulate=True), sm)
         bwd.add_callable(lambda: ops.colsum(self.dscores, G(n["bias"])), sm)
         # scores = h . W_vis: dh = dscores . W_vis^T ; dW_vis += h^T . dscores
-        bwd.add("univl_gemm", _gemm_desc(dt, self.dscores, D, fl.wop(n["vw"]), D, Tv, H, D, out32=self.dh, ldc=H), sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.h16, H, self.dscores, D, H, D, Tv, trans_a=1, trans_b=1, out32=G(n["vw"]), ldc=D,
+        bwd.add("univl_gemm", _gemm_desc(dt, self.dscores, D, fl.wop(n["vw"]), D, Tv, H, D, out32=tr.dh, ldc=H), sm)
+        bwd.add("univl_gemm", _gemm_desc(dt, tr.h16, H, self.dscores, D, H, D, Tv, trans_a=1, trans_b=1, out32=G(n["vw"]), ldc=D,
                                          accumulate=gs.acc(n["vw"])), sm)
-        bwd.add("univl_layernorm_bwd", ops.layernorm_desc(dt, Tv, H, gamma=W32(n["lg"]), y=self.hy, stats=self.hst, dout=self.dh,
-                                                          dx32=self.dg, dgamma=G(n["lg"]), dbeta=G(n["lb"])), sm)
-        bwd.add_callable(lambda: ops.gelu_bwd(self.dg, self.u, self.du), sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.du, H, self.vpart16, H, H, H, Tv, trans_a=1, trans_b=1, out32=G(n["tw"]), ldc=H,
-                                         accumulate=gs.acc(n["tw"]), dbias=G(n["tb"])), sm)
-        bwd.add("univl_gemm", _gemm_desc(dt, self.du, H, fl.wop(n["tw"]), H, Tv, H, H, trans_b=1, out32=self.dvpart, ldc=H), sm)
+        tr.build_backward(bwd, gs, self.vpart16, self.dvpart, accumulate_dx=False)
         self.mlm.build_backward(bwd, gs, gout, self.tpart16, self.dtpart, accumulate_dx=False)
         # d cross_output = cat(d text part, d video part): written in full (this run has no other consumer)
         bwd.add_callable(lambda: ops.pair_concat_fwd(self.dtpart, self.dvpart, run.enc.amask, run.enc.vmask, self.arange, self.arange,
