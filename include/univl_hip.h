@@ -399,6 +399,53 @@ typedef struct {
     void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch of >= n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8 bytes          */
 } UnivlBeamStep;
 int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream);
+/* Diverse Beam Search (Vijayakumar et al.; elsewhere `num_beam_groups` + `diversity_penalty`): the n_bm beams of an instance are
+ * n_groups = G groups of width k' = n_bm / G, and a group is penalised for the tokens that EARLIER groups chose at the same position
+ * (Hamming diversity).  Two launches, no host involvement, capturable, the workspace of univl_beam_step.
+ * LAYOUT: done and length are [n_inst * G], one entry per (instance, group); group g of instance i owns beams b in [g k', (g+1) k'),
+ * i.e. rows i * n_bm + b.  The history arrays [Tmax, n_inst, n_bm] are, byte for byte, [Tmax, n_inst * G, k'], and the parents written
+ * into them are LOCAL to the group: to univl_beam_backtrack, univl_beam_captions, univl_gather_rows and univl_decode_constrain
+ * (done_stride = k') the call is an ordinary search on n_inst * G pseudo-instances of width k'.
+ * Per instance i the groups g = 0 .. G-1 are handled IN ORDER.  A group with done[i G + g] != 0 is FROZEN exactly as a frozen instance
+ * of univl_beam_step (state untouched, src and the history's parents the identity, the history's tokens / scores repeat the state) and
+ * contributes NO tokens to the penalty of later groups.  A live group:
+ *   value(b, v)  = lp[i * n_bm + b, v] + scores[i, b]   (one fp32 addition; at the first step only the group's first beam counts and
+ *                  nothing is added), v < V;
+ *   c(v)         = the number of beams of EARLIER LIVE groups of instance i whose token chosen at this position is v;
+ *   ranked(b, v) = value - p, p = lambda * (float)c(v): the product rounded to fp32 once, the subtraction rounded separately (no fma
+ *                  across them); c = 0 subtracts +0;
+ *   the k' candidates with the largest `ranked` (TIE RULE of univl_beam_step: equal fp32 values by LOWER flat index b * V + v first),
+ *   then RE-SORTED by their unpenalised value, descending, same tie rule.  scores / the history's scores get the UNPENALISED value:
+ *   the penalty orders the selection and does not accumulate, so scores stay the model's log-probabilities, beam 0 of a group is its
+ *   best, and hypothesis scores are comparable across groups.  tokens, src (i * n_bm + parent) and the history row as univl_beam_step
+ *   writes them;  length[i G + g] += 1;  done[i G + g] <- 1 if the group's TOP beam's token == eos.
+ * lambda = *diversity_dev when that optional device word is given (the pattern of eos_dev: one capture serves every penalty; a
+ * negative or non-finite word there is the caller's error, indices stay in range), else `diversity`.
+ * IDENTITIES: n_groups == 1 is univl_beam_step bit for bit; diversity == 0 with any G is univl_beam_step called with
+ * (n_inst * G, k') on the same buffers, bit for bit.  NaN values: unspecified, every index written stays in range.
+ * Range: that of univl_beam_step, and 1 <= n_groups <= n_bm, n_bm % n_groups == 0, diversity finite and >= 0 (unless diversity_dev);
+ * otherwise UNIVL_EINVAL and nothing is launched.  The struct is in neither numbered size table: univl_beam_group_step_sizeof states
+ * its size. */
+typedef struct {
+    const float* lp; int64_t ld;     /* the fields of UnivlBeamStep, in its order ...                                             */
+    int32_t n_inst, n_bm, V;
+    int32_t first_step;              /* != 0: only the first beam's row of every group is read and no score is added              */
+    int32_t eos;
+    const int32_t* eos_dev;
+    int32_t t, Tmax;
+    float* scores;                   /* [n_inst, n_bm]       read and written                                                     */
+    uint8_t* done;                   /* [n_inst * n_groups]  read and written                                                     */
+    int32_t* length;                 /* [n_inst * n_groups]  read and written                                                     */
+    int64_t* tokens;
+    int32_t* src;
+    int32_t* hist_parents; int32_t* hist_tokens; float* hist_scores;
+    void* ws; int64_t ws_bytes;      /* as UnivlBeamStep.ws                                                                       */
+    int32_t n_groups;                /* ... then G                                                                                */
+    float diversity;                 /* lambda                                                                                    */
+    const float* diversity_dev;      /* optional device word read INSTEAD of diversity; NULL: diversity                           */
+} UnivlBeamGroupStep;
+int univl_beam_group_step_sizeof(void);
+int univl_beam_group_step(const UnivlBeamGroupStep* d, hipStream_t stream);
 /* Beam.get_hypothesis (beam.py:108-116) for the n_best best beams of every instance (beams are sorted after univl_beam_step, so
  * beam k is the k-th best): hyp[i, k, 0 .. length[i]) <- the tokens found by walking the history back from (row length[i] - 1,
  * beam k) through the parents, the rest of hyp[i, k, :] (Tmax entries) <- -1;  hyp_scores[i, k] <- scores[i, k].

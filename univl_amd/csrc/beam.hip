@@ -8,6 +8,21 @@
 //            creates between different log-probabilities of a row are seen by the tie rule like any other tie.
 //   phase 2  one wave per instance: the n_bm best of the (1 or n_bm) x slices x n_bm pairs, then parents / tokens / state / history.
 // Order of candidates everywhere: larger value first, equal values by LOWER flat index b * V + v first (`better`, ranked.h).
+//
+// univl_beam_group_step is Diverse Beam Search (Vijayakumar et al.: beam groups, Hamming diversity) on the same two launches.  The G
+// groups of width k' = n_bm / G of an instance are the pseudo-instances i * G + g of an ordinary search of width k': `done`, `length`
+// and the history are laid out that way, and phase 1 is the scan above with the frozen test reading done[row / k'] (its `stride`) while
+// every row still keeps a top-n_bm.  Phase 2 (beam_group_select_kernel) takes the groups of an instance in order inside one wave.
+// WHY THE PER-ROW TOP-n_bm IS ENOUGH.  A group ranks its candidates by value - lambda * c(v), c(v) = the number of beams of earlier live
+// groups that chose v at this position, and keeps the k' best.  lambda >= 0, so the penalty only lowers a candidate (rounding is
+// monotone: fl(value - p) <= value), and it touches at most (G - 1) k' distinct tokens.  Take a candidate x of row b outside that row's
+// unpenalised top-n_bm: n_bm candidates of row b stand in front of it in the order above, at least n_bm - (G - 1) k' = k' of them
+// unpenalised, and each of those k' still stands in front of x after the penalty (its ranked value is its value, x's is at most x's
+// value, the index decides a tie as before).  So x is not among the group's k' best: a row's penalised top-k' lies inside its
+// unpenalised top-n_bm, which lies inside the union of its slices' top-n_bm.  With lambda < 0 the argument fails (a candidate far down
+// a row could be lifted past the list), which is why a negative penalty is refused.
+#include <cmath>
+
 #include "common.h"
 #include "ranked.h"
 #include "univl_hip.h"
@@ -30,13 +45,14 @@ __device__ __forceinline__ void keep(float (&tv)[NB], int (&ti)[NB], float v, in
 // ws_val / ws_idx: [rows][slices][NB]; idx is the COLUMN within the row (RANK_NONE: empty)
 template <int NB>
 __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict__ lp, long ld, int V, int first_step, const float* __restrict__ scores,
-                                                        const uint8_t* __restrict__ done, int chunk, int vec, float* __restrict__ ws_val,
-                                                        int* __restrict__ ws_idx) {
+                                                        const uint8_t* __restrict__ done, int stride, int chunk, int vec,
+                                                        float* __restrict__ ws_val, int* __restrict__ ws_idx) {
     __shared__ float red_v[2][4];
     __shared__ int red_i[2][4];
-    const int inst = first_step ? (int)blockIdx.x : (int)blockIdx.x / NB;
+    // stride: rows per entry of done -- n_bm for univl_beam_step (an instance), k' for univl_beam_group_step (a group)
+    const int inst = first_step ? (int)blockIdx.x : (int)blockIdx.x / stride;
     if (done[inst]) return;                                   // frozen instance: phase 2 does not read its slots
-    const int row = first_step ? inst * NB : (int)blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
+    const int row = first_step ? inst * stride : (int)blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
     const float add = first_step ? 0.f : scores[row];
     const float* x = lp + (long)row * ld;
     const int c0 = slice * chunk, c1 = min(V, c0 + chunk);    // chunk is a multiple of 4
@@ -193,11 +209,133 @@ __global__ __launch_bounds__(256) void beam_captions_kernel(const int32_t* hyp, 
     if (lane == 0) cap_len[row] = cut;
 }
 
+// Phase 2 of univl_beam_group_step: one wave per instance, its G groups in order.  A stage stages the (value, flat index) pairs of
+// its own k' rows (at most 8 x 8 x 8 = 512 for G = 1) together with their ranked value, takes k' rounds of wave_best on `ranked`,
+// re-sorts the k' winners by their unpenalised value and appends their tokens to pen_tok, the list the later stages count c(v) in
+// (at most n_bm - k' entries when it is read; a token chosen by several beams stands there once per beam, so the count is the
+// number of matches).  A frozen group writes its frozen rows and appends nothing.  Single wave, fixed order, no atomics.
+__device__ __forceinline__ float ranked_value(float value, float lambda, int c) {
+#pragma clang fp contract(off)                                // two roundings: the product, then the difference
+    const float p = lambda * (float)c;
+    return value - p;
+}
+
+__global__ __launch_bounds__(64) void beam_group_select_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx, int n_bm, int n_groups,
+                                                               int V, int slices, int first_step, int eos, const int32_t* __restrict__ eos_dev,
+                                                               float diversity, const float* __restrict__ diversity_dev, long hist_row, BeamOut o) {
+    __shared__ float cv[512];                                 // unpenalised value: what is stored
+    __shared__ float rk[512];                                 // ranked value: what is selected by
+    __shared__ int ci[512];
+    __shared__ float win_v[8], srt_v[8];
+    __shared__ int win_i[8], srt_i[8];
+    __shared__ int pen_tok[8];
+    const int inst = blockIdx.x, lane = threadIdx.x, kp = n_bm / n_groups;
+    const float lambda = diversity_dev ? *diversity_dev : diversity;
+    const int end = eos_dev ? *eos_dev : eos;
+    const int per_row = slices * n_bm;
+    int npen = 0;                                             // wave-uniform
+    for (int g = 0; g < n_groups; ++g) {
+        const int grp = inst * n_groups + g, b0 = g * kp;     // the pseudo-instance; the group's first beam within the instance
+        const long s0 = (long)inst * n_bm + b0;               // its first row / state slot
+        if (o.done[grp]) {                                    // frozen (wave-uniform): as a frozen instance of beam_select_kernel
+            if (lane < kp) {
+                o.src[s0 + lane] = (int32_t)(s0 + lane);
+                o.hist_parents[hist_row + s0 + lane] = lane;
+                o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
+                o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
+            }
+            continue;
+        }
+        const int ncand = (first_step ? 1 : kp) * per_row;
+        for (int c = lane; c < ncand; c += 64) {
+            const int col = ws_idx[s0 * per_row + c];
+            const float v = ws_val[s0 * per_row + c];
+            int cnt = 0;
+            for (int j = 0; j < npen; ++j) cnt += pen_tok[j] == col ? 1 : 0;
+            cv[c] = v;
+            rk[c] = ranked_value(v, lambda, cnt);
+            ci[c] = col == RANK_NONE ? RANK_NONE : (b0 + c / per_row) * V + col;
+        }
+        // a lane reads back only the slots it wrote (c = lane mod 64): no barrier until the winners are exchanged
+        for (int r = 0; r < kp; ++r) {
+            float v = -INFINITY;
+            int i = RANK_NONE, at = -1;
+            for (int c = lane; c < ncand; c += 64)
+                if (better(rk[c], ci[c], v, i)) { v = rk[c]; i = ci[c]; at = c; }
+            const int mine = i;
+            wave_best(v, i);
+            if (i == RANK_NONE) {
+                if (lane == 0) { win_v[r] = -INFINITY; win_i[r] = RANK_NONE; }
+            } else if (mine == i) {                            // flat indices are unique: one owner
+                win_v[r] = cv[at]; win_i[r] = i;
+                rk[at] = -INFINITY; ci[at] = RANK_NONE;
+            }
+        }
+        __syncthreads();
+        if (lane < kp) {                                      // place among the k' winners by (value, flat index); slot order settles empty ones
+            const float mv = win_v[lane];
+            const int mi = win_i[lane];
+            int place = 0;
+            for (int j = 0; j < kp; ++j)
+                if (j != lane && (better(win_v[j], win_i[j], mv, mi) || (!better(mv, mi, win_v[j], win_i[j]) && j < lane))) ++place;
+            srt_v[place] = mv; srt_i[place] = mi;
+        }
+        __syncthreads();
+        if (lane < kp) {
+            // fewer than k' comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
+            const int flat = srt_i[lane] == RANK_NONE ? (b0 + lane) * V : srt_i[lane], parent = flat / V, token = flat % V;
+            o.scores[s0 + lane] = srt_v[lane];
+            o.tokens[s0 + lane] = token;
+            o.src[s0 + lane] = (int32_t)((long)inst * n_bm + parent);
+            o.hist_parents[hist_row + s0 + lane] = parent - b0;           // local to the group: the pseudo-instance view
+            o.hist_tokens[hist_row + s0 + lane] = token;
+            o.hist_scores[hist_row + s0 + lane] = srt_v[lane];
+            pen_tok[npen + lane] = token;
+            if (lane == 0) {
+                o.length[grp] += 1;
+                if (token == end) o.done[grp] = 1;
+            }
+        }
+        npen += kp;
+        __syncthreads();                                      // pen_tok is read, and win / srt rewritten, by the next stage
+    }
+}
+
+// what the two entry points hand to phase 1; n_units x stride = rows, done has n_units entries
+struct Scan {
+    const float* lp; long ld; int V, first_step; const float* scores; const uint8_t* done; int n_units, stride;
+};
+
 template <int NB>
-void launch_scan(const UnivlBeamStep* d, int slices, int chunk, int vec, float* ws_val, int* ws_idx, hipStream_t stream) {
-    const unsigned rows = d->first_step ? d->n_inst : d->n_inst * NB;
-    hipLaunchKernelGGL(beam_scan_kernel<NB>, dim3(rows, slices), dim3(256), 0, stream, d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores,
-                       d->done, chunk, vec, ws_val, ws_idx);
+void launch_scan(const Scan& a, int slices, int chunk, int vec, float* ws_val, int* ws_idx, hipStream_t stream) {
+    const unsigned rows = a.first_step ? a.n_units : a.n_units * a.stride;
+    hipLaunchKernelGGL(beam_scan_kernel<NB>, dim3(rows, slices), dim3(256), 0, stream, a.lp, a.ld, a.V, a.first_step, a.scores, a.done, a.stride,
+                       chunk, vec, ws_val, ws_idx);
+}
+
+// Phase 1 with a sorted top-n_bm per (row, slice); returns the slices used.  ws: [rows][slices][n_bm] values, then as many indices.
+int scan_rows(const Scan& a, int n_bm, void* ws, float** ws_val, int** ws_idx, hipStream_t stream) {
+    const int64_t rows = (int64_t)a.n_units * a.stride;
+    // slices: enough workgroups for the whole chip (~4 per CU at 80 rows), but at least 1024 columns each
+    const int64_t scanned = a.first_step ? a.n_units : rows;
+    int slices = (int)((1024 + scanned - 1) / scanned);
+    const int by_len = (a.V + 1023) / 1024;
+    slices = slices > by_len ? by_len : slices;
+    slices = slices < 1 ? 1 : (slices > UNIVL_BEAM_SLICES ? UNIVL_BEAM_SLICES : slices);
+    const int chunk = slice_chunk(a.V, slices), vec = rows_vec4(a.lp, a.ld);
+    *ws_val = static_cast<float*>(ws);
+    *ws_idx = reinterpret_cast<int*>(*ws_val + rows * slices * n_bm);
+    switch (n_bm) {
+        case 1: launch_scan<1>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 2: launch_scan<2>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 3: launch_scan<3>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 4: launch_scan<4>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 5: launch_scan<5>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 6: launch_scan<6>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 7: launch_scan<7>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        default: launch_scan<8>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+    }
+    return slices;
 }
 
 }  // namespace
@@ -217,29 +355,48 @@ extern "C" int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream) {
     UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
                     "univl_beam_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); got %lld",
                     (long long)need, (long long)d->ws_bytes);
-    // slices: enough workgroups for the whole chip (~4 per CU at 80 rows), but at least 1024 columns each
-    const int64_t scanned = d->first_step ? d->n_inst : rows;
-    int slices = (int)((1024 + scanned - 1) / scanned);
-    const int by_len = (d->V + 1023) / 1024;
-    slices = slices > by_len ? by_len : slices;
-    slices = slices < 1 ? 1 : (slices > UNIVL_BEAM_SLICES ? UNIVL_BEAM_SLICES : slices);
-    const int chunk = slice_chunk(d->V, slices), vec = rows_vec4(d->lp, d->ld);
-    float* ws_val = static_cast<float*>(d->ws);
-    int* ws_idx = reinterpret_cast<int*>(ws_val + rows * slices * d->n_bm);
-    switch (d->n_bm) {
-        case 1: launch_scan<1>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        case 2: launch_scan<2>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        case 3: launch_scan<3>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        case 4: launch_scan<4>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        case 5: launch_scan<5>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        case 6: launch_scan<6>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        case 7: launch_scan<7>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-        default: launch_scan<8>(d, slices, chunk, vec, ws_val, ws_idx, stream); break;
-    }
+    float* ws_val;
+    int* ws_idx;
+    const Scan a{d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores, d->done, d->n_inst, d->n_bm};
+    const int slices = scan_rows(a, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
     UNIVL_LAUNCH_CHECK();
     BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
     hipLaunchKernelGGL(beam_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->V, slices, d->first_step ? 1 : 0,
                        d->eos, d->eos_dev, (long)d->t * rows, o);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_beam_group_step_sizeof(void) { return (int)sizeof(UnivlBeamGroupStep); }
+
+extern "C" int univl_beam_group_step(const UnivlBeamGroupStep* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_group_step: null descriptor");
+    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V &&
+                    d->V <= INT_MAX / UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
+                    "univl_beam_group_step: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", d->n_inst, d->n_bm, d->V,
+                    (long long)d->ld, UNIVL_BEAM_MAX);
+    UNIVL_CHECK_ARG(d->n_groups >= 1 && d->n_groups <= d->n_bm && d->n_bm % d->n_groups == 0, UNIVL_EINVAL,
+                    "univl_beam_group_step: n_groups=%d does not divide n_bm=%d (1 <= n_groups <= n_bm)", d->n_groups, d->n_bm);
+    UNIVL_CHECK_ARG(d->diversity_dev != nullptr || (std::isfinite(d->diversity) && d->diversity >= 0.f), UNIVL_EINVAL,
+                    "univl_beam_group_step: diversity=%g, expected finite and >= 0 (the per-row top-n_bm lists hold every winner only then)",
+                    (double)d->diversity);
+    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "univl_beam_group_step: history row t=%d of Tmax=%d", d->t, d->Tmax);
+    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
+                    d->ws, UNIVL_EINVAL, "univl_beam_group_step: null pointer");
+    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
+    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
+    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
+                    "univl_beam_group_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); "
+                    "got %lld", (long long)need, (long long)d->ws_bytes);
+    float* ws_val;
+    int* ws_idx;
+    const Scan a{d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores, d->done, d->n_inst * d->n_groups, d->n_bm / d->n_groups};
+    const int slices = scan_rows(a, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
+    UNIVL_LAUNCH_CHECK();
+    BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
+    hipLaunchKernelGGL(beam_group_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->n_groups, d->V, slices,
+                       d->first_step ? 1 : 0, d->eos, d->eos_dev, d->diversity, d->diversity_dev, (long)d->t * rows, o);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

@@ -22,16 +22,41 @@ of earlier inputs, so here:
   * `beam_step="host"` keeps the earlier bookkeeping (torch.topk / where on the device, one host read per position) as the
     comparand of the tests and the A/B of the timing; it fills the same result object.
 
+  * `beam_groups=G > 1` is Diverse Beam Search (Vijayakumar et al.): the n_bm beams of an instance are G groups of width
+    k' = n_bm / G, searched in order at every position, each penalised by `diversity_penalty` times the number of beams of
+    earlier groups that chose the same token at that position.  Only the last launch of a position changes
+    (univl_beam_group_step instead of univl_beam_step): to every other launch and to the walk-back the session is an ordinary
+    search on n_inst * G pseudo-instances of width k'.  The penalty is a device word (set_diversity).
+
 Same results as the reference's procedure on the same logits: first step uses beam 0's distribution only (beam.py:69),
 an instance is done when its top beam emits EOS (beam.py:84), the reported hypotheses are the n_best best-scored beams walked
 back through the back-pointers (beam.py:108-116, collect_hypothesis_and_scores).  Candidates of exactly equal fp32 value
 are ordered by lower flat index first in the device path (include/univl_hip.h); torch.topk leaves that order open.
 """
+import math
+
 import torch
 
 from . import _ab, ops
 from .engine import DecoderLayer, DecoderStack, Plan, _gemm_desc
 from .steps import EvalSession, VocabHead, H
+
+
+def check_beam_groups(n_bm, beam_groups=1, diversity_penalty=0.0):
+    """The argument rule of group search, on the host and before any device work: beam_groups divides n_bm, the penalty is finite
+    and >= 0 (a negative one would lift candidates that the per-row candidate lists of the beam step do not hold).  Returns
+    (G, k' = n_bm // G, penalty as float); ValueError otherwise."""
+    if isinstance(beam_groups, bool) or not isinstance(beam_groups, int) or not isinstance(n_bm, int):
+        raise ValueError("beam_groups=%r, n_bm=%r: expected integers" % (beam_groups, n_bm))
+    if not 1 <= beam_groups <= n_bm or n_bm % beam_groups:
+        raise ValueError("beam_groups=%d does not divide n_bm=%d (1 <= beam_groups <= n_bm)" % (beam_groups, n_bm))
+    try:
+        pen = float(diversity_penalty)
+    except (TypeError, ValueError):
+        raise ValueError("diversity_penalty=%r is not a number" % (diversity_penalty,))
+    if not math.isfinite(pen) or pen < 0.0:
+        raise ValueError("diversity_penalty=%r, expected a finite value >= 0" % (diversity_penalty,))
+    return beam_groups, n_bm // beam_groups, pen
 
 
 class BeamResult:
@@ -40,11 +65,17 @@ class BeamResult:
       scores  [n, n_best] fp32          their accumulated log-probabilities (non-increasing in k)
       lengths [n] int32                 generated tokens per instance (all n_best hypotheses of an instance share it)
       parents / step_tokens / step_scores  [steps_run, n, n_bm]   the history; steps_run is the max_len of the call, rows at or
-                                        past an instance's length are frozen rows (identity parents, state repeated)."""
+                                        past an instance's length are frozen rows (identity parents, state repeated).
+      groups  G                         1 for a plain search, whose shapes are the ones above.  For a group search (G > 1, n_best
+                                        counted PER GROUP): tokens [n, G * n_best, Tmax] and scores [n, G * n_best] group-major
+                                        (entry g * n_best + k is the k-th best of group g; non-increasing in k within a group),
+                                        lengths [n, G], and the history's n_bm axis is G runs of k' beams with parents LOCAL to
+                                        their group."""
 
-    def __init__(self, tokens, scores, lengths, parents, step_tokens, step_scores):
+    def __init__(self, tokens, scores, lengths, parents, step_tokens, step_scores, groups=1):
         self.tokens, self.scores, self.lengths = tokens, scores, lengths
         self.parents, self.step_tokens, self.step_scores = parents, step_tokens, step_scores
+        self.groups = groups
 
     @property
     def steps_run(self):
@@ -54,14 +85,23 @@ class BeamResult:
         """The reference's cut of every hypothesis at the first eos ("[SEP]"), then at the first pad ("[PAD]")
         (main_task_caption.py:555-560), on the device (ops.beam_captions): (cap_tokens [n, n_best, Tmax] int32, -1 past the cut;
         cap_len [n, n_best] int32), device tensors.  eos / pad: token ids, negative for none; eos_dev: a device word read instead
-        of eos.  `tokens` is left as it is."""
-        return ops.beam_captions(self.tokens, self.lengths, eos, pad, eos_dev=eos_dev)
+        of eos.  `tokens` is left as it is.  A group search's hypotheses are cut at their own group's length; the shapes follow
+        `tokens` ([n, G * n_best, Tmax] and [n, G * n_best])."""
+        if self.groups == 1:
+            return ops.beam_captions(self.tokens, self.lengths, eos, pad, eos_dev=eos_dev)
+        n, gk, Tmax = self.tokens.shape
+        P = n * self.groups
+        cap, cap_len = ops.beam_captions(self.tokens.reshape(P, gk // self.groups, Tmax), self.lengths.reshape(P), eos, pad, eos_dev=eos_dev)
+        return cap.view(n, gk, Tmax), cap_len.view(n, gk)
 
     def hypotheses(self):
         """[n][n_best] token lists, as collect_hypothesis_and_scores(inst_dec_beams, n_best) gives them -- the one place that
         copies to the host."""
         tok, lens = self.tokens.cpu().tolist(), self.lengths.cpu().tolist()
-        return [[row[:lens[i]] for row in inst] for i, inst in enumerate(tok)]
+        if self.groups == 1:
+            return [[row[:lens[i]] for row in inst] for i, inst in enumerate(tok)]
+        nb = self.tokens.shape[1] // self.groups
+        return [[row[:lens[i][j // nb]] for j, row in enumerate(inst)] for i, inst in enumerate(tok)]
 
 
 class CaptionBeamSearch:
@@ -79,7 +119,8 @@ class CaptionBeamSearch:
 
     NH = 12
 
-    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None, constraints=None):
+    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None, constraints=None, beam_groups=1,
+                 diversity_penalty=0.0):
         """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
         None: the UNIVL_AB key `beam_step` (default device).
         constraints: a constrain.DecodeConstraints (no repeated n-gram, a minimum length, suppressed ids) or None.  The session binds
@@ -87,13 +128,21 @@ class CaptionBeamSearch:
         the beam step, so both beam_step modes decode under the same constraints, and step_logprobs returns constrained rows PROVIDED
         positions are visited in order from 0 with `parents` given (the launch keeps each row's prefix up to date from them).  The
         minimum length counts against the `eos` of decode().  Every live row must keep n_bm finite columns: the caller's condition.
-        None adds no launch, no buffer and no plan entry."""
+        None adds no launch, no buffer and no plan entry.
+        beam_groups, diversity_penalty: Diverse Beam Search with G groups of n_bm // G beams (check_beam_groups states the rule).
+        1 (default) is the plain search: the same plans launch for launch, no new buffer, the penalty unused.  With G > 1 the last
+        launch of a position is univl_beam_group_step, `done` / `length` hold one entry per (instance, group), constraints see
+        done_stride = k', the penalty is a device word (set_diversity), and beam_step="host" is a ValueError: the host comparand
+        has no group form."""
+        self.G, self.kp, penalty = check_beam_groups(n_bm, beam_groups, diversity_penalty)
         if model.decoder is None:
             raise RuntimeError("CaptionBeamSearch: this model was built without a decoder (stage one)")
         if beam_step is None:
             beam_step = "device" if _ab.get("beam_step") else "host"
         if beam_step not in ("device", "host"):
             raise ValueError("CaptionBeamSearch: beam_step must be 'device' or 'host', got %r" % (beam_step,))
+        if self.G > 1 and beam_step != "device":
+            raise ValueError("CaptionBeamSearch: beam_groups=%d needs beam_step='device'; the host path has no group form" % self.G)
         self.beam_step = beam_step
         self.model, self.n_inst, self.W, self.F, self.n_bm = model, n_inst, W, F, n_bm
         self.use_graphs = bool(use_graphs)     # each step plan (one per position) is captured once into a hipGraph
@@ -132,17 +181,20 @@ class CaptionBeamSearch:
         # ---- beam state and history (read and written by univl_beam_step; the host path fills the same buffers)
         dev = cx.dev
         self.scores = torch.zeros(n_inst, n_bm, device=dev)
-        self.done = torch.zeros(n_inst, dtype=torch.uint8, device=dev)
-        self.length = torch.zeros(n_inst, dtype=torch.int32, device=dev)
+        G, P = self.G, n_inst * self.G                   # P: (instance, group) pairs, the pseudo-instances of width k'
+        self.done = torch.zeros(P, dtype=torch.uint8, device=dev)
+        self.length = torch.zeros(P, dtype=torch.int32, device=dev)
         self.hist_par = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
         self.hist_tok = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
         self.hist_sc = torch.zeros(Tmax, n_inst, n_bm, device=dev)
         self.eos_dev = torch.full((1,), -1, dtype=torch.int32, device=dev)     # a device word: the captured plans serve any eos
         self.ident = torch.arange(R, device=dev, dtype=torch.int32)
-        self.ident_nb = torch.arange(n_bm, device=dev, dtype=torch.int32).expand(n_inst, n_bm)
-        self.done_host = torch.zeros(n_inst, dtype=torch.uint8).pin_memory()
+        self.ident_nb = torch.arange(self.kp, device=dev, dtype=torch.int32).repeat(G).expand(n_inst, n_bm)      # parents are local to a group
+        self.done_host = torch.zeros(P, dtype=torch.uint8).pin_memory()
         self.done_event = torch.cuda.Event()
         self.beam_ws = ops.beam_ws(n_inst, n_bm, dev) if beam_step == "device" else None
+        if G > 1:
+            self.diversity_dev = torch.full((1,), penalty, dtype=torch.float32, device=dev)     # a device word: the captured plans serve any penalty
 
     # ------------------------------------------------------------------------------------------ step plans
     def _step_plan(self, t, beam=False):
@@ -211,8 +263,13 @@ class CaptionBeamSearch:
             c, prefix = self.constraints, self._prefix_buffers()
             pl.add("univl_decode_constrain", ops.decode_constrain_desc(
                 self.head.logits, self.V, t, prefix_in=prefix[(t + 1) % 2], prefix_out=prefix[t % 2], src=self.src, last=self.ids,
-                done=self.done, done_stride=self.n_bm, eos_dev=self.eos_dev, params_dev=c.params_dev, suppress=c.suppress_dev))
-        if beam:
+                done=self.done, done_stride=self.kp, eos_dev=self.eos_dev, params_dev=c.params_dev, suppress=c.suppress_dev))
+        if beam and self.G > 1:
+            pl.add("univl_beam_group_step", ops.beam_group_step_desc(
+                self.head.logits, self.V, self.n_inst, self.n_bm, self.G, t, scores=self.scores, done=self.done, length=self.length,
+                tokens=self.ids, src=self.src, hist_parents=self.hist_par, hist_tokens=self.hist_tok, hist_scores=self.hist_sc,
+                ws=self.beam_ws, diversity_dev=self.diversity_dev, eos_dev=self.eos_dev))
+        elif beam:
             pl.add("univl_beam_step", ops.beam_step_desc(
                 self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done, length=self.length,
                 tokens=self.ids, src=self.src, hist_parents=self.hist_par, hist_tokens=self.hist_tok, hist_scores=self.hist_sc,
@@ -226,6 +283,13 @@ class CaptionBeamSearch:
         if self.constraints is None:
             raise ValueError("set_constraints: this session was built with constraints=None; its plans carry no constraint launch")
         self.constraints.set(ngram=ngram, min_len=min_len)
+
+    def set_diversity(self, penalty):
+        """Rewrite the diversity penalty of a session built with beam_groups > 1.  It is a device word that the captured beam step
+        reads: nothing is captured again."""
+        if self.G == 1:
+            raise ValueError("set_diversity: this session was built with beam_groups=1; its plans carry no group step")
+        self.diversity_dev.fill_(check_beam_groups(self.n_bm, self.G, penalty)[2])
 
     @torch.no_grad()
     def step_logprobs(self, t, last_tokens, parents=None):
@@ -275,21 +339,21 @@ class CaptionBeamSearch:
     def decode(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None, n_best=1, sync_every=8,
                n_active=None):
         """Beam search over at most max_len positions; returns a BeamResult (device tensors).  n_best <= n_bm hypotheses per
-        instance.  sync_every: the host reads the done flags every that many positions to stop early (0: never, run to max_len);
+        instance; in a group search n_best <= k' is counted PER GROUP and the result is group-major (BeamResult).  sync_every: the host reads the done flags every that many positions to stop early (0: never, run to max_len);
         finished instances are frozen, so the result does not depend on it.  n_active: instances in this batch (class docstring);
         the result then has n_active instances."""
-        n, nb = self.n_inst, self.n_bm
+        n, nb, G, kp = self.n_inst, self.n_bm, self.G, self.kp
         m = self._active(n_active)
         max_len = min(int(max_len or self.Tmax), self.Tmax)
-        if not 1 <= int(n_best) <= nb:
-            raise ValueError("CaptionBeamSearch.decode: n_best=%r, expected 1 .. n_bm=%d" % (n_best, nb))
+        if not 1 <= int(n_best) <= kp:
+            raise ValueError("CaptionBeamSearch.decode: n_best=%r, expected 1 .. %s=%d" % (n_best, "n_bm" if G == 1 else "n_bm / beam_groups", kp))
         self.encode(sequence_output, visual_output, input_mask, video_mask, n_active=n_active)
         # state reset (outside the position loop)
         self.scores.zero_()
         self.done.zero_()
         self.length.zero_()
         if m < n:
-            self.done[m:].fill_(1)           # idle slots: done from the start, length 0
+            self.done[m * G:].fill_(1)       # idle slots: done from the start (every group), length 0
         self.ids.fill_(int(bos))
         self.src.copy_(self.ident)
         self.eos_dev.fill_(int(eos))
@@ -310,9 +374,16 @@ class CaptionBeamSearch:
             self.hist_par[ran:max_len] = self.ident_nb
             self.hist_tok[ran:max_len] = self.hist_tok[ran - 1]
             self.hist_sc[ran:max_len] = self.hist_sc[ran - 1]
-        tokens, scores = ops.beam_backtrack(self.hist_par, self.hist_tok, self.scores, self.length, int(n_best))
-        return BeamResult(tokens[:m], scores[:m], self.length[:m].clone(), self.hist_par[:max_len, :m].clone(),
-                          self.hist_tok[:max_len, :m].clone(), self.hist_sc[:max_len, :m].clone())
+        if G == 1:
+            tokens, scores = ops.beam_backtrack(self.hist_par, self.hist_tok, self.scores, self.length, int(n_best))
+            lengths = self.length[:m].clone()
+        else:                        # the walk-back on the (n * G, k') view: the history's parents are local to their group
+            tokens, scores = ops.beam_backtrack(self.hist_par.view(self.Tmax, n * G, kp), self.hist_tok.view(self.Tmax, n * G, kp),
+                                                self.scores.view(n * G, kp), self.length, int(n_best))
+            tokens, scores = tokens.view(n, G * int(n_best), self.Tmax), scores.view(n, G * int(n_best))
+            lengths = self.length.view(n, G)[:m].clone()
+        return BeamResult(tokens[:m], scores[:m], lengths, self.hist_par[:max_len, :m].clone(),
+                          self.hist_tok[:max_len, :m].clone(), self.hist_sc[:max_len, :m].clone(), groups=G)
 
     def _host_steps(self, max_len, eos):
         """beam_step="host": the bookkeeping as ATen calls on the device with one host read per position -- the arithmetic of the

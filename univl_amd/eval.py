@@ -131,7 +131,7 @@ class CaptionEvalResult:
 
 @torch.no_grad()
 def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, session=None, output_dir=None, nlg_eval=None,
-                 device="cuda", constraints=None):
+                 device="cuda", constraints=None, beam_groups=1, diversity_penalty=0.0):
     """Caption evaluation over a loader (main_task_caption.py:490-618).  batches: the reference loader's 12-tuples (:504-506);
     tokenizer: any object with vocab["[CLS]"], vocab["[SEP]"], vocab["[PAD]"] and convert_ids_to_tokens.  One CaptionBeamSearch,
     sized by the first batch (or the `session` passed in), decodes every batch; a smaller batch runs with n_active, a larger one is
@@ -139,11 +139,19 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
     hyp.txt and ref.txt are written there as :588-597 writes them.  nlg_eval: optional metric object (NLGEval).
     constraints: a constrain.DecodeConstraints for the session this call builds; together with a `session` it is a ValueError, because
     a session owns the constraints it was built with.
+    beam_groups, diversity_penalty: Diverse Beam Search for the session this call builds (decode.CaptionBeamSearch); with a `session`
+    they are a ValueError for the same reason.  With G > 1 groups n_best is counted per group, hyp_ids[item] holds G * n_best
+    hypotheses group-major, scores is [items, G * n_best] and lengths [items, G].  hyps / hyp.txt still get the best hypothesis of
+    group 0, which no penalty reaches: at ANY penalty that is the result of a plain beam search of width n_bm / G.
     Returns a CaptionEvalResult; for a stage-one model an empty one (float() == 0.0, :495) without decoding anything."""
-    from .decode import CaptionBeamSearch
+    from .decode import CaptionBeamSearch, check_beam_groups
     if session is not None and constraints is not None:
         raise ValueError("eval_caption: constraints= with a supplied session; the session already owns its constraints "
                          "(CaptionBeamSearch(..., constraints=))")
+    if session is not None and (beam_groups != 1 or diversity_penalty != 0.0):
+        raise ValueError("eval_caption: beam_groups= / diversity_penalty= with a supplied session; the session already owns them "
+                         "(CaptionBeamSearch(..., beam_groups=, diversity_penalty=))")
+    check_beam_groups(n_bm, beam_groups, diversity_penalty)
     if model._stage_one:
         return CaptionEvalResult([], [], [], torch.zeros(0, n_best), torch.zeros(0, dtype=torch.int32), None, None)
     bos, eos, pad = tokenizer.vocab["[CLS]"], tokenizer.vocab["[SEP]"], tokenizer.vocab["[PAD]"]
@@ -156,7 +164,8 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
             so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
             n = int(so.shape[0])
             if session is None:
-                session = CaptionBeamSearch(model, n, so.shape[1], vo.shape[1], n_bm=n_bm, max_len=max_len, constraints=constraints)
+                session = CaptionBeamSearch(model, n, so.shape[1], vo.shape[1], n_bm=n_bm, max_len=max_len, constraints=constraints,
+                                            beam_groups=beam_groups, diversity_penalty=diversity_penalty)
             if n > session.n_inst:
                 raise ValueError("eval_caption: a batch of %d items does not fit the decoding session's %d instances"
                                  % (n, session.n_inst))
@@ -166,7 +175,7 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
             # the one host copy of the batch: tokens, cut lengths, scores and lengths
             cap, cap_len, sc, ln = cap.cpu().tolist(), cap_len.cpu().tolist(), res.scores.cpu(), res.lengths.cpu()
             for i in range(n):
-                ids = [cap[i][k][:cap_len[i][k]] for k in range(n_best)]
+                ids = [cap[i][k][:cap_len[i][k]] for k in range(len(cap[i]))]
                 hyp_ids.append(ids)
                 hyps.append(ids_to_caption(tokenizer, ids[0]))
             scores.append(sc)

@@ -389,6 +389,38 @@ def beam_step(*a, **kw):
     _lib.check(_lib.lib().univl_beam_step(_BYREF(d), _stream()), "beam_step")
 
 
+def beam_group_step_desc(lp, V, n_inst, n_bm, n_groups, t, *, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws,
+                         diversity=0.0, diversity_dev=None, eos=-1, eos_dev=None, first_step=None):
+    """beam_step_desc for n_groups groups of n_bm // n_groups beams (include/univl_hip.h: UnivlBeamGroupStep): done and length have
+    n_inst * n_groups entries, one per (instance, group); diversity_dev: fp32 device word read instead of diversity.  ws: beam_ws(n_inst,
+    n_bm).  Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
+    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev, diversity_dev)
+    R, P = n_inst * n_bm, n_inst * n_groups
+    assert lp.dtype == torch.float32 and lp.dim() == 2 and lp.stride(1) == 1 and lp.shape[0] >= R
+    assert scores.dtype == torch.float32 and scores.numel() == R and scores.is_contiguous()
+    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == P and done.is_contiguous()
+    assert length.dtype == torch.int32 and length.numel() == P and length.is_contiguous()
+    assert tokens.dtype == torch.int64 and tokens.numel() == R and src.dtype == torch.int32 and src.numel() == R
+    Tmax = hist_parents.shape[0]
+    for h, dt_ in ((hist_parents, torch.int32), (hist_tokens, torch.int32), (hist_scores, torch.float32)):
+        assert h.dtype == dt_ and h.is_contiguous() and h.shape[0] == Tmax and h.numel() == Tmax * R
+    assert eos_dev is None or eos_dev.dtype == torch.int32
+    assert diversity_dev is None or (diversity_dev.dtype == torch.float32 and diversity_dev.numel() == 1)
+    d = _lib.BeamGroupStep()
+    d.lp, d.ld, d.n_inst, d.n_bm, d.V = _p(lp), lp.stride(0), n_inst, n_bm, V
+    d.first_step, d.eos, d.eos_dev, d.t, d.Tmax = int(t == 0 if first_step is None else first_step), int(eos), _p(eos_dev), t, Tmax
+    d.scores, d.done, d.length, d.tokens, d.src = _p(scores), _p(done), _p(length), _p(tokens), _p(src)
+    d.hist_parents, d.hist_tokens, d.hist_scores = _p(hist_parents), _p(hist_tokens), _p(hist_scores)
+    d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
+    d.n_groups, d.diversity, d.diversity_dev = int(n_groups), float(diversity), _p(diversity_dev)
+    return d
+
+
+def beam_group_step(*a, **kw):
+    d = beam_group_step_desc(*a, **kw)
+    _lib.check(_lib.lib().univl_beam_group_step(_BYREF(d), _stream()), "beam_group_step")
+
+
 def sample_ws(R, k, device):
     """Scratch of univl_sample_step for R rows and a top-k of k (include/univl_hip.h: UnivlSampleStep.ws)."""
     return torch.empty(R * _lib.SAMPLE_SLICES * (2 * k + 4), dtype=torch.float32, device=device)
