@@ -754,6 +754,28 @@ def test_plan_ops_still_read_by_position_like_the_tuples_they_replace():
         ops_[0][5]
 
 
+def test_caption_sessions_share_the_instance_session_half():
+    """steps.InstanceSession states n_active and the graph-or-eager replay once for the beam search, the sampler and the scorer: the
+    three classes hold the SAME function objects, and an n_active outside 1 .. n_inst is a ValueError that names the concrete class."""
+    from univl_amd.decode import CachedDecoder, CaptionBeamSearch
+    from univl_amd.sample import CaptionSampler
+    from univl_amd.score import CaptionScorer
+    from univl_amd.steps import InstanceSession
+    classes = (CaptionBeamSearch, CaptionSampler, CaptionScorer)
+    for cls in classes:
+        ses = object.__new__(cls)            # a stand-in: no model, no device
+        ses.n_inst = 4
+        assert ses._active(None) == 4 and ses._active(1) == 1 and ses._active(4) == 4
+        for bad in (0, 5):
+            with pytest.raises(ValueError, match="^%s: n_active=%d" % (cls.__name__, bad)):
+                ses._active(bad)
+        assert cls._active is InstanceSession._active and cls._replay is InstanceSession._replay
+        assert cls.load_features is InstanceSession.load_features
+    assert issubclass(CaptionBeamSearch, CachedDecoder) and issubclass(CaptionSampler, CachedDecoder)
+    assert not issubclass(CaptionSampler, CaptionBeamSearch) and not issubclass(CaptionScorer, CachedDecoder)
+    assert CaptionBeamSearch._run_positions is CaptionSampler._run_positions is CachedDecoder._run_positions
+
+
 def test_head_transform_and_loss_forms_are_stated_once():
     """steps.HeadTransform serves the MLM head and the visual head of the pretrain step: the two transform launches of the forward and the
     transform's backward tail (LayerNorm backward, gelu_bwd, weight gradient with its dbias, dgrad) carry the same names and, pointers

@@ -565,6 +565,24 @@ def test_seeds_and_sync_every():
         smp.sample(*enc, bos=BOS, eos=eos, seed=7, top_p=0.0)
 
 
+def test_sampler_owns_no_beam_state_and_no_beam_form():
+    """The sampler is a decode.CachedDecoder beside CaptionBeamSearch, not under it: no beam score, history or beam workspace exists on
+    it, its plans are of the forms "logits" and "sample" only, and a request for any other form is an error that builds nothing."""
+    smp = _sampler(torch.float32, 3)
+    enc = _toy(torch.float32)[2][0]
+    smp.sample(*enc, bos=BOS, eos=-1, seed=3)
+    smp.step_logits(0, torch.full((3 * N_SAMP,), BOS, dtype=torch.int64, device=DEV))
+    assert not isinstance(smp, CaptionBeamSearch)
+    for name in ("hist_par", "hist_tok", "hist_sc", "beam_ws", "scores", "ident_nb"):
+        assert not hasattr(smp, name), name
+    keys = set(smp.steps)
+    assert {form for _, form in keys} == {"logits", "sample"}
+    for form in (True, False, "beam", None):
+        with pytest.raises(ValueError, match="CaptionSampler"):
+            smp._step_plan(0, form)
+    assert set(smp.steps) == keys
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_partial_batches(dtype):
     """E (iii).  n_active = 2 of 3 after two different full batches went through the session (two kinds of stale contents in the idle

@@ -32,6 +32,12 @@ Same results as the reference's procedure on the same logits: first step uses be
 an instance is done when its top beam emits EOS (beam.py:84), the reported hypotheses are the n_best best-scored beams walked
 back through the back-pointers (beam.py:108-116, collect_hypothesis_and_scores).  Candidates of exactly equal fp32 value
 are ordered by lower flat index first in the device path (include/univl_hip.h); torch.topk leaves that order open.
+
+Three layers, each naming what it owns:
+  steps.InstanceSession   the cross encoder over n_inst instances on supplied features, idle slots, n_active, graph-or-eager replay
+                          (score.CaptionScorer builds on this layer alone);
+  CachedDecoder           the row decoder: encoder K/V, the per-row cache, the (position, form) plans, the loop over the positions;
+  CaptionBeamSearch       the beam state, its history and the beam step (sample.CaptionSampler: the sampling state and the sample step).
 """
 import math
 
@@ -39,7 +45,7 @@ import torch
 
 from . import _ab, ops
 from .engine import DecoderLayer, DecoderStack, Plan, _gemm_desc
-from .steps import EvalSession, VocabHead, H
+from .steps import InstanceSession, VocabHead, H
 
 
 def check_beam_groups(n_bm, beam_groups=1, diversity_penalty=0.0):
@@ -87,130 +93,78 @@ class BeamResult:
         cap_len [n, n_best] int32), device tensors.  eos / pad: token ids, negative for none; eos_dev: a device word read instead
         of eos.  `tokens` is left as it is.  A group search's hypotheses are cut at their own group's length; the shapes follow
         `tokens` ([n, G * n_best, Tmax] and [n, G * n_best])."""
-        if self.groups == 1:
-            return ops.beam_captions(self.tokens, self.lengths, eos, pad, eos_dev=eos_dev)
         n, gk, Tmax = self.tokens.shape
-        P = n * self.groups
+        P = n * self.groups                  # the (instance, group) view; groups = 1: the tensors as they are
         cap, cap_len = ops.beam_captions(self.tokens.reshape(P, gk // self.groups, Tmax), self.lengths.reshape(P), eos, pad, eos_dev=eos_dev)
         return cap.view(n, gk, Tmax), cap_len.view(n, gk)
 
     def hypotheses(self):
         """[n][n_best] token lists, as collect_hypothesis_and_scores(inst_dec_beams, n_best) gives them -- the one place that
         copies to the host."""
-        tok, lens = self.tokens.cpu().tolist(), self.lengths.cpu().tolist()
-        if self.groups == 1:
-            return [[row[:lens[i]] for row in inst] for i, inst in enumerate(tok)]
-        nb = self.tokens.shape[1] // self.groups
+        n, gk, _ = self.tokens.shape
+        tok, lens = self.tokens.cpu().tolist(), self.lengths.reshape(n, self.groups).cpu().tolist()
+        nb = gk // self.groups
         return [[row[:lens[i][j // nb]] for j, row in enumerate(inst)] for i, inst in enumerate(tok)]
 
 
-class CaptionBeamSearch:
-    """Compiled decoding session for a fixed (n_inst, max_words W, max_frames F, beam size, max_len).
-
-    Partial batches: encode() / decode() / __call__ take n_active (None: n_inst), the number of instances the call carries; the
-    feature and mask tensors then have n_active rows.  Slots [0, n_active) carry the batch, slots [n_active, n_inst) are IDLE: their
-    `done` byte is preset to 1 and their `length` to 0 before position 0, so the beam scan skips them and the select kernel writes
-    frozen rows for them, as both do for an instance that has finished.  The launch shapes do not change, so a loader's short last
-    batch replays the plans and hipGraphs of the full ones: no second session, no new capture.  The decoder plans still run over
-    the idle rows, so what they read there must be defined and finite: the feature and mask slots are zero-filled once at
-    construction, and after that an idle slot simply keeps what an earlier batch left in it.  No launch reduces across instances
-    (DESIGN.md section 7), so the active instances' results do not depend on it.  The BeamResult holds the first n_active
-    instances only."""
+class CachedDecoder(InstanceSession):
+    """The cached row decoder over an InstanceSession: R = n_inst * n_rows rows (the n_rows rows of an instance share its encoder K/V),
+    the per-layer encoder K/V computed once per batch (encode()), a self-attention cache per row, and one plan per (position, form),
+    replayed as a hipGraph.  A subclass names its forms and says per form whether rows change places between positions
+    (_reorders(form)) and what follows the vocabulary classifier (_plan_tail(pl, t, form)); it owns the state its tails read and write
+    and resets it before _run_positions, the one loop over the positions."""
 
     NH = 12
+    FORMS = ()           # the subclass's plan forms; a plan's key in self.steps is (t, form)
 
-    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None, constraints=None, beam_groups=1,
-                 diversity_penalty=0.0):
-        """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
-        None: the UNIVL_AB key `beam_step` (default device).
-        constraints: a constrain.DecodeConstraints (no repeated n-gram, a minimum length, suppressed ids) or None.  The session binds
-        a copy (self.constraints) and adds ONE launch, univl_decode_constrain, to every position's plan between the log-softmax and
-        the beam step, so both beam_step modes decode under the same constraints, and step_logprobs returns constrained rows PROVIDED
-        positions are visited in order from 0 with `parents` given (the launch keeps each row's prefix up to date from them).  The
-        minimum length counts against the `eos` of decode().  Every live row must keep n_bm finite columns: the caller's condition.
-        None adds no launch, no buffer and no plan entry.
-        beam_groups, diversity_penalty: Diverse Beam Search with G groups of n_bm // G beams (check_beam_groups states the rule).
-        1 (default) is the plain search: the same plans launch for launch, no new buffer, the penalty unused.  With G > 1 the last
-        launch of a position is univl_beam_group_step, `done` / `length` hold one entry per (instance, group), constraints see
-        done_stride = k', the penalty is a device word (set_diversity), and beam_step="host" is a ValueError: the host comparand
-        has no group form."""
-        self.G, self.kp, penalty = check_beam_groups(n_bm, beam_groups, diversity_penalty)
-        if model.decoder is None:
-            raise RuntimeError("CaptionBeamSearch: this model was built without a decoder (stage one)")
-        if beam_step is None:
-            beam_step = "device" if _ab.get("beam_step") else "host"
-        if beam_step not in ("device", "host"):
-            raise ValueError("CaptionBeamSearch: beam_step must be 'device' or 'host', got %r" % (beam_step,))
-        if self.G > 1 and beam_step != "device":
-            raise ValueError("CaptionBeamSearch: beam_groups=%d needs beam_step='device'; the host path has no group form" % self.G)
-        self.beam_step = beam_step
-        self.model, self.n_inst, self.W, self.F, self.n_bm = model, n_inst, W, F, n_bm
-        self.use_graphs = bool(use_graphs)     # each step plan (one per position) is captured once into a hipGraph
+    def __init__(self, model, n_inst, W, F, n_rows, n_done, max_len=None, use_graphs=True, constraints=None):
+        """n_done: the length of the done buffer that _run_positions polls.
+        constraints: a constrain.DecodeConstraints or None.  The session binds a copy (self.constraints); the subclass's _plan_tail adds
+        ONE launch, univl_decode_constrain, in front of its selection kernel.  None adds no launch, no buffer and no plan entry."""
         self.Tmax = Tmax = int(max_len or model.task_config.max_words)
         assert Tmax <= model.decoder_config.max_target_embeddings
         if constraints is not None:          # validated against this session before any device work
             constraints = constraints.bind(model.bert_config.vocab_size, Tmax, next(model.parameters()).device)
         self.constraints = constraints
-        model.flat.refresh_shadow()
-        self.R = R = n_inst * n_bm
-        self.V = V = model.bert_config.vocab_size
+        super().__init__(model, n_inst, W, F, use_graphs)
+        self.n_rows = n_rows
+        self.R = R = n_inst * n_rows
+        self.V = model.bert_config.vocab_size
         self.L = L = model.decoder_config.num_decoder_layers
-        rows = list(range(n_inst))
-        # ---- once per batch: cross encoder per instance + encoder K/V of every decoder layer
-        ses = EvalSession(model, n_inst, n_inst, W, F, rows, rows)
-        cx, self.feats, self.run, self.setup = ses.cx, ses.feats, ses.run, ses.plan
-        self.cx, e, ct, bf, fl, dt = cx, cx.e, cx.ct, cx.bf, cx.fl, cx.dt
-        for buf in (self.feats.seq_out, self.feats.vis_out, self.feats.amask, self.feats.vmask):
-            buf.zero_()                                  # idle slots of a partial first batch read these (class docstring)
-        self.S = S = self.run.S
+        cx, S = self.cx, self.S
+        e, ct, fl, dt = cx.e, cx.ct, cx.fl, cx.dt
+        # ---- once per batch, after the cross encoder: encoder K/V of every decoder layer
         self.kv2 = [e(n_inst * S, 2 * H, dtype=ct) for _ in range(L)]
         for l in range(L):
             nm = DecoderStack._names(l)
-            self.setup.add("univl_gemm", _gemm_desc(dt, self.run.out16, H, fl.wop_fused(nm["c_kv_w"]), H, n_inst * S, 2 * H, H,
-                                                    out16=self.kv2[l], ldc=2 * H, bias=fl.w32_fused(nm["c_kv_b"])))
+            self.plan.add("univl_gemm", _gemm_desc(dt, self.run.out16, H, fl.wop_fused(nm["c_kv_w"]), H, n_inst * S, 2 * H, H,
+                                                   out16=self.kv2[l], ldc=2 * H, bias=fl.w32_fused(nm["c_kv_b"])))
         # ---- per step buffers (R rows)
         self.ids = e(R, dtype=torch.int64)
         self.ey, self.est, self.e32 = e(R, H), e(R, 2), e(R, H)
-        self.e16 = e(R, H, dtype=ct) if bf else self.e32
+        self.e16 = e(R, H, dtype=ct) if cx.bf else self.e32
         self.cache = [[torch.zeros(R, Tmax, 2 * H, device=cx.dev, dtype=ct) for _ in range(2)] for _ in range(L)]
         self.ws = [dict(DecoderStack.layer_workspace(e, ct, R), q1=e(R, H, dtype=ct)) for _ in range(L)]
         self.head = VocabHead(cx, "decoder.classifier.cls.predictions", R)
-        self.src = e(R, dtype=torch.int32)               # cache row each beam continues from
+        self.src = e(R, dtype=torch.int32)               # cache row each row continues from (forms that reorder)
         self.steps = {}
-        self.base = torch.arange(n_inst, device=cx.dev, dtype=torch.int64)[:, None] * n_bm
-        # ---- beam state and history (read and written by univl_beam_step; the host path fills the same buffers)
-        dev = cx.dev
-        self.scores = torch.zeros(n_inst, n_bm, device=dev)
-        G, P = self.G, n_inst * self.G                   # P: (instance, group) pairs, the pseudo-instances of width k'
-        self.done = torch.zeros(P, dtype=torch.uint8, device=dev)
-        self.length = torch.zeros(P, dtype=torch.int32, device=dev)
-        self.hist_par = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
-        self.hist_tok = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
-        self.hist_sc = torch.zeros(Tmax, n_inst, n_bm, device=dev)
-        self.eos_dev = torch.full((1,), -1, dtype=torch.int32, device=dev)     # a device word: the captured plans serve any eos
-        self.ident = torch.arange(R, device=dev, dtype=torch.int32)
-        self.ident_nb = torch.arange(self.kp, device=dev, dtype=torch.int32).repeat(G).expand(n_inst, n_bm)      # parents are local to a group
-        self.done_host = torch.zeros(P, dtype=torch.uint8).pin_memory()
+        self.eos_dev = torch.full((1,), -1, dtype=torch.int32, device=cx.dev)     # a device word: the captured plans serve any eos
+        self.done_host = torch.zeros(n_done, dtype=torch.uint8).pin_memory()
         self.done_event = torch.cuda.Event()
-        self.beam_ws = ops.beam_ws(n_inst, n_bm, dev) if beam_step == "device" else None
-        if G > 1:
-            self.diversity_dev = torch.full((1,), penalty, dtype=torch.float32, device=dev)     # a device word: the captured plans serve any penalty
 
     # ------------------------------------------------------------------------------------------ step plans
-    def _step_plan(self, t, beam=False):
-        """The plan of position t.  beam=False: embedding .. log-probabilities (what step_logprobs replays; it neither reads nor
-        advances the beam state).  beam=True: a second captured form of the same launches with univl_beam_step as its last entry
-        (t, the history row and first_step are baked into that position's descriptor).  A subclass may name further forms
-        (sample.CaptionSampler): _reorders(form) says whether rows change places between positions, _plan_tail(pl, t, form) adds
-        what follows the vocabulary classifier."""
-        pl = self.steps.get((t, beam))
+    def _step_plan(self, t, form):
+        """The plan of position t in one of the subclass's forms: embedding .. vocabulary classifier, then _plan_tail."""
+        pl = self.steps.get((t, form))
         if pl is not None:
             return pl
+        if form not in self.FORMS:
+            raise ValueError("%s: no plan form %r, expected one of %r" % (type(self).__name__, form, self.FORMS))
         cx, fl, dt, R, Tmax, S = self.cx, self.cx.fl, self.cx.dt, self.R, self.Tmax, self.S
         W32 = fl.w32
         es = 2 if cx.bf else 4
         pl = Plan()
-        reorder = self._reorders(beam)
+        reorder = self._reorders(form)
         cur, prev = (t % 2, (t + 1) % 2) if reorder else (0, 0)     # rows that stay where they are need one cache buffer and no gather
         pos = W32("bert.embeddings.position_embeddings.weight")[t:]
         pl.add("univl_embed_text_fwd", ops.embed_text_desc(
@@ -223,8 +177,8 @@ class CaptionBeamSearch:
             lay = DecoderLayer(pl, fl, l, ws, R)
             nm = lay.nm
             cache = self.cache[l][cur]
-            if t > 0 and reorder:        # beams continue from re-ordered parents: gather positions [0, t) of the parent rows
-                src_c, n_rows, stride, nbytes = self.cache[l][prev], R, Tmax * 2 * H * es, t * 2 * H * es
+            if t > 0 and reorder:        # rows continue from re-ordered parents: gather positions [0, t) of the parent rows
+                src_c, stride, nbytes = self.cache[l][prev], Tmax * 2 * H * es, t * 2 * H * es
                 pl.add_callable(lambda s=src_c, d=cache, st=stride, nb=nbytes: ops.gather_rows(s, d, self.src, R, st, nb))
             wqkv, bqkv = fl.wop_fused(nm["s_qkv_w"]), fl.w32_fused(nm["s_qkv_b"])
             pl.add("univl_gemm", _gemm_desc(dt, x16, H, wqkv[:H], H, R, H, H, out16=ws["q1"], ldc=H, bias=bqkv[:H]))
@@ -235,45 +189,30 @@ class CaptionBeamSearch:
                 bsk=Tmax * 2 * H, bsv=Tmax * 2 * H))
             lay.attn_output("s_", x32)
             lay.enc_query()
-            lay.enc_attention(self.n_inst, self.n_bm, S, self.kv2[l], self.run.cmask)
+            lay.enc_attention(self.n_inst, self.n_rows, S, self.kv2[l], self.run.cmask)
             lay.attn_output("c_", ws["a32"])
             lay.ffn()
             x32, x16 = ws["o32"], ws["o16"]
         self.head.build_forward(pl, x16, with_loss=False)
-        self._plan_tail(pl, t, beam)
+        self._plan_tail(pl, t, form)
         pl.keepalive = (pos,)
-        self.steps[(t, beam)] = pl
+        self.steps[(t, form)] = pl
         return pl
 
     def _reorders(self, form):
-        return True
+        raise NotImplementedError
+
+    def _plan_tail(self, pl, t, form):
+        raise NotImplementedError
 
     def _prefix_buffers(self):
         """Each row's emitted tokens, two [R, Tmax] int32 buffers used with parity t % 2 like self.cache (rows change places between
-        positions).  Allocated when the first plan that reorders rows is built -- plans are built outside any capture -- so a session
-        that never builds one (CaptionSampler's "sample" form reads its own tokens_out) has none.  Zero-filled: the rows of idle slots
-        are copied along, from defined memory."""
+        positions).  Allocated when the first plan that needs them is built -- plans are built outside any capture -- so a session
+        whose rows stay in place (CaptionSampler reads its own tokens_out) has none.  Zero-filled: the rows of idle slots are copied
+        along, from defined memory."""
         if not hasattr(self, "prefix"):
             self.prefix = [torch.zeros(self.R, self.Tmax, dtype=torch.int32, device=self.cx.dev) for _ in range(2)]
         return self.prefix
-
-    def _plan_tail(self, pl, t, beam):
-        pl.add_callable(lambda: ops.log_softmax_rows(self.head.logits, self.V))
-        if self.constraints is not None:
-            c, prefix = self.constraints, self._prefix_buffers()
-            pl.add("univl_decode_constrain", ops.decode_constrain_desc(
-                self.head.logits, self.V, t, prefix_in=prefix[(t + 1) % 2], prefix_out=prefix[t % 2], src=self.src, last=self.ids,
-                done=self.done, done_stride=self.kp, eos_dev=self.eos_dev, params_dev=c.params_dev, suppress=c.suppress_dev))
-        if beam and self.G > 1:
-            pl.add("univl_beam_group_step", ops.beam_group_step_desc(
-                self.head.logits, self.V, self.n_inst, self.n_bm, self.G, t, scores=self.scores, done=self.done, length=self.length,
-                tokens=self.ids, src=self.src, hist_parents=self.hist_par, hist_tokens=self.hist_tok, hist_scores=self.hist_sc,
-                ws=self.beam_ws, diversity_dev=self.diversity_dev, eos_dev=self.eos_dev))
-        elif beam:
-            pl.add("univl_beam_step", ops.beam_step_desc(
-                self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done, length=self.length,
-                tokens=self.ids, src=self.src, hist_parents=self.hist_par, hist_tokens=self.hist_tok, hist_scores=self.hist_sc,
-                ws=self.beam_ws, eos_dev=self.eos_dev))
 
     # ------------------------------------------------------------------------------------------------- run
     def set_constraints(self, ngram=None, min_len=None):
@@ -284,6 +223,100 @@ class CaptionBeamSearch:
             raise ValueError("set_constraints: this session was built with constraints=None; its plans carry no constraint launch")
         self.constraints.set(ngram=ngram, min_len=min_len)
 
+    @torch.no_grad()
+    def encode(self, sequence_output, visual_output, input_mask, video_mask, n_active=None):
+        self.load_features(sequence_output, visual_output, input_mask, video_mask, self._active(n_active), "encode")
+        self.plan.run()
+
+    def _run_positions(self, form, max_len, sync_every, done):
+        """One replay of the form's plan per position 0 .. max_len-1; returns the number of positions run.  Every sync_every positions
+        (0: never) the host reads the `done` bytes through the pinned buffer and an event wait -- the only host read of the loop -- and
+        stops when all are set.  Finished rows are frozen by the tails, so the result does not depend on when the host looks."""
+        for t in range(max_len):
+            self._replay(self._step_plan(t, form))
+            if sync_every and (t + 1) % sync_every == 0 and t + 1 < max_len:
+                self.done_host.copy_(done, non_blocking=True)
+                self.done_event.record()
+                self.done_event.synchronize()
+                if bool(self.done_host.all()):
+                    return t + 1
+        return max_len
+
+
+class CaptionBeamSearch(CachedDecoder):
+    """Compiled decoding session for a fixed (n_inst, max_words W, max_frames F, beam size, max_len): the beam state, its history and
+    the beam step as the tail of CachedDecoder's plans.  The forms are True (embedding .. log-probabilities .. univl_beam_step, with t,
+    the history row and first_step baked into that position's descriptor; what decode() replays) and False (the same launches without
+    the beam step: what step_logprobs replays; it neither reads nor advances the beam state).  Rows change places in both.
+
+    Partial batches (steps.InstanceSession): encode() / decode() / __call__ take n_active.  The `done` byte of an idle slot is preset
+    to 1 and its `length` to 0 before position 0, so the beam scan skips it and the select kernel writes frozen rows for it, as both do
+    for an instance that has finished.  The BeamResult holds the first n_active instances only."""
+
+    def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None, constraints=None, beam_groups=1,
+                 diversity_penalty=0.0):
+        """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
+        None: the UNIVL_AB key `beam_step` (default device).
+        constraints: a constrain.DecodeConstraints (no repeated n-gram, a minimum length, suppressed ids) or None.  The launch sits
+        between the log-softmax and the beam step, so both beam_step modes decode under the same constraints, and step_logprobs returns
+        constrained rows PROVIDED positions are visited in order from 0 with `parents` given (the launch keeps each row's prefix up to
+        date from them).  The minimum length counts against the `eos` of decode().  Every live row must keep n_bm finite columns: the
+        caller's condition.
+        beam_groups, diversity_penalty: Diverse Beam Search with G groups of n_bm // G beams (check_beam_groups states the rule).
+        1 (default) is the plain search: the same plans launch for launch, no new buffer, the penalty unused.  With G > 1 the last
+        launch of a position is univl_beam_group_step, `done` / `length` hold one entry per (instance, group), constraints see
+        done_stride = k', the penalty is a device word (set_diversity), and beam_step="host" is a ValueError: the host comparand
+        has no group form."""
+        self.G, self.kp, penalty = check_beam_groups(n_bm, beam_groups, diversity_penalty)
+        G, kp = self.G, self.kp
+        if beam_step is None:
+            beam_step = "device" if _ab.get("beam_step") else "host"
+        if beam_step not in ("device", "host"):
+            raise ValueError("CaptionBeamSearch: beam_step must be 'device' or 'host', got %r" % (beam_step,))
+        if G > 1 and beam_step != "device":
+            raise ValueError("CaptionBeamSearch: beam_groups=%d needs beam_step='device'; the host path has no group form" % G)
+        self.beam_step, self.n_bm = beam_step, n_bm
+        P = n_inst * G                                   # (instance, group) pairs, the pseudo-instances of width k'
+        super().__init__(model, n_inst, W, F, n_bm, P, max_len=max_len, use_graphs=use_graphs, constraints=constraints)
+        dev, R, Tmax = self.cx.dev, self.R, self.Tmax
+        # ---- beam state and history (read and written by univl_beam_step; the host path fills the same buffers)
+        self.scores = torch.zeros(n_inst, n_bm, device=dev)
+        self.done = torch.zeros(P, dtype=torch.uint8, device=dev)
+        self.length = torch.zeros(P, dtype=torch.int32, device=dev)
+        self.hist_par = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
+        self.hist_tok = torch.zeros(Tmax, n_inst, n_bm, dtype=torch.int32, device=dev)
+        self.hist_sc = torch.zeros(Tmax, n_inst, n_bm, device=dev)
+        self.base = torch.arange(n_inst, device=dev, dtype=torch.int64)[:, None] * n_bm
+        self.ident = torch.arange(R, device=dev, dtype=torch.int32)
+        self.ident_nb = torch.arange(kp, device=dev, dtype=torch.int32).repeat(G).expand(n_inst, n_bm)      # parents are local to a group
+        self.beam_ws = ops.beam_ws(n_inst, n_bm, dev) if beam_step == "device" else None
+        if G > 1:
+            self.diversity_dev = torch.full((1,), penalty, dtype=torch.float32, device=dev)     # a device word: the captured plans serve any penalty
+
+    # ------------------------------------------------------------------------------------------ step plans
+    FORMS = (False, True)
+
+    def _reorders(self, beam):
+        return True
+
+    def _plan_tail(self, pl, t, beam):
+        pl.add_callable(lambda: ops.log_softmax_rows(self.head.logits, self.V))
+        if self.constraints is not None:
+            c, prefix = self.constraints, self._prefix_buffers()
+            pl.add("univl_decode_constrain", ops.decode_constrain_desc(
+                self.head.logits, self.V, t, prefix_in=prefix[(t + 1) % 2], prefix_out=prefix[t % 2], src=self.src, last=self.ids,
+                done=self.done, done_stride=self.kp, eos_dev=self.eos_dev, params_dev=c.params_dev, suppress=c.suppress_dev))
+        if not beam:
+            return
+        state = dict(scores=self.scores, done=self.done, length=self.length, tokens=self.ids, src=self.src, hist_parents=self.hist_par,
+                     hist_tokens=self.hist_tok, hist_scores=self.hist_sc, ws=self.beam_ws, eos_dev=self.eos_dev)
+        if self.G > 1:
+            pl.add("univl_beam_group_step", ops.beam_group_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, self.G, t,
+                                                                     diversity_dev=self.diversity_dev, **state))
+        else:
+            pl.add("univl_beam_step", ops.beam_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, t, **state))
+
+    # ------------------------------------------------------------------------------------------------- run
     def set_diversity(self, penalty):
         """Rewrite the diversity penalty of a session built with beam_groups > 1.  It is a device word that the captured beam step
         reads: nothing is captured again."""
@@ -302,38 +335,8 @@ class CaptionBeamSearch:
         self.ids.copy_(last_tokens.reshape(-1))
         if t > 0:
             self.src.copy_(parents.reshape(-1).to(torch.int32))
-        pl = self._step_plan(t)
-        if self.use_graphs and not torch.cuda.is_current_stream_capturing():
-            pl.run_graphed()
-        else:
-            pl.run()
+        self._replay(self._step_plan(t, False))
         return self.head.logits[:, :self.V]
-
-    @torch.no_grad()
-    def _active(self, n_active):
-        if n_active is None:
-            return self.n_inst
-        if not 1 <= int(n_active) <= self.n_inst:
-            raise ValueError("CaptionBeamSearch: n_active=%r, expected 1 .. n_inst=%d" % (n_active, self.n_inst))
-        return int(n_active)
-
-    @torch.no_grad()
-    def encode(self, sequence_output, visual_output, input_mask, video_mask, n_active=None):
-        m = self._active(n_active)
-        if sequence_output.shape[0] != m or visual_output.shape[0] != m:
-            raise ValueError("CaptionBeamSearch.encode: features of %d / %d instances, expected %d"
-                             % (sequence_output.shape[0], visual_output.shape[0], m))
-        self.model.flat.refresh_shadow()
-        self.feats.load(sequence_output.to(torch.float32), visual_output.to(torch.float32),
-                        input_mask.reshape(-1, input_mask.shape[-1]), video_mask.reshape(-1, video_mask.shape[-1]), rows=m)
-        self.setup.run()
-
-    def _all_done(self):
-        """The n done bytes through a pinned buffer and an event wait (the only host read of the device path's loop)."""
-        self.done_host.copy_(self.done, non_blocking=True)
-        self.done_event.record()
-        self.done_event.synchronize()
-        return bool(self.done_host.all())
 
     @torch.no_grad()
     def decode(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, max_len=None, n_best=1, sync_every=8,
@@ -342,10 +345,10 @@ class CaptionBeamSearch:
         instance; in a group search n_best <= k' is counted PER GROUP and the result is group-major (BeamResult).  sync_every: the host reads the done flags every that many positions to stop early (0: never, run to max_len);
         finished instances are frozen, so the result does not depend on it.  n_active: instances in this batch (class docstring);
         the result then has n_active instances."""
-        n, nb, G, kp = self.n_inst, self.n_bm, self.G, self.kp
+        n, G, kp, Tmax, n_best = self.n_inst, self.G, self.kp, self.Tmax, int(n_best)
         m = self._active(n_active)
-        max_len = min(int(max_len or self.Tmax), self.Tmax)
-        if not 1 <= int(n_best) <= kp:
+        max_len = min(int(max_len or Tmax), Tmax)
+        if not 1 <= n_best <= kp:
             raise ValueError("CaptionBeamSearch.decode: n_best=%r, expected 1 .. %s=%d" % (n_best, "n_bm" if G == 1 else "n_bm / beam_groups", kp))
         self.encode(sequence_output, visual_output, input_mask, video_mask, n_active=n_active)
         # state reset (outside the position loop)
@@ -357,32 +360,20 @@ class CaptionBeamSearch:
         self.ids.fill_(int(bos))
         self.src.copy_(self.ident)
         self.eos_dev.fill_(int(eos))
-        ran = max_len
         if self.beam_step == "device":
-            for t in range(max_len):
-                pl = self._step_plan(t, beam=True)
-                if self.use_graphs and not torch.cuda.is_current_stream_capturing():
-                    pl.run_graphed()
-                else:
-                    pl.run()
-                if sync_every and (t + 1) % sync_every == 0 and t + 1 < max_len and self._all_done():
-                    ran = t + 1
-                    break
+            ran = self._run_positions(True, max_len, sync_every, self.done)
         else:
             ran = self._host_steps(max_len, int(eos))
         if ran < max_len:            # every instance is done: the rows not run are the frozen rows the kernel would have written
             self.hist_par[ran:max_len] = self.ident_nb
             self.hist_tok[ran:max_len] = self.hist_tok[ran - 1]
             self.hist_sc[ran:max_len] = self.hist_sc[ran - 1]
-        if G == 1:
-            tokens, scores = ops.beam_backtrack(self.hist_par, self.hist_tok, self.scores, self.length, int(n_best))
-            lengths = self.length[:m].clone()
-        else:                        # the walk-back on the (n * G, k') view: the history's parents are local to their group
-            tokens, scores = ops.beam_backtrack(self.hist_par.view(self.Tmax, n * G, kp), self.hist_tok.view(self.Tmax, n * G, kp),
-                                                self.scores.view(n * G, kp), self.length, int(n_best))
-            tokens, scores = tokens.view(n, G * int(n_best), self.Tmax), scores.view(n, G * int(n_best))
-            lengths = self.length.view(n, G)[:m].clone()
-        return BeamResult(tokens[:m], scores[:m], lengths, self.hist_par[:max_len, :m].clone(),
+        # the walk-back on the (n * G, k') view: the history's parents are local to their group (G = 1: the tensors as they are)
+        tokens, scores = ops.beam_backtrack(self.hist_par.view(Tmax, n * G, kp), self.hist_tok.view(Tmax, n * G, kp),
+                                            self.scores.view(n * G, kp), self.length, n_best)
+        tokens, scores = tokens.view(n, G * n_best, Tmax), scores.view(n, G * n_best)
+        lengths = self.length[:m * G].clone()
+        return BeamResult(tokens[:m], scores[:m], lengths if G == 1 else lengths.view(m, G), self.hist_par[:max_len, :m].clone(),
                           self.hist_tok[:max_len, :m].clone(), self.hist_sc[:max_len, :m].clone(), groups=G)
 
     def _host_steps(self, max_len, eos):

@@ -1233,7 +1233,7 @@ class EncoderStack:
 
 
 class DecoderLayer:
-    """What training (DecoderStack.build_forward) and cached decoding (decode.CaptionBeamSearch._step_plan) share of a decoder layer
+    """What training (DecoderStack.build_forward) and cached decoding (decode.CachedDecoder._step_plan) share of a decoder layer
     (module_decoder.py:268-320), stated once: emitters over one layer's workspace of T rows (DecoderStack.layer_workspace).  The
     self-attention core stays with each caller.  p / off / seed_dev: dropout probability, the layer's five stream offsets, the seed word."""
 

@@ -5,15 +5,16 @@ independent captions per instance from the decoder's own distribution (cut to th
 a temperature, cut again to a nucleus of mass top_p) and reports, per token and per caption, both the model's log-probability and
 the proposal's, so that a consumer can re-rank or importance-weight the samples.
 
-The session is decode.CaptionBeamSearch's, with n_samp rows per instance in the place of n_bm beams: the cross encoder once per
-instance, the per-layer encoder K/V, the per-row self-attention cache, the rows of an instance sharing its encoder K/V, idle slots
-for partial batches, one hipGraph per position.  Two things differ:
+The session is a decode.CachedDecoder with n_samp rows per instance: from steps.InstanceSession the cross encoder once per instance,
+idle slots for partial batches and the graph-or-eager replay; from CachedDecoder the per-layer encoder K/V, the per-row self-attention
+cache, the rows of an instance sharing its encoder K/V, one hipGraph per position and the loop over the positions.  CaptionSampler
+itself owns the sampling state and two forms of a position's plan, "logits" and "sample":
 
-  * rows never change places, so the sampling forms of a position's plan use ONE cache buffer per layer and have no cache gather;
-  * the tail of a position is univl_sample_step (csrc/sample.hip) on the RAW logits: no univl_log_softmax_rows, no beam step.  Top-k,
+  * rows never change places, so both forms use ONE cache buffer per layer and have no cache gather;
+  * the tail of "sample" is univl_sample_step (csrc/sample.hip) on the RAW logits: no univl_log_softmax_rows, no beam step.  Top-k,
     weights, nucleus, the draw, the token into the buffer the next position's embedding reads, the log-probabilities and the per-row
     done / length all happen in its two launches.  temperature, top_p, the seed and the end token are device words, so one capture
-    serves every value of them.
+    serves every value of them.  "logits" has no tail.
 
 A draw is a pure function of (the row's logits, top_k, temperature, top_p, seed, position, row): the same seed gives the same
 captions whatever sync_every or n_active is, and two rows of one instance differ because the row index keys the generator.
@@ -22,7 +23,7 @@ import torch
 
 from . import ops
 from ._lib import SAMPLE_KMAX
-from .decode import CaptionBeamSearch
+from .decode import CachedDecoder
 
 
 class SampleResult:
@@ -51,10 +52,10 @@ class SampleResult:
         return [[row[:lens[i][k]] for k, row in enumerate(inst)] for i, inst in enumerate(tok)]
 
 
-class CaptionSampler(CaptionBeamSearch):
+class CaptionSampler(CachedDecoder):
     """Compiled sampling session for a fixed (n_inst, max_words W, max_frames F, n_samp, max_len, top_k).  temperature and top_p given
     here are the defaults of sample(); they, the seed and the end token live in device words and never force a new capture.
-    Partial batches: n_active as in CaptionBeamSearch; the rows of idle slots have `done` preset to 1."""
+    Partial batches: n_active as in steps.InstanceSession; the rows of idle slots have `row_done` preset to 1."""
 
     def __init__(self, model, n_inst, W, F, n_samp=5, max_len=None, top_k=50, temperature=1.0, top_p=1.0, use_graphs=True, constraints=None):
         """constraints: a constrain.DecodeConstraints or None.  With one, univl_decode_constrain runs on the RAW logits between the
@@ -71,9 +72,9 @@ class CaptionSampler(CaptionBeamSearch):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("CaptionSampler needs a model on a HIP device (got %s); there is no CPU fallback" % dev)
-        super().__init__(model, n_inst, W, F, n_bm=int(n_samp), max_len=max_len, use_graphs=use_graphs, beam_step="device",
-                         constraints=constraints)
         self.n_samp, self.top_k, self.temperature, self.top_p = int(n_samp), int(top_k), float(temperature), float(top_p)
+        super().__init__(model, n_inst, W, F, self.n_samp, n_inst * self.n_samp, max_len=max_len, use_graphs=use_graphs,
+                         constraints=constraints)
         R, Tmax, dev = self.R, self.Tmax, self.cx.dev
         # ---- sampling state (read and written by univl_sample_step), all per ROW
         self.row_done = torch.zeros(R, dtype=torch.uint8, device=dev)
@@ -85,7 +86,6 @@ class CaptionSampler(CaptionBeamSearch):
         self.seq_q = torch.zeros(R, device=dev)
         self.sampling_dev = torch.tensor([1.0 / self.temperature, self.top_p], dtype=torch.float32, device=dev)
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.row_done_host = torch.zeros(R, dtype=torch.uint8).pin_memory()
         self.sample_ws = ops.sample_ws(R, self.top_k, dev)
 
     @staticmethod
@@ -96,15 +96,15 @@ class CaptionSampler(CaptionBeamSearch):
             raise ValueError("CaptionSampler: top_p=%r, expected a value > 0 (>= 1: no nucleus cut)" % (top_p,))
 
     # ------------------------------------------------------------------------------------------ step plans
+    FORMS = ("logits", "sample")
+
     def _reorders(self, form):
-        return form not in ("logits", "sample")
+        return False
 
     def _plan_tail(self, pl, t, form):
         """"logits": nothing after the vocabulary classifier (step_logits).  "sample": univl_sample_step on the raw logits."""
         if form == "logits":
             return
-        if form != "sample":
-            return super()._plan_tail(pl, t, form)
         if self.constraints is not None:
             c = self.constraints
             pl.add("univl_decode_constrain", ops.decode_constrain_desc(
@@ -115,12 +115,6 @@ class CaptionSampler(CaptionBeamSearch):
             tokens_out=self.tokens_out, tok_logprob=self.tok_lp, q_logprob=self.q_lp, seq_logprob=self.seq_lp,
             seq_q_logprob=self.seq_q, ws=self.sample_ws, sampling_dev=self.sampling_dev, seed_dev=self.seed_dev, eos_dev=self.eos_dev))
 
-    def _run_plan(self, pl):
-        if self.use_graphs and not torch.cuda.is_current_stream_capturing():
-            pl.run_graphed()
-        else:
-            pl.run()
-
     # ------------------------------------------------------------------------------------------------- run
     @torch.no_grad()
     def step_logits(self, t, last_tokens):
@@ -128,15 +122,8 @@ class CaptionSampler(CaptionBeamSearch):
         token at position t (the rows' cache holds positions [0, t) from the calls before).  The position plan without the sample
         tail; it neither reads nor advances the sampling state.  Exposed for the parity tests."""
         self.ids.copy_(last_tokens.reshape(-1))
-        self._run_plan(self._step_plan(t, "logits"))
+        self._replay(self._step_plan(t, "logits"))
         return self.head.logits[:, :self.V]
-
-    def _all_done(self):
-        """The R done bytes through a pinned buffer and an event wait (the only host read of the loop)."""
-        self.row_done_host.copy_(self.row_done, non_blocking=True)
-        self.done_event.record()
-        self.done_event.synchronize()
-        return bool(self.row_done_host.all())
 
     @torch.no_grad()
     def sample(self, sequence_output, visual_output, input_mask, video_mask, bos, eos, seed, max_len=None, sync_every=8, n_active=None,
@@ -167,10 +154,7 @@ class CaptionSampler(CaptionBeamSearch):
         self.seed_dev.fill_(s - (1 << 64) if s >= (1 << 63) else s)          # the word's 64 bits in int64 storage
         self.sampling_dev[0:1].fill_(1.0 / float(temperature))               # rounded to fp32 once: the contract's inv_T
         self.sampling_dev[1:2].fill_(float(top_p))
-        for t in range(max_len):
-            self._run_plan(self._step_plan(t, "sample"))
-            if sync_every and (t + 1) % sync_every == 0 and t + 1 < max_len and self._all_done():
-                break
+        self._run_positions("sample", max_len, sync_every, self.row_done)
         R = m * ns
         view = lambda x: x[:R].view(m, ns, *x.shape[1:]).clone()
         return SampleResult(view(self.tokens_out), view(self.tok_lp), view(self.q_lp), view(self.seq_lp), view(self.seq_q),

@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .engine import DecoderStack
-from .steps import EvalSession, VocabHead, H
+from .steps import InstanceSession, VocabHead, H
 
 
 class CaptionScores:
@@ -65,39 +65,29 @@ def beam_inputs_labels(tokens, lengths, bos, eos, pad, Wd):
     return inputs, labels, keep.to(torch.int64)
 
 
-class CaptionScorer:
+class CaptionScorer(InstanceSession):
     """Compiled scoring session for a fixed (n_inst, max_words W, max_frames F, caption length Wd, n_cand captions per instance).
 
-    Partial batches follow decode.CaptionBeamSearch: score() takes n_active (None: n_inst); the tensors then carry n_active
-    instances.  Slots [n_active, n_inst) are IDLE: their labels are set to -1 and their decoder masks and input ids to 0, the feature
-    and mask slots are zero-filled once at construction and afterwards keep what an earlier batch left in them.  The launch shapes do
-    not change, so a loader's short last batch replays the plan and hipGraph of the full ones.  No launch reduces across instances
-    or captions, so the active results do not depend on idle contents.  The result holds the first n_active instances only.
+    The encoder half is steps.InstanceSession (the cross encoder alone, once per instance; idle slots; n_active); this class appends the
+    decoder over the captions and the scoring head to its plan.  Partial batches: score() takes n_active (None: n_inst); the tensors
+    then carry n_active instances.  The labels of idle slots are set to -1 and their decoder masks and input ids to 0.  No launch
+    reduces across instances or captions, so the active results do not depend on idle contents.  The result holds the first n_active
+    instances only.
 
     The scores are the model's UNSMOOTHED log-probabilities: model.caption_label_smoothing shapes the training loss only and is not
     looked at here."""
 
     def __init__(self, model, n_inst, W, F, Wd, n_cand=1, use_graphs=True):
-        if model.decoder is None:
-            raise RuntimeError("CaptionScorer: this model was built without a decoder (stage one)")
         if n_inst < 1 or n_cand < 1 or Wd < 1:
             raise ValueError("CaptionScorer: n_inst=%r, n_cand=%r, Wd=%r must be positive" % (n_inst, n_cand, Wd))
         assert Wd <= model.decoder_config.max_target_embeddings
         if n_cand > 1 and (W + F) % 2:
             raise ValueError("CaptionScorer: n_cand > 1 needs an even W + F (univl_gather_rows moves the int64 key mask in 16-byte units)")
-        self.model, self.n_inst, self.W, self.F, self.Wd, self.n_cand = model, n_inst, W, F, Wd, n_cand
-        self.use_graphs = bool(use_graphs)
-        model.flat.refresh_shadow()
-        rows = list(range(n_inst))
-        ses = EvalSession(model, n_inst, n_inst, W, F, rows, rows)              # the cross encoder alone, once per instance
-        self.cx, self.feats, self.run, self.plan = ses.cx, ses.feats, ses.run, ses.plan
+        super().__init__(model, n_inst, W, F, use_graphs)
+        self.Wd, self.n_cand = Wd, n_cand
         self.n_cross_ops = len(self.plan)
-        cx = self.cx
+        cx, run, pl, S = self.cx, self.run, self.plan, self.S
         e, ct, bf, fl, dt, dev = cx.e, cx.ct, cx.bf, cx.fl, cx.dt, cx.dev
-        for buf in (self.feats.seq_out, self.feats.vis_out, self.feats.amask, self.feats.vmask):
-            buf.zero_()                                  # idle slots of a partial first batch read these (class docstring)
-        run, pl = self.run, self.plan
-        S = self.S = run.S
         B = self.B = n_inst * n_cand
         T = self.T = B * Wd
         # ---- the cross encoder's output and key mask, once per caption
@@ -131,13 +121,6 @@ class CaptionScorer:
         self.vs_desc, self.out = ops.vocab_score_desc(head.h16, fl.wop(nm["emb"]), W32(nm["bias"]), head.labels, V, Wd)
         pl.add("univl_vocab_score", self.vs_desc)
 
-    def _active(self, n_active):
-        if n_active is None:
-            return self.n_inst
-        if not 1 <= int(n_active) <= self.n_inst:
-            raise ValueError("CaptionScorer: n_active=%r, expected 1 .. n_inst=%d" % (n_active, self.n_inst))
-        return int(n_active)
-
     def _captions(self, t, m, what):
         nc, Wd = self.n_cand, self.Wd
         if t.numel() != m * nc * Wd or t.shape[-1] != Wd:
@@ -151,15 +134,10 @@ class CaptionScorer:
         positions that do not count.  Returns a CaptionScores of new device tensors."""
         n, nc, Wd = self.n_inst, self.n_cand, self.Wd
         m = self._active(n_active)
-        if sequence_output.shape[0] != m or visual_output.shape[0] != m:
-            raise ValueError("CaptionScorer.score: features of %d / %d instances, expected %d"
-                             % (sequence_output.shape[0], visual_output.shape[0], m))
+        self.load_features(sequence_output, visual_output, input_mask, video_mask, m, "score")
         ids = self._captions(input_caption_ids, m, "input_caption_ids")
         dm = self._captions(decoder_mask, m, "decoder_mask")
         lab = self._captions(output_caption_ids, m, "output_caption_ids")
-        self.model.flat.refresh_shadow()
-        self.feats.load(sequence_output.to(torch.float32), visual_output.to(torch.float32),
-                        input_mask.reshape(-1, input_mask.shape[-1]), video_mask.reshape(-1, video_mask.shape[-1]), rows=m)
         k = m * nc
         self.cap_ids[:k].copy_(ids, non_blocking=True)
         self.dmask[:k].copy_(dm, non_blocking=True)
@@ -169,10 +147,7 @@ class CaptionScorer:
             self.cap_ids[k:].zero_()
             self.dmask[k:].zero_()
             labels[k:].fill_(-1)
-        if self.use_graphs and not torch.cuda.is_current_stream_capturing():
-            self.plan.run_graphed()
-        else:
-            self.plan.run()
+        self._replay(self.plan)
         o = self.out
         tok = lambda name: o[name].view(n, nc, Wd)[:m].clone()
         seq = lambda name: o[name].view(n, nc)[:m].clone()

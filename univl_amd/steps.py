@@ -772,7 +772,7 @@ class EvalSession:
     """A compiled evaluation-side forward over features the caller supplies: RowFeatures (Bt text rows, Bv video rows) -> CrossRun over
     the pairs (tidx[p], vidx[p]) -> an optional head -> one Plan.  The head is head(cx, run, *head_args): PoolerSim without loss
     (cross-encoder similarity, reranking) or DecoderRun without loss (decoder_caption); None: the cross encoder alone
-    (decode.CaptionBeamSearch appends its own launches).  Cached in model._steps beside the Steps (UniVL._eval_session); unlike a Step
+    (InstanceSession below: the caption sessions append their own launches).  Cached in model._steps beside the Steps (UniVL._eval_session); unlike a Step
     it has no kind and no fwd / bwd plans, and its cx.training is False."""
 
     def __init__(self, model, Bt, Bv, W, F, tidx, vidx, head=None, *head_args):
@@ -785,6 +785,52 @@ class EvalSession:
         if head is not None:
             self.head = head(cx, self.run, *head_args)
             self.head.build_forward(self.plan)
+
+
+class InstanceSession:
+    """The encoder half of a caption session (decode.CachedDecoder, score.CaptionScorer): an EvalSession of the cross encoder alone over
+    n_inst instances (text row i with video row i) on features the caller supplies; the subclass appends its own launches to `plan`.
+
+    Partial batches: a call carries n_active instances (None: n_inst) in slots [0, n_active); slots [n_active, n_inst) are IDLE.  The
+    launch shapes do not change, so a loader's short last batch replays the plans and hipGraphs of the full ones.  The plans still run
+    over the idle slots, so what they read there must be defined and finite: the feature and mask slots are zero-filled once here, and
+    after that an idle slot keeps what an earlier batch left in it.  No launch reduces across instances, so the
+    active instances' results do not depend on it."""
+
+    def __init__(self, model, n_inst, W, F, use_graphs=True):
+        if model.decoder is None:
+            raise RuntimeError("%s: this model was built without a decoder (stage one)" % type(self).__name__)
+        self.model, self.n_inst, self.W, self.F = model, n_inst, W, F
+        self.use_graphs = bool(use_graphs)               # _replay: a plan is captured once into a hipGraph
+        model.flat.refresh_shadow()
+        rows = list(range(n_inst))
+        ses = EvalSession(model, n_inst, n_inst, W, F, rows, rows)
+        self.cx, self.feats, self.run, self.plan = ses.cx, ses.feats, ses.run, ses.plan
+        self.S = self.run.S
+        for buf in (self.feats.seq_out, self.feats.vis_out, self.feats.amask, self.feats.vmask):
+            buf.zero_()                                  # idle slots of a partial first batch read these
+
+    def _active(self, n_active):
+        if n_active is None:
+            return self.n_inst
+        if not 1 <= int(n_active) <= self.n_inst:
+            raise ValueError("%s: n_active=%r, expected 1 .. n_inst=%d" % (type(self).__name__, n_active, self.n_inst))
+        return int(n_active)
+
+    def load_features(self, sequence_output, visual_output, input_mask, video_mask, m, method):
+        """The features of m instances into slots [0, m); `method` names the caller in the error text."""
+        if sequence_output.shape[0] != m or visual_output.shape[0] != m:
+            raise ValueError("%s.%s: features of %d / %d instances, expected %d"
+                             % (type(self).__name__, method, sequence_output.shape[0], visual_output.shape[0], m))
+        self.model.flat.refresh_shadow()
+        self.feats.load(sequence_output.to(torch.float32), visual_output.to(torch.float32),
+                        input_mask.reshape(-1, input_mask.shape[-1]), video_mask.reshape(-1, video_mask.shape[-1]), rows=m)
+
+    def _replay(self, plan):
+        if self.use_graphs and not torch.cuda.is_current_stream_capturing():
+            plan.run_graphed()
+        else:
+            plan.run()
 
 
 # ------------------------------------------------------------------------------------------------ step assembly
