@@ -446,6 +446,68 @@ typedef struct {
 } UnivlBeamGroupStep;
 int univl_beam_group_step_sizeof(void);
 int univl_beam_group_step(const UnivlBeamGroupStep* d, hipStream_t stream);
+/* Beam search with a POOL OF FINISHED HYPOTHESES, a length penalty and an early-stopping switch (elsewhere `length_penalty`,
+ * `early_stopping`).  Two launches per position, no host involvement, capturable, the workspace of univl_beam_step; one more launch
+ * (univl_beam_pool_finish) after the last position.  Per instance i that is not done, at position t:
+ *   CANDIDATES  candidate(b, v) = lp[i * n_bm + b, v] + scores[i, b], exactly as univl_beam_step forms it (one fp32 addition; at the
+ *               first step only b = 0 counts and nothing is added), ordered by larger value first, then LOWER flat index b * V + v.
+ *               A candidate whose value is -inf is not a candidate (a minimum length of univl_decode_constrain masks the end column
+ *               that way); NaN values: unspecified, every index written stays in range.
+ *   LIVE BEAMS  the first n_bm candidates with v != eos, in that order: scores, tokens, src and history row t are written exactly as
+ *               univl_beam_step writes them.  A live beam never holds the end token.  The caller's condition: n_bm finite non-end
+ *               columns per live row.
+ *   FINISHING   every candidate with v == eos whose rank among ALL candidates (the number of candidates in front of it) is < n_bm
+ *               is offered to the pool, in candidate order, as the entry
+ *                 raw = the candidate's value, len = t + 1 (the end token counts), key = raw * w[len] (one fp32 multiplication),
+ *                 end_t = t, beam = b, finished = 1;
+ *               its tokens are the walk-back from history row end_t - 1 at `beam`: end_t tokens, the empty caption at t = 0.
+ *   w           a device table of Tmax + 2 floats that the HOST fills: w[L] = (float)pow((double)L, -alpha), w[0] = 1.  There is no
+ *               powf on the device, so a host reference reproduces every key bit for bit.
+ *   POOL ORDER  larger key first, then smaller end_t, then smaller beam.  The pool holds at most n_bm entries per instance: a new entry
+ *               is appended while there is room (slot pool_count[i]); otherwise it replaces, in that entry's slot, the LAST entry in
+ *               pool order if it stands in front of it, and is dropped if it does not.  Slots are therefore in arrival order, not sorted.
+ *   AFTER THE OFFERS  length[i] += 1;  done[i] <- 1 when the pool holds n_bm entries AND (params[0] != 0 [early_stopping] OR
+ *               scores[i, 0] * w[Lmax] <= the key of the last pool entry), with scores[i, 0] the NEW best live score and
+ *               Lmax = params[1] clamped to [0, Tmax + 1], the call's max_len: for alpha >= 0 and log-probabilities <= 0 that
+ *               product is the best key a live beam can still reach.
+ * Done instances and idle slots are FROZEN exactly as univl_beam_step freezes them; their pool is untouched too.
+ * IDENTITY: with no end token (eos < 0 or >= V) the step is univl_beam_step bit for bit and the pool is not written.
+ * univl_beam_pool_finish(d, n_best, ...) reads the same descriptor (lp, ws, t, tokens and src are not looked at): for every instance
+ * that is NOT done the live beams b = 0 .. n_bm-1 are offered in order (raw = scores[i, b], len = length[i], key = raw * w[len],
+ * end_t = length[i], beam = b, finished = 0) -- in the kernel's own memory, the pool arrays are only read -- then the pool is sorted in
+ * pool order and its first n_best entries are written out: hyp [n_inst, n_best, Tmax] int32 (the walk-back, every parent clamped into
+ * [0, n_bm) as univl_beam_backtrack does; for a finished entry FOLLOWED BY THE END TOKEN at index end_t, so that the row holds `len`
+ * tokens as a plain search's row holds the end token its top beam emitted; then -1), hyp_raw, hyp_key, hyp_len (`len`) and the
+ * finished byte, [n_inst, n_best] each.  A slot with fewer pool entries than n_best is an idle one: -1 tokens, -inf, -inf, length 0,
+ * finished 0.
+ * Range: that of univl_beam_step (the finish: 1 <= n_best <= n_bm <= UNIVL_BEAM_MAX, Tmax >= 1), w, params and every pool array
+ * non-NULL; otherwise UNIVL_EINVAL and nothing is launched.  The struct is in neither numbered size table:
+ * univl_beam_pool_step_sizeof states its size. */
+typedef struct {
+    const float* lp; int64_t ld;     /* the fields of UnivlBeamStep, in its order ...                                             */
+    int32_t n_inst, n_bm, V;
+    int32_t first_step;
+    int32_t eos;
+    const int32_t* eos_dev;
+    int32_t t, Tmax;
+    float* scores;
+    uint8_t* done;
+    int32_t* length;
+    int64_t* tokens;
+    int32_t* src;
+    int32_t* hist_parents; int32_t* hist_tokens; float* hist_scores;
+    void* ws; int64_t ws_bytes;      /* as UnivlBeamStep.ws                                                                       */
+    const float* w;                  /* ... then [Tmax + 2] device floats, the length weights (host-filled)                       */
+    const int32_t* params;           /* int32 [2] device words {early_stopping, Lmax}: one capture serves every mode and max_len   */
+    float* pool_key; float* pool_raw;                          /* [n_inst, n_bm] each, read and written                           */
+    int32_t* pool_end_t; int32_t* pool_beam;                   /* [n_inst, n_bm]                                                  */
+    uint8_t* pool_finished;                                    /* [n_inst, n_bm]                                                  */
+    int32_t* pool_count;                                       /* [n_inst] entries held, 0 before position 0                      */
+} UnivlBeamPoolStep;
+int univl_beam_pool_step_sizeof(void);
+int univl_beam_pool_step(const UnivlBeamPoolStep* d, hipStream_t stream);
+int univl_beam_pool_finish(const UnivlBeamPoolStep* d, int32_t n_best, int32_t* hyp, float* hyp_raw, float* hyp_key, int32_t* hyp_len,
+                           uint8_t* hyp_finished, hipStream_t stream);
 /* Beam.get_hypothesis (beam.py:108-116) for the n_best best beams of every instance (beams are sorted after univl_beam_step, so
  * beam k is the k-th best): hyp[i, k, 0 .. length[i]) <- the tokens found by walking the history back from (row length[i] - 1,
  * beam k) through the parents, the rest of hyp[i, k, :] (Tmax entries) <- -1;  hyp_scores[i, k] <- scores[i, k].

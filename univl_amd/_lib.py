@@ -82,6 +82,13 @@ class BeamGroupStep(C.Structure):
     _fields_ = BeamStep._fields_ + [("n_groups", i32), ("diversity", f32), ("diversity_dev", vp)]
 
 
+class BeamPoolStep(C.Structure):
+    """include/univl_hip.h: UnivlBeamPoolStep -- BeamStep's fields, then the length weights, the parameter words and the pool arrays.
+    Not in _STRUCTS: the library states its size through univl_beam_pool_step_sizeof (checked in lib())."""
+    _fields_ = BeamStep._fields_ + [("w", vp), ("params", vp), ("pool_key", vp), ("pool_raw", vp), ("pool_end_t", vp), ("pool_beam", vp),
+                                    ("pool_finished", vp), ("pool_count", vp)]
+
+
 class SimTopk(C.Structure):
     _fields_ = [("q", vp), ("ldq", i64), ("g", vp), ("ldg", i64), ("Nq", i32), ("Ng", i32), ("H", i32), ("k", i32), ("slices", i32),
                 ("reserved", i32), ("idx", vp), ("score", vp), ("target", vp), ("gt", vp), ("eq", vp), ("ws", vp), ("ws_bytes", i64)]
@@ -175,7 +182,8 @@ def lib():
                  "univl_attention_bwd", "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_pool_fwd",
                  "univl_pool_bwd", "univl_bert_adam", "univl_beam_step", "univl_sim_topk", "univl_vocab_score",
                  "univl_sample_step", "univl_caption_overlap", "univl_ngram_df", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd",
-                 "univl_decode_constrain", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "univl_beam_group_step"):
+                 "univl_decode_constrain", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "univl_beam_group_step",
+                 "univl_beam_pool_step"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     L.univl_caption_overlap_sizeof.argtypes = []
@@ -213,6 +221,13 @@ def lib():
     if L.univl_beam_group_step_sizeof() != C.sizeof(BeamGroupStep):
         raise RuntimeError("ABI mismatch for BeamGroupStep: library %d bytes, ctypes %d"
                            % (L.univl_beam_group_step_sizeof(), C.sizeof(BeamGroupStep)))
+    L.univl_beam_pool_step_sizeof.argtypes = []
+    L.univl_beam_pool_step_sizeof.restype = i32
+    if L.univl_beam_pool_step_sizeof() != C.sizeof(BeamPoolStep):
+        raise RuntimeError("ABI mismatch for BeamPoolStep: library %d bytes, ctypes %d"
+                           % (L.univl_beam_pool_step_sizeof(), C.sizeof(BeamPoolStep)))
+    L.univl_beam_pool_finish.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.univl_beam_pool_finish.restype = i32
     L.univl_caption_advantage.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, vp, vp]
     L.univl_caption_advantage.restype = i32
     L.univl_consensus_pick.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -301,7 +316,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_group_step_sizeof", "univl_beam_group_step", "univl_sample_step", "univl_decode_constrain_sizeof", "univl_decode_constrain", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_group_step_sizeof", "univl_beam_group_step", "univl_beam_pool_step_sizeof", "univl_beam_pool_step", "univl_beam_pool_finish", "univl_sample_step", "univl_decode_constrain_sizeof", "univl_decode_constrain", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_ce_weighted_sizeof", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "univl_vocab_ce_smooth_sizeof", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

@@ -21,6 +21,13 @@
 // value, the index decides a tie as before).  So x is not among the group's k' best: a row's penalised top-k' lies inside its
 // unpenalised top-n_bm, which lies inside the union of its slices' top-n_bm.  With lambda < 0 the argument fails (a candidate far down
 // a row could be lifted past the list), which is why a negative penalty is refused.
+//
+// univl_beam_pool_step / univl_beam_pool_finish are beam search with a pool of finished hypotheses, a length penalty and an
+// early-stopping switch, on the same two launches per position (include/univl_hip.h states the rule).  Live beams never hold the end
+// token: phase 1 is the scan above with the end column left out (beam_scan_kernel<NB, true>), the workspace that of univl_beam_step,
+// and phase 2 (beam_pool_select_kernel, which carries the sufficiency argument) reads the n_bm end-column values itself, ranks them
+// among all candidates and offers those of rank < n_bm to the instance's pool, kept in the LDS of its one wave.  Keys are
+// raw * w[len] with w a HOST-filled table: no powf on the device.  With no end token (eos < 0) the step is univl_beam_step bit for bit.
 #include <cmath>
 
 #include "common.h"
@@ -43,10 +50,13 @@ __device__ __forceinline__ void keep(float (&tv)[NB], int (&ti)[NB], float v, in
 }
 
 // ws_val / ws_idx: [rows][slices][NB]; idx is the COLUMN within the row (RANK_NONE: empty)
-template <int NB>
+// SKIP (univl_beam_pool_step): the end column is not a candidate of the scan; phase 2 reads it itself.  Without SKIP the two
+// arguments behind it are not read and the code is the one the plain and the group step always had.
+template <int NB, bool SKIP>
 __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict__ lp, long ld, int V, int first_step, const float* __restrict__ scores,
                                                         const uint8_t* __restrict__ done, int stride, int chunk, int vec,
-                                                        float* __restrict__ ws_val, int* __restrict__ ws_idx) {
+                                                        float* __restrict__ ws_val, int* __restrict__ ws_idx, int eos,
+                                                        const int32_t* __restrict__ eos_dev) {
     __shared__ float red_v[2][4];
     __shared__ int red_i[2][4];
     // stride: rows per entry of done -- n_bm for univl_beam_step (an instance), k' for univl_beam_group_step (a group)
@@ -54,6 +64,7 @@ __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict_
     if (done[inst]) return;                                   // frozen instance: phase 2 does not read its slots
     const int row = first_step ? inst * stride : (int)blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
     const float add = first_step ? 0.f : scores[row];
+    const int skip = SKIP ? (eos_dev ? *eos_dev : eos) : -1;  // never a column when negative
     const float* x = lp + (long)row * ld;
     const int c0 = slice * chunk, c1 = min(V, c0 + chunk);    // chunk is a multiple of 4
     float tv[NB];
@@ -74,11 +85,12 @@ __global__ __launch_bounds__(256) void beam_scan_kernel(const float* __restrict_
                 const int cu = c + u * 1024;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (cu + e < c1) keep<NB>(tv, ti, first_step ? q[u][e] : q[u][e] + add, cu + e);
+                    if (cu + e < c1 && !(SKIP && cu + e == skip)) keep<NB>(tv, ti, first_step ? q[u][e] : q[u][e] + add, cu + e);
             }
         }
     } else {
-        for (int c = c0 + tid; c < c1; c += 256) keep<NB>(tv, ti, first_step ? x[c] : x[c] + add, c);
+        for (int c = c0 + tid; c < c1; c += 256)
+            if (!(SKIP && c == skip)) keep<NB>(tv, ti, first_step ? x[c] : x[c] + add, c);
     }
     // NB rounds: the best head of the workgroup; its owner (columns are unique to a thread) moves on to its next entry
     const int wave = tid >> 6;
@@ -301,19 +313,234 @@ __global__ __launch_bounds__(64) void beam_group_select_kernel(const float* __re
     }
 }
 
-// what the two entry points hand to phase 1; n_units x stride = rows, done has n_units entries
-struct Scan {
-    const float* lp; long ld; int V, first_step; const float* scores; const uint8_t* done; int n_units, stride;
+// ---- the pooled search (univl_beam_pool_step, univl_beam_pool_finish)
+struct BeamPool {
+    const float* w; const int32_t* params;
+    float* key; float* raw; int32_t* end_t; int32_t* beam; uint8_t* fin; int32_t* count;
 };
 
-template <int NB>
+// pool order: larger key first, then smaller end_t, then smaller beam
+__device__ __forceinline__ bool pool_before(float ka, int ea, int ba, float kb, int eb, int bb) {
+    return ka > kb || (ka == kb && (ea < eb || (ea == eb && ba < bb)));
+}
+
+// An instance's pool in the LDS of its one wave; slots are in arrival order, a replacement takes the slot of the entry it displaces.
+struct PoolLds {
+    float key[UNIVL_BEAM_MAX], raw[UNIVL_BEAM_MAX];
+    int end_t[UNIVL_BEAM_MAX], beam[UNIVL_BEAM_MAX], fin[UNIVL_BEAM_MAX];
+};
+
+__device__ __forceinline__ int pool_last(const PoolLds& q, int cnt) {
+    int last = 0;
+    for (int j = 1; j < cnt; ++j)
+        if (pool_before(q.key[last], q.end_t[last], q.beam[last], q.key[j], q.end_t[j], q.beam[j])) last = j;
+    return last;
+}
+
+// one lane: append while there is room, else replace the last entry in pool order if the new one stands in front of it
+__device__ __forceinline__ void pool_offer(PoolLds& q, int& cnt, int cap, float key, float raw, int end_t, int beam, int fin) {
+    int slot = cnt;
+    if (cnt < cap) {
+        ++cnt;
+    } else {
+        slot = pool_last(q, cnt);
+        if (!pool_before(key, end_t, beam, q.key[slot], q.end_t[slot], q.beam[slot])) return;
+    }
+    q.key[slot] = key; q.raw[slot] = raw; q.end_t[slot] = end_t; q.beam[slot] = beam; q.fin[slot] = fin;
+}
+
+__device__ __forceinline__ int pool_load(PoolLds& q, const BeamPool& p, long s0, int inst, int n_bm, int lane) {
+    if (lane < n_bm) {
+        q.key[lane] = p.key[s0 + lane]; q.raw[lane] = p.raw[s0 + lane]; q.end_t[lane] = p.end_t[s0 + lane];
+        q.beam[lane] = p.beam[s0 + lane]; q.fin[lane] = p.fin[s0 + lane];
+    }
+    const int cnt = p.count[inst];
+    return cnt < 0 ? 0 : (cnt > n_bm ? n_bm : cnt);
+}
+
+// Phase 2 of univl_beam_pool_step: one wave per instance.  The workspace holds each (row, slice)'s top-n_bm NON-END candidates
+// (beam_scan_kernel<NB, SKIP>); the wave reads the (1 or n_bm) end-column values itself.
+// WHY THAT IS ENOUGH.  Live beams: the first n_bm non-end candidates of the instance.  A non-end candidate x of row b outside that
+// row's non-end top-n_bm has n_bm non-end candidates of its own row in front of it, so it is not among the instance's first n_bm; a
+// row's non-end top-n_bm lies inside the union of its slices' non-end top-n_bm.  Finishing: a row has ONE end column, and ALL of them
+// are read here, so none can be missed.  The rank of an end candidate e among all candidates is
+//   #(non-end candidates in front of e) + #(end candidates in front of e);
+// the second count is taken over the end values read here; for the first, the non-end candidates in front of e are a PREFIX of the
+// non-end order, so counting over the n_bm live winners gives min(true count, n_bm) -- exact whenever rank < n_bm can still hold.
+// A value of -inf (a column univl_decode_constrain masked) or NaN is not a candidate: `v > -inf` is false for both.
+__global__ __launch_bounds__(64) void beam_pool_select_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx,
+                                                              const float* __restrict__ lp, long ld, int n_bm, int V, int slices, int first_step,
+                                                              int eos, const int32_t* __restrict__ eos_dev, int t, int Tmax, long hist_row,
+                                                              BeamOut o, BeamPool p) {
+    __shared__ float cv[512];
+    __shared__ int ci[512];
+    __shared__ float win_v[8], ev[8];
+    __shared__ int win_i[8], ord[8];
+    __shared__ PoolLds q;
+    __shared__ int cnt_s;
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    const long s0 = (long)inst * n_bm;                        // first row / state slot / pool slot of the instance
+    if (o.done[inst]) {                                       // frozen as in beam_select_kernel; the pool is untouched too
+        if (lane < n_bm) {
+            o.src[s0 + lane] = (int32_t)(s0 + lane);
+            o.hist_parents[hist_row + s0 + lane] = lane;
+            o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
+            o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
+        }
+        return;
+    }
+    const int end = eos_dev ? *eos_dev : eos, nrows = first_step ? 1 : n_bm;
+    const bool has_end = end >= 0 && end < V;
+    const int per_row = slices * n_bm, ncand = nrows * per_row;
+    for (int c = lane; c < ncand; c += 64) {
+        const int b = c / per_row, col = ws_idx[s0 * per_row + c];
+        cv[c] = ws_val[s0 * per_row + c];
+        ci[c] = col == RANK_NONE ? RANK_NONE : b * V + col;
+    }
+    if (lane < 8) {                                           // the end candidates, formed as the scan forms a candidate
+        float v = -INFINITY;
+        if (has_end && lane < nrows) {
+            const float x = lp[(s0 + lane) * ld + end];
+            v = first_step ? x : x + o.scores[s0 + lane];
+        }
+        ev[lane] = v;
+    }
+    int cnt = pool_load(q, p, s0, inst, n_bm, lane);
+    __syncthreads();
+    for (int r = 0; r < n_bm; ++r) {                          // the live beams: beam_select_kernel's rounds
+        float v = -INFINITY;
+        int i = RANK_NONE, at = -1;
+        for (int c = lane; c < ncand; c += 64)
+            if (better(cv[c], ci[c], v, i)) { v = cv[c]; i = ci[c]; at = c; }
+        const int mine = i;
+        wave_best(v, i);
+        if (i != RANK_NONE && mine == i) { cv[at] = -INFINITY; ci[at] = RANK_NONE; }
+        if (lane == 0) { win_v[r] = v; win_i[r] = i; }
+        __syncthreads();
+    }
+    // lane b: the rank of end candidate b; the taken ones, in candidate order, into ord[]
+    bool taken = false;
+    if (lane < nrows) {
+        const float v = ev[lane];
+        const int fi = lane * V + end;
+        if (v > -INFINITY) {
+            int ahead = 0, ends_ahead = 0;
+            for (int j = 0; j < n_bm; ++j) ahead += (win_i[j] != RANK_NONE && better(win_v[j], win_i[j], v, fi)) ? 1 : 0;
+            for (int j = 0; j < nrows; ++j) ends_ahead += (j != lane && ev[j] > -INFINITY && better(ev[j], j * V + end, v, fi)) ? 1 : 0;
+            taken = ahead + ends_ahead < n_bm;                // every end candidate in front of a taken one is taken: ends_ahead is its place
+            if (taken) ord[ends_ahead] = lane;
+        }
+    }
+    const int ntaken = __popcll(__ballot(taken));
+    __syncthreads();
+    if (lane < n_bm) {
+        // fewer than n_bm comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
+        const int flat = win_i[lane] == RANK_NONE ? lane * V : win_i[lane], parent = flat / V, token = flat % V;
+        o.scores[s0 + lane] = win_v[lane];
+        o.tokens[s0 + lane] = token;
+        o.src[s0 + lane] = (int32_t)(s0 + parent);
+        o.hist_parents[hist_row + s0 + lane] = parent;
+        o.hist_tokens[hist_row + s0 + lane] = token;
+        o.hist_scores[hist_row + s0 + lane] = win_v[lane];
+    }
+    if (lane == 0) {
+        const float wl = p.w[t + 1];                          // len = t + 1 <= Tmax
+        for (int k = 0; k < ntaken; ++k) {
+            const int b = ord[k];
+            pool_offer(q, cnt, n_bm, ev[b] * wl, ev[b], t, b, 1);
+        }
+        o.length[inst] += 1;
+        if (cnt == n_bm) {
+            int lmax = p.params[1];
+            lmax = lmax < 0 ? 0 : (lmax > Tmax + 1 ? Tmax + 1 : lmax);
+            if (p.params[0] != 0 || win_v[0] * p.w[lmax] <= q.key[pool_last(q, cnt)]) o.done[inst] = 1;
+        }
+        p.count[inst] = cnt;
+        cnt_s = cnt;
+    }
+    __syncthreads();
+    if (ntaken && lane < cnt_s) {
+        p.key[s0 + lane] = q.key[lane]; p.raw[s0 + lane] = q.raw[lane]; p.end_t[s0 + lane] = q.end_t[lane];
+        p.beam[s0 + lane] = q.beam[lane]; p.fin[s0 + lane] = (uint8_t)q.fin[lane];
+    }
+}
+
+struct PoolHyp {
+    int32_t* tokens; float* raw; float* key; int32_t* len; uint8_t* fin;
+};
+
+// univl_beam_pool_finish: one wave per instance.  The live beams of an instance that is not done are offered (in LDS: the pool arrays
+// themselves are only read), the pool is ranked in pool order and lane k < n_best writes hypothesis k.
+__global__ __launch_bounds__(64) void beam_pool_finish_kernel(int n_inst, int n_bm, int n_best, int Tmax, int eos, const int32_t* __restrict__ eos_dev,
+                                                              const float* __restrict__ scores, const uint8_t* __restrict__ done,
+                                                              const int32_t* __restrict__ length, const int32_t* __restrict__ hp,
+                                                              const int32_t* __restrict__ ht, BeamPool p, PoolHyp h) {
+    __shared__ PoolLds q;
+    __shared__ int cnt_s, srt[8];
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    const long s0 = (long)inst * n_bm;
+    int cnt = pool_load(q, p, s0, inst, n_bm, lane);
+    __syncthreads();
+    if (lane == 0) {
+        if (!done[inst]) {
+            int len = length[inst];
+            len = len < 0 ? 0 : (len > Tmax ? Tmax : len);
+            const float wl = p.w[len];
+            for (int b = 0; b < n_bm; ++b) pool_offer(q, cnt, n_bm, scores[s0 + b] * wl, scores[s0 + b], len, b, 0);
+        }
+        cnt_s = cnt;
+    }
+    __syncthreads();
+    cnt = cnt_s;
+    if (lane < cnt) {
+        int place = 0;
+        for (int j = 0; j < cnt; ++j)
+            place += (j != lane && pool_before(q.key[j], q.end_t[j], q.beam[j], q.key[lane], q.end_t[lane], q.beam[lane])) ? 1 : 0;
+        // (end_t, beam) is unique in a pool; equal entries (a corrupt pool) must still leave every srt slot written
+        for (int j = 0; j < lane; ++j)
+            place += (q.key[j] == q.key[lane] && q.end_t[j] == q.end_t[lane] && q.beam[j] == q.beam[lane]) ? 1 : 0;
+        srt[place] = lane;
+    }
+    __syncthreads();
+    if (lane >= n_best) return;
+    const long e = (long)inst * n_best + lane;
+    int32_t* out = h.tokens + e * Tmax;
+    if (lane >= cnt) {                                        // an idle slot
+        for (int j = 0; j < Tmax; ++j) out[j] = -1;
+        h.raw[e] = -INFINITY; h.key[e] = -INFINITY; h.len[e] = 0; h.fin[e] = 0;
+        return;
+    }
+    const int s = srt[lane], fin = q.fin[s] ? 1 : 0;
+    int ntok = q.end_t[s];
+    ntok = ntok < 0 ? 0 : (ntok > Tmax ? Tmax : ntok);
+    for (int j = ntok; j < Tmax; ++j) out[j] = -1;
+    int b = q.beam[s];
+    for (int j = ntok - 1; j >= 0; --j) {
+        b = b < 0 ? 0 : (b >= n_bm ? n_bm - 1 : b);            // a corrupt history must not walk out of the arrays
+        const long at = ((long)j * n_inst + inst) * n_bm + b;
+        out[j] = ht[at];
+        b = hp[at];
+    }
+    if (fin && ntok < Tmax) out[ntok] = eos_dev ? *eos_dev : eos;        // the end token that finished it: the row holds len tokens
+    h.raw[e] = q.raw[s]; h.key[e] = q.key[s]; h.fin[e] = (uint8_t)fin;
+    h.len[e] = fin && ntok < Tmax ? ntok + 1 : ntok;
+}
+
+// what the entry points hand to phase 1; n_units x stride = rows, done has n_units entries; eos / eos_dev: read by the SKIP form only
+struct Scan {
+    const float* lp; long ld; int V, first_step; const float* scores; const uint8_t* done; int n_units, stride;
+    int eos = -1; const int32_t* eos_dev = nullptr;
+};
+
+template <int NB, bool SKIP>
 void launch_scan(const Scan& a, int slices, int chunk, int vec, float* ws_val, int* ws_idx, hipStream_t stream) {
     const unsigned rows = a.first_step ? a.n_units : a.n_units * a.stride;
-    hipLaunchKernelGGL(beam_scan_kernel<NB>, dim3(rows, slices), dim3(256), 0, stream, a.lp, a.ld, a.V, a.first_step, a.scores, a.done, a.stride,
-                       chunk, vec, ws_val, ws_idx);
+    hipLaunchKernelGGL((beam_scan_kernel<NB, SKIP>), dim3(rows, slices), dim3(256), 0, stream, a.lp, a.ld, a.V, a.first_step, a.scores, a.done,
+                       a.stride, chunk, vec, ws_val, ws_idx, a.eos, a.eos_dev);
 }
 
 // Phase 1 with a sorted top-n_bm per (row, slice); returns the slices used.  ws: [rows][slices][n_bm] values, then as many indices.
+template <bool SKIP = false>
 int scan_rows(const Scan& a, int n_bm, void* ws, float** ws_val, int** ws_idx, hipStream_t stream) {
     const int64_t rows = (int64_t)a.n_units * a.stride;
     // slices: enough workgroups for the whole chip (~4 per CU at 80 rows), but at least 1024 columns each
@@ -326,14 +553,14 @@ int scan_rows(const Scan& a, int n_bm, void* ws, float** ws_val, int** ws_idx, h
     *ws_val = static_cast<float*>(ws);
     *ws_idx = reinterpret_cast<int*>(*ws_val + rows * slices * n_bm);
     switch (n_bm) {
-        case 1: launch_scan<1>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        case 2: launch_scan<2>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        case 3: launch_scan<3>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        case 4: launch_scan<4>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        case 5: launch_scan<5>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        case 6: launch_scan<6>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        case 7: launch_scan<7>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
-        default: launch_scan<8>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 1: launch_scan<1, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 2: launch_scan<2, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 3: launch_scan<3, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 4: launch_scan<4, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 5: launch_scan<5, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 6: launch_scan<6, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        case 7: launch_scan<7, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
+        default: launch_scan<8, SKIP>(a, slices, chunk, vec, *ws_val, *ws_idx, stream); break;
     }
     return slices;
 }
@@ -397,6 +624,57 @@ extern "C" int univl_beam_group_step(const UnivlBeamGroupStep* d, hipStream_t st
     BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
     hipLaunchKernelGGL(beam_group_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->n_groups, d->V, slices,
                        d->first_step ? 1 : 0, d->eos, d->eos_dev, d->diversity, d->diversity_dev, (long)d->t * rows, o);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_beam_pool_step_sizeof(void) { return (int)sizeof(UnivlBeamPoolStep); }
+
+extern "C" int univl_beam_pool_step(const UnivlBeamPoolStep* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_pool_step: null descriptor");
+    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V &&
+                    d->V <= INT_MAX / UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
+                    "univl_beam_pool_step: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", d->n_inst, d->n_bm, d->V,
+                    (long long)d->ld, UNIVL_BEAM_MAX);
+    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "univl_beam_pool_step: history row t=%d of Tmax=%d", d->t, d->Tmax);
+    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
+                    d->ws, UNIVL_EINVAL, "univl_beam_pool_step: null pointer");
+    UNIVL_CHECK_ARG(d->w && d->params && d->pool_key && d->pool_raw && d->pool_end_t && d->pool_beam && d->pool_finished && d->pool_count,
+                    UNIVL_EINVAL, "univl_beam_pool_step: null pointer (w, params or a pool array)");
+    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
+    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
+    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
+                    "univl_beam_pool_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); "
+                    "got %lld", (long long)need, (long long)d->ws_bytes);
+    float* ws_val;
+    int* ws_idx;
+    const Scan a{d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores, d->done, d->n_inst, d->n_bm, d->eos, d->eos_dev};
+    const int slices = scan_rows<true>(a, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
+    UNIVL_LAUNCH_CHECK();
+    BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
+    BeamPool p{d->w, d->params, d->pool_key, d->pool_raw, d->pool_end_t, d->pool_beam, d->pool_finished, d->pool_count};
+    hipLaunchKernelGGL(beam_pool_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->lp, (long)d->ld, d->n_bm, d->V, slices,
+                       d->first_step ? 1 : 0, d->eos, d->eos_dev, d->t, d->Tmax, (long)d->t * rows, o, p);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_beam_pool_finish(const UnivlBeamPoolStep* d, int32_t n_best, int32_t* hyp, float* hyp_raw, float* hyp_key, int32_t* hyp_len,
+                                      uint8_t* hyp_finished, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_pool_finish: null descriptor");
+    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && n_best >= 1 && n_best <= d->n_bm && d->Tmax >= 1 &&
+                    (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
+                    "univl_beam_pool_finish: n_inst=%d n_bm=%d n_best=%d Tmax=%d (1 <= n_best <= n_bm <= %d)", d->n_inst, d->n_bm, n_best, d->Tmax,
+                    UNIVL_BEAM_MAX);
+    UNIVL_CHECK_ARG(d->scores && d->done && d->length && d->hist_parents && d->hist_tokens && d->w && d->pool_key && d->pool_raw &&
+                    d->pool_end_t && d->pool_beam && d->pool_finished && d->pool_count && hyp && hyp_raw && hyp_key && hyp_len && hyp_finished,
+                    UNIVL_EINVAL, "univl_beam_pool_finish: null pointer");
+    BeamPool p{d->w, d->params, d->pool_key, d->pool_raw, d->pool_end_t, d->pool_beam, d->pool_finished, d->pool_count};
+    PoolHyp h{hyp, hyp_raw, hyp_key, hyp_len, hyp_finished};
+    hipLaunchKernelGGL(beam_pool_finish_kernel, dim3(d->n_inst), dim3(64), 0, stream, d->n_inst, d->n_bm, n_best, d->Tmax, d->eos, d->eos_dev,
+                       d->scores, d->done, d->length, d->hist_parents, d->hist_tokens, p, h);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

@@ -107,6 +107,63 @@ class BeamResult:
         return [[row[:lens[i][j // nb]] for j, row in enumerate(inst)] for i, inst in enumerate(tok)]
 
 
+def check_length_penalty(length_penalty, early_stopping=False, beam_groups=1, beam_step="device"):
+    """The argument rule of the pooled search, on the host and before any device work.  length_penalty: None (the reference search:
+    returns None) or a finite number >= 0; early_stopping: a bool (or 0 / 1).  The pooled search has neither a group form nor a host
+    comparand: together with beam_groups > 1 or beam_step="host" it is a ValueError.  Returns (alpha as float, early_stopping as int)."""
+    if length_penalty is None:
+        if early_stopping not in (False, 0):
+            raise ValueError("early_stopping=%r needs a length_penalty (0.0 for none); length_penalty=None is the reference search, "
+                             "which stops when the top beam emits the end token" % (early_stopping,))
+        return None
+    ops.length_weights(length_penalty, 0)            # ValueError unless a finite number >= 0
+    if early_stopping not in (False, True, 0, 1):
+        raise ValueError("early_stopping=%r, expected a bool" % (early_stopping,))
+    if beam_groups != 1:
+        raise ValueError("length_penalty= with beam_groups=%r: the pooled search has no group form (out of scope); use one or the "
+                         "other" % (beam_groups,))
+    if beam_step == "host":
+        raise ValueError("length_penalty= with beam_step='host': the pooled search has no host comparand (out of scope); it needs "
+                         "beam_step='device'")
+    return float(length_penalty), int(bool(early_stopping))
+
+
+class PoolBeamResult:
+    """What CaptionBeamSearch.decode returns in a session built with a length_penalty -- DEVICE tensors only:
+      tokens      [n, n_best, Tmax] int32  the n_best best entries of every instance's pool, in pool order, -1 padded; a FINISHED
+                                           hypothesis ends with the end token, as a plain search's does
+      scores      [n, n_best] fp32         their RAW summed log-probabilities (the end token's included): what score.score_beams,
+                                           caption_metrics.consensus and rl compare, as with BeamResult; not sorted
+      norm_scores [n, n_best] fp32         the keys raw * len ** -alpha the pool is ordered by (non-increasing in k)
+      lengths     [n, n_best] int32        tokens PER HYPOTHESIS (the end token counts)
+      finished    [n, n_best] uint8        1: ended with the end token; 0: a live beam when the positions ran out
+      positions   [n] int32                positions the instance ran before it was done
+      parents / step_tokens / step_scores  [steps_run, n, n_bm]   the history, as in BeamResult.
+    A slot past an instance's pool (never the case when it ran a position and n_best <= n_bm) is -1 tokens, -inf, -inf, 0, 0."""
+    groups = 1
+
+    def __init__(self, tokens, scores, norm_scores, lengths, finished, positions, parents, step_tokens, step_scores):
+        self.tokens, self.scores, self.norm_scores, self.lengths, self.finished = tokens, scores, norm_scores, lengths, finished
+        self.positions, self.parents, self.step_tokens, self.step_scores = positions, parents, step_tokens, step_scores
+
+    @property
+    def steps_run(self):
+        return self.parents.shape[0]
+
+    def captions(self, eos, pad, eos_dev=None):
+        """BeamResult.captions on per-hypothesis lengths: (cap_tokens [n, n_best, Tmax] int32, cap_len [n, n_best] int32).  The rows
+        are cut as n * n_best instances of one hypothesis each."""
+        n, nb, Tmax = self.tokens.shape
+        cap, cap_len = ops.beam_captions(self.tokens.reshape(n * nb, 1, Tmax), self.lengths.reshape(n * nb).contiguous(), eos, pad,
+                                         eos_dev=eos_dev)
+        return cap.view(n, nb, Tmax), cap_len.view(n, nb)
+
+    def hypotheses(self):
+        """[n][n_best] token lists, each of its own length -- the one place that copies to the host."""
+        tok, lens = self.tokens.cpu().tolist(), self.lengths.cpu().tolist()
+        return [[row[:lens[i][j]] for j, row in enumerate(inst)] for i, inst in enumerate(tok)]
+
+
 class CachedDecoder(InstanceSession):
     """The cached row decoder over an InstanceSession: R = n_inst * n_rows rows (the n_rows rows of an instance share its encoder K/V),
     the per-layer encoder K/V computed once per batch (encode()), a self-attention cache per row, and one plan per (position, form),
@@ -254,7 +311,7 @@ class CaptionBeamSearch(CachedDecoder):
     for an instance that has finished.  The BeamResult holds the first n_active instances only."""
 
     def __init__(self, model, n_inst, W, F, n_bm=5, max_len=None, use_graphs=True, beam_step=None, constraints=None, beam_groups=1,
-                 diversity_penalty=0.0):
+                 diversity_penalty=0.0, length_penalty=None, early_stopping=False):
         """beam_step: "device" (default; univl_beam_step as the tail of each position's plan) | "host" (the ATen comparand);
         None: the UNIVL_AB key `beam_step` (default device).
         constraints: a constrain.DecodeConstraints (no repeated n-gram, a minimum length, suppressed ids) or None.  The launch sits
@@ -266,7 +323,13 @@ class CaptionBeamSearch(CachedDecoder):
         1 (default) is the plain search: the same plans launch for launch, no new buffer, the penalty unused.  With G > 1 the last
         launch of a position is univl_beam_group_step, `done` / `length` hold one entry per (instance, group), constraints see
         done_stride = k', the penalty is a device word (set_diversity), and beam_step="host" is a ValueError: the host comparand
-        has no group form."""
+        has no group form.
+        length_penalty, early_stopping: None (default) is the search above, the same plans launch for launch, no new buffer.  A
+        finite alpha >= 0 is beam search with a pool of finished hypotheses (include/univl_hip.h: univl_beam_pool_step): a beam that
+        emits the end token leaves the beams for the pool, hypotheses are ranked by raw * len ** -alpha, an instance is done when
+        its pool is full and (early_stopping, or no live beam can still enter it), and decode() returns a PoolBeamResult.  The last
+        launch of a position is univl_beam_pool_step; alpha and the mode are device words (set_length_penalty).  Out of scope, a
+        ValueError: together with beam_groups > 1 or beam_step="host"."""
         self.G, self.kp, penalty = check_beam_groups(n_bm, beam_groups, diversity_penalty)
         G, kp = self.G, self.kp
         if beam_step is None:
@@ -275,6 +338,8 @@ class CaptionBeamSearch(CachedDecoder):
             raise ValueError("CaptionBeamSearch: beam_step must be 'device' or 'host', got %r" % (beam_step,))
         if G > 1 and beam_step != "device":
             raise ValueError("CaptionBeamSearch: beam_groups=%d needs beam_step='device'; the host path has no group form" % G)
+        pooled = check_length_penalty(length_penalty, early_stopping, G, beam_step)
+        self.pooled = pooled is not None
         self.beam_step, self.n_bm = beam_step, n_bm
         P = n_inst * G                                   # (instance, group) pairs, the pseudo-instances of width k'
         super().__init__(model, n_inst, W, F, n_bm, P, max_len=max_len, use_graphs=use_graphs, constraints=constraints)
@@ -292,6 +357,12 @@ class CaptionBeamSearch(CachedDecoder):
         self.beam_ws = ops.beam_ws(n_inst, n_bm, dev) if beam_step == "device" else None
         if G > 1:
             self.diversity_dev = torch.full((1,), penalty, dtype=torch.float32, device=dev)     # a device word: the captured plans serve any penalty
+        if self.pooled:
+            # device words: the captured plans serve any penalty, stopping mode and max_len
+            self.length_penalty, self.early_stopping = pooled
+            self.pool_w = ops.length_weights(pooled[0], Tmax).to(dev)
+            self.pool_params = torch.tensor([pooled[1], Tmax], dtype=torch.int32, device=dev)
+            self.pool = ops.beam_pool(n_inst, n_bm, dev)
 
     # ------------------------------------------------------------------------------------------ step plans
     FORMS = (False, True)
@@ -310,13 +381,33 @@ class CaptionBeamSearch(CachedDecoder):
             return
         state = dict(scores=self.scores, done=self.done, length=self.length, tokens=self.ids, src=self.src, hist_parents=self.hist_par,
                      hist_tokens=self.hist_tok, hist_scores=self.hist_sc, ws=self.beam_ws, eos_dev=self.eos_dev)
-        if self.G > 1:
+        if self.pooled:
+            pl.add("univl_beam_pool_step", self._pool_desc(t))
+        elif self.G > 1:
             pl.add("univl_beam_group_step", ops.beam_group_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, self.G, t,
                                                                      diversity_dev=self.diversity_dev, **state))
         else:
             pl.add("univl_beam_step", ops.beam_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, t, **state))
 
+    def _pool_desc(self, t):
+        return ops.beam_pool_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done,
+                                       length=self.length, tokens=self.ids, src=self.src, hist_parents=self.hist_par,
+                                       hist_tokens=self.hist_tok, hist_scores=self.hist_sc, ws=self.beam_ws, eos_dev=self.eos_dev,
+                                       w=self.pool_w, params=self.pool_params, **self.pool)
+
     # ------------------------------------------------------------------------------------------------- run
+    def set_length_penalty(self, alpha, early_stopping=None):
+        """Rewrite the length penalty and (None: keep) the stopping mode of a session built with a length_penalty.  They are a device
+        table and a device word that the captured beam step reads: nothing is captured again."""
+        if not self.pooled:
+            raise ValueError("set_length_penalty: this session was built with length_penalty=None; its plans carry no pool step")
+        if alpha is None:
+            raise ValueError("set_length_penalty: alpha=None; the reference search is another session (length_penalty=None)")
+        alpha, es = check_length_penalty(alpha, self.early_stopping if early_stopping is None else early_stopping)
+        self.pool_w.copy_(ops.length_weights(alpha, self.Tmax))
+        self.pool_params[0:1].fill_(es)
+        self.length_penalty, self.early_stopping = alpha, es
+
     def set_diversity(self, penalty):
         """Rewrite the diversity penalty of a session built with beam_groups > 1.  It is a device word that the captured beam step
         reads: nothing is captured again."""
@@ -360,6 +451,9 @@ class CaptionBeamSearch(CachedDecoder):
         self.ids.fill_(int(bos))
         self.src.copy_(self.ident)
         self.eos_dev.fill_(int(eos))
+        if self.pooled:
+            self.pool["pool_count"].zero_()
+            self.pool_params[1:2].fill_(max_len)
         if self.beam_step == "device":
             ran = self._run_positions(True, max_len, sync_every, self.done)
         else:
@@ -368,6 +462,10 @@ class CaptionBeamSearch(CachedDecoder):
             self.hist_par[ran:max_len] = self.ident_nb
             self.hist_tok[ran:max_len] = self.hist_tok[ran - 1]
             self.hist_sc[ran:max_len] = self.hist_sc[ran - 1]
+        if self.pooled:
+            tokens, raw, key, lens, fin = ops.beam_pool_finish(self._pool_desc(0), n_best)
+            return PoolBeamResult(tokens[:m], raw[:m], key[:m], lens[:m], fin[:m], self.length[:m].clone(), self.hist_par[:max_len, :m].clone(),
+                                  self.hist_tok[:max_len, :m].clone(), self.hist_sc[:max_len, :m].clone())
         # the walk-back on the (n * G, k') view: the history's parents are local to their group (G = 1: the tensors as they are)
         tokens, scores = ops.beam_backtrack(self.hist_par.view(Tmax, n * G, kp), self.hist_tok.view(Tmax, n * G, kp),
                                             self.scores.view(n * G, kp), self.length, n_best)

@@ -131,7 +131,7 @@ class CaptionEvalResult:
 
 @torch.no_grad()
 def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, session=None, output_dir=None, nlg_eval=None,
-                 device="cuda", constraints=None, beam_groups=1, diversity_penalty=0.0):
+                 device="cuda", constraints=None, beam_groups=1, diversity_penalty=0.0, length_penalty=None, early_stopping=False):
     """Caption evaluation over a loader (main_task_caption.py:490-618).  batches: the reference loader's 12-tuples (:504-506);
     tokenizer: any object with vocab["[CLS]"], vocab["[SEP]"], vocab["[PAD]"] and convert_ids_to_tokens.  One CaptionBeamSearch,
     sized by the first batch (or the `session` passed in), decodes every batch; a smaller batch runs with n_active, a larger one is
@@ -143,15 +143,22 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
     they are a ValueError for the same reason.  With G > 1 groups n_best is counted per group, hyp_ids[item] holds G * n_best
     hypotheses group-major, scores is [items, G * n_best] and lengths [items, G].  hyps / hyp.txt still get the best hypothesis of
     group 0, which no penalty reaches: at ANY penalty that is the result of a plain beam search of width n_bm / G.
+    length_penalty, early_stopping: the pooled search for the session this call builds (decode.CaptionBeamSearch: a pool of finished
+    hypotheses ranked by raw * len ** -alpha); with a `session` they are a ValueError for the same reason.  scores stay the RAW sums
+    (not sorted then), lengths is [items, n_best], one per hypothesis, and hyps / hyp.txt get hypothesis 0, the pool's best.
     Returns a CaptionEvalResult; for a stage-one model an empty one (float() == 0.0, :495) without decoding anything."""
-    from .decode import CaptionBeamSearch, check_beam_groups
+    from .decode import CaptionBeamSearch, check_beam_groups, check_length_penalty
     if session is not None and constraints is not None:
         raise ValueError("eval_caption: constraints= with a supplied session; the session already owns its constraints "
                          "(CaptionBeamSearch(..., constraints=))")
     if session is not None and (beam_groups != 1 or diversity_penalty != 0.0):
         raise ValueError("eval_caption: beam_groups= / diversity_penalty= with a supplied session; the session already owns them "
                          "(CaptionBeamSearch(..., beam_groups=, diversity_penalty=))")
+    if session is not None and (length_penalty is not None or early_stopping not in (False, 0)):
+        raise ValueError("eval_caption: length_penalty= / early_stopping= with a supplied session; the session already owns them "
+                         "(CaptionBeamSearch(..., length_penalty=, early_stopping=))")
     check_beam_groups(n_bm, beam_groups, diversity_penalty)
+    check_length_penalty(length_penalty, early_stopping, beam_groups)
     if model._stage_one:
         return CaptionEvalResult([], [], [], torch.zeros(0, n_best), torch.zeros(0, dtype=torch.int32), None, None)
     bos, eos, pad = tokenizer.vocab["[CLS]"], tokenizer.vocab["[SEP]"], tokenizer.vocab["[PAD]"]
@@ -165,7 +172,8 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
             n = int(so.shape[0])
             if session is None:
                 session = CaptionBeamSearch(model, n, so.shape[1], vo.shape[1], n_bm=n_bm, max_len=max_len, constraints=constraints,
-                                            beam_groups=beam_groups, diversity_penalty=diversity_penalty)
+                                            beam_groups=beam_groups, diversity_penalty=diversity_penalty,
+                                            length_penalty=length_penalty, early_stopping=early_stopping)
             if n > session.n_inst:
                 raise ValueError("eval_caption: a batch of %d items does not fit the decoding session's %d instances"
                                  % (n, session.n_inst))

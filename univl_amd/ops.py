@@ -4,7 +4,9 @@ PyTorch is used here only for device memory and streams.  Every function fills t
 pointers/strides and raises RuntimeError on a non-zero status.  The execution plans in `univl_amd.engine` build the
 same descriptors once and replay them; these wrappers are the eager form (unit tests, small host-side ops)."""
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -419,6 +421,77 @@ def beam_group_step_desc(lp, V, n_inst, n_bm, n_groups, t, *, scores, done, leng
 def beam_group_step(*a, **kw):
     d = beam_group_step_desc(*a, **kw)
     _lib.check(_lib.lib().univl_beam_group_step(_BYREF(d), _stream()), "beam_group_step")
+
+
+def length_weights(alpha, Tmax):
+    """The length-weight table of univl_beam_pool_step as a CPU fp32 tensor of Tmax + 2 entries: w[L] = float32(float64(L) ** -alpha),
+    w[0] = 1.  alpha: a finite number >= 0 (ValueError otherwise; bool is refused)."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
+        raise ValueError("length_penalty=%r, expected a finite number >= 0" % (alpha,))
+    w = np.ones(Tmax + 2, dtype=np.float64)
+    w[1:] = np.arange(1, Tmax + 2, dtype=np.float64) ** -float(alpha)
+    return torch.from_numpy(w.astype(np.float32))
+
+
+def beam_pool(n_inst, n_bm, device):
+    """The pool arrays of univl_beam_pool_step for n_inst x n_bm beams, empty: a dict of the descriptor builder's pool arguments."""
+    z = lambda dt: torch.zeros(n_inst, n_bm, dtype=dt, device=device)
+    return dict(pool_key=z(torch.float32), pool_raw=z(torch.float32), pool_end_t=z(torch.int32), pool_beam=z(torch.int32),
+                pool_finished=z(torch.uint8), pool_count=torch.zeros(n_inst, dtype=torch.int32, device=device))
+
+
+def beam_pool_step_desc(lp, V, n_inst, n_bm, t, *, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, w, params,
+                        pool_key, pool_raw, pool_end_t, pool_beam, pool_finished, pool_count, eos=-1, eos_dev=None, first_step=None):
+    """beam_step_desc for the pooled search (include/univl_hip.h: UnivlBeamPoolStep).  w: fp32 [Tmax + 2] device table
+    (length_weights); params: int32 [2] device words {early_stopping, Lmax}; pool_*: [n_inst, n_bm] (beam_pool).  Shapes and dtypes
+    are checked here; the argument RANGE is the library's to refuse."""
+    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev, w, params, pool_key, pool_raw,
+                 pool_end_t, pool_beam, pool_finished, pool_count)
+    R = n_inst * n_bm
+    assert lp.dtype == torch.float32 and lp.dim() == 2 and lp.stride(1) == 1 and lp.shape[0] >= R
+    assert scores.dtype == torch.float32 and scores.numel() == R and scores.is_contiguous()
+    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == n_inst
+    assert length.dtype == torch.int32 and length.numel() == n_inst
+    assert tokens.dtype == torch.int64 and tokens.numel() == R and src.dtype == torch.int32 and src.numel() == R
+    Tmax = hist_parents.shape[0]
+    for h, dt_ in ((hist_parents, torch.int32), (hist_tokens, torch.int32), (hist_scores, torch.float32)):
+        assert h.dtype == dt_ and h.is_contiguous() and h.shape[0] == Tmax and h.numel() == Tmax * R
+    assert eos_dev is None or eos_dev.dtype == torch.int32
+    assert w.dtype == torch.float32 and w.numel() == Tmax + 2 and w.is_contiguous()
+    assert params.dtype == torch.int32 and params.numel() == 2 and params.is_contiguous()
+    for h, dt_ in ((pool_key, torch.float32), (pool_raw, torch.float32), (pool_end_t, torch.int32), (pool_beam, torch.int32),
+                   (pool_finished, torch.uint8)):
+        assert h.dtype == dt_ and h.numel() == R and h.is_contiguous()
+    assert pool_count.dtype == torch.int32 and pool_count.numel() == n_inst and pool_count.is_contiguous()
+    d = _lib.BeamPoolStep()
+    d.lp, d.ld, d.n_inst, d.n_bm, d.V = _p(lp), lp.stride(0), n_inst, n_bm, V
+    d.first_step, d.eos, d.eos_dev, d.t, d.Tmax = int(t == 0 if first_step is None else first_step), int(eos), _p(eos_dev), t, Tmax
+    d.scores, d.done, d.length, d.tokens, d.src = _p(scores), _p(done), _p(length), _p(tokens), _p(src)
+    d.hist_parents, d.hist_tokens, d.hist_scores = _p(hist_parents), _p(hist_tokens), _p(hist_scores)
+    d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
+    d.w, d.params = _p(w), _p(params)
+    d.pool_key, d.pool_raw, d.pool_end_t, d.pool_beam = _p(pool_key), _p(pool_raw), _p(pool_end_t), _p(pool_beam)
+    d.pool_finished, d.pool_count = _p(pool_finished), _p(pool_count)
+    return d
+
+
+def beam_pool_step(*a, **kw):
+    d = beam_pool_step_desc(*a, **kw)
+    _lib.check(_lib.lib().univl_beam_pool_step(_BYREF(d), _stream()), "beam_pool_step")
+
+
+def beam_pool_finish(desc, n_best):
+    """univl_beam_pool_finish on a descriptor of beam_pool_step_desc (its lp, ws and t are not looked at).  Returns (hyp [n, n_best,
+    Tmax] int32, -1 padded; raw [n, n_best] fp32; key [n, n_best] fp32; len [n, n_best] int32; finished [n, n_best] uint8)."""
+    n, Tmax, dev = desc.n_inst, desc.Tmax, torch.device("cuda", torch.cuda.current_device())
+    n_best = int(n_best)
+    hyp = torch.empty(n, max(n_best, 1), Tmax, dtype=torch.int32, device=dev)
+    raw, key = (torch.empty(n, max(n_best, 1), dtype=torch.float32, device=dev) for _ in range(2))
+    ln = torch.empty(n, max(n_best, 1), dtype=torch.int32, device=dev)
+    fin = torch.empty(n, max(n_best, 1), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().univl_beam_pool_finish(_BYREF(desc), n_best, _p(hyp), _p(raw), _p(key), _p(ln), _p(fin), _stream()),
+               "beam_pool_finish")
+    return hyp, raw, key, ln, fin
 
 
 def sample_ws(R, k, device):
