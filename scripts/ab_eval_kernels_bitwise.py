@@ -3,7 +3,9 @@ written to an .npz: run it once per build of the library, each in a fresh proces
 
     python scripts/ab_eval_kernels_bitwise.py <libunivl_hip.so> <out.npz>
 
-Entry points: univl_beam_step (a first and a later step, n_bm = 5), univl_sample_step (k = 50), univl_sim_topk (Nq = 33, Ng = 300,
+Entry points: univl_beam_step (a first and a later step, n_bm = 5), univl_beam_group_step (G = 2, lambda = 0.5, a first and a later
+step), univl_beam_pool_step over a run of tests/pool_beam_ref.py (n_bm = 5) with univl_beam_pool_finish (n_best = 3), univl_beam_backtrack
+-- each at (V, ld) = (37, 40) and (30522, 30528) with one of 3 instances preset done --, univl_sample_step (k = 50), univl_sim_topk (Nq = 33, Ng = 300,
 k = 10, with a target), univl_vocab_score, univl_vocab_ce_fwd / _bwd.  Every input set holds engineered ties: equal values whose
 order only the tie rule (lower index first) decides."""
 import os
@@ -51,6 +53,42 @@ def main(lib_path, out_path):
     state["done"][3] = 1                               # a frozen instance
     ops.beam_step(lp, V, n_inst, nb, 1, **state)
     keep("beam.later", **{k: v for k, v in state.items() if k != "ws"})
+
+    # ---- the group step, the pooled step with its finish, and the walk-back: 3 instances (the last one preset done: frozen rows) on
+    # the log-probabilities of tests/pool_beam_ref.py (multiples of 1/4: ties everywhere), scalar loads in one slice and 16-byte
+    # loads in several
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import pool_beam_ref as PR
+    n3, T3 = PR.N_INST, PR.TMAX
+
+    def beam_state(nb, units):
+        R3 = n3 * nb
+        s = dict(scores=torch.zeros(R3, device=dev), done=torch.zeros(units, dtype=torch.uint8, device=dev),
+                 length=torch.zeros(units, dtype=torch.int32, device=dev), tokens=torch.zeros(R3, dtype=torch.int64, device=dev),
+                 src=torch.zeros(R3, dtype=torch.int32, device=dev), hist_parents=torch.zeros(T3, n3, nb, dtype=torch.int32, device=dev),
+                 hist_tokens=torch.zeros(T3, n3, nb, dtype=torch.int32, device=dev), hist_scores=torch.zeros(T3, n3, nb, device=dev),
+                 ws=ops.beam_ws(n3, nb, dev))
+        s["done"][units - 1] = 1
+        return s
+
+    for Vb, ldb in ((37, 40), (30522, 30528)):
+        tag = "V%d" % Vb
+        lps = [torch.from_numpy(x).to(dev) for x in PR.make_lps(21, 4, Vb, ldb)]
+        s = beam_state(4, n3 * 2)
+        for t, name in ((0, "first"), (1, "later")):
+            ops.beam_group_step(lps[t], Vb, n3, 4, 2, t, diversity=0.5, eos=PR.EOS, **s)
+            keep("group.%s.%s" % (tag, name), **{k: v.clone() for k, v in s.items() if k != "ws"})
+        lps = [torch.from_numpy(x).to(dev) for x in PR.make_lps(PR.case_seed(5, Vb, 0, 0.6, False), 5, Vb, ldb)]
+        s = beam_state(5, n3)
+        pool = dict(ops.beam_pool(n3, 5, dev), w=ops.length_weights(0.6, T3).to(dev),
+                    params=torch.tensor([0, T3], dtype=torch.int32, device=dev))
+        for t in range(T3):
+            ops.beam_pool_step(lps[t], Vb, n3, 5, t, eos=PR.EOS, **s, **pool)
+            keep("pool.%s.t%d" % (tag, t), **{k: v.clone() for k, v in list(s.items()) + list(pool.items()) if k not in ("ws", "w", "params")})
+        hyp, raw, key, ln, fin = ops.beam_pool_finish(ops.beam_pool_step_desc(lps[0], Vb, n3, 5, 0, eos=PR.EOS, **s, **pool), 3)
+        keep("pool.%s.finish" % tag, hyp=hyp, raw=raw, key=key, len=ln, finished=fin)
+        hyp, hs = ops.beam_backtrack(s["hist_parents"], s["hist_tokens"], s["scores"].view(n3, 5), s["length"], 3)
+        keep("backtrack.%s" % tag, hyp=hyp, hyp_scores=hs)
 
     # ---- univl_sample_step: 12 rows, k = 50, top-p 0.9; rows of few distinct values, so that the k-th entry sits inside a tie
     Rs, k, Ts = 12, 50, 3

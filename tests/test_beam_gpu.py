@@ -230,6 +230,40 @@ def test_beam_step_argument_range():
         assert L.univl_beam_backtrack(*a) == EINVAL
 
 
+@pytest.mark.parametrize("entry", ["univl_beam_step", "univl_beam_group_step", "univl_beam_pool_step"])
+def test_step_entry_points_share_the_common_argument_rule(entry):
+    """The three step entry points refuse the same common arguments, each under its own name: UNIVL_EINVAL, univl_last_error()
+    beginning with the entry point's name, and the state untouched (nothing launched).  No kernel runs in this test."""
+    n, nb, G, V, ld, T = 2, 4, 2, 16, 16, 3
+    units = n * G if entry == "univl_beam_group_step" else n
+    z = lambda *shape, dt=torch.float32, fill=-7: torch.full(shape, fill, dtype=dt, device=DEV)
+    state = dict(scores=z(n, nb), done=z(units, dt=torch.uint8, fill=0), length=z(units, dt=torch.int32, fill=1), tokens=z(n * nb, dt=torch.int64),
+                 src=z(n * nb, dt=torch.int32), hist_parents=z(T, n, nb, dt=torch.int32), hist_tokens=z(T, n, nb, dt=torch.int32),
+                 hist_scores=z(T, n, nb), ws=ops.beam_ws(n, nb, DEV))
+    lp = torch.zeros(n * nb, ld, device=DEV)
+    if entry == "univl_beam_step":
+        desc = ops.beam_step_desc(lp, V, n, nb, 1, **state)
+    elif entry == "univl_beam_group_step":
+        desc = ops.beam_group_step_desc(lp, V, n, nb, G, 1, diversity=0.5, **state)
+    else:
+        pool = dict(ops.beam_pool(n, nb, DEV), w=ops.length_weights(0.6, T).to(DEV), params=torch.tensor([0, T], dtype=torch.int32, device=DEV))
+        desc = ops.beam_pool_step_desc(lp, V, n, nb, 1, **state, **pool)
+        state.update(pool)
+    before = {k: v.clone() for k, v in state.items() if k != "ws"}
+    L, EINVAL = _lib.lib(), -1
+    need = n * nb * _lib.BEAM_SLICES * nb * 8
+    assert desc.ws_bytes == need
+    for field, bad in (("n_bm", 9), ("ld", V - 1), ("t", T), ("scores", None), ("ws_bytes", need - 1), ("ws", state["ws"].data_ptr() + 4)):
+        good = getattr(desc, field)
+        setattr(desc, field, bad)
+        assert getattr(L, entry)(C.byref(desc), C.c_void_p(torch.cuda.current_stream().cuda_stream)) == EINVAL, field
+        assert L.univl_last_error().decode().startswith(entry + ":"), (field, L.univl_last_error())
+        setattr(desc, field, good)
+    torch.cuda.synchronize()
+    for k, v in before.items():
+        assert torch.equal(state[k], v), k
+
+
 # ------------------------------------------------------------------------------------------------ whole runs
 def _walk_back(parents, tokens, t, i, k=0):
     hyp = []

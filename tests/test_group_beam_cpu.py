@@ -134,6 +134,31 @@ def test_binding_refuses_cpu_tensors():
         ops.beam_group_step(torch.zeros(n * nb, V), V, n, nb, G, 0, diversity=0.5, **kw)
 
 
+@pytest.mark.parametrize("builder", ["beam_step_desc", "beam_group_step_desc", "beam_pool_step_desc"])
+def test_builders_refuse_the_same_wrong_common_arguments(builder):
+    """The three descriptor builders check their common arguments through one helper: each refuses a strided `done`, a `length` of
+    the wrong dtype and a `hist_tokens` whose first dimension is not hist_parents'.  No CPU test of these builders replaces
+    ops._require_gpu, so this one stays with what is reachable before the device check: the helper looks at shapes and dtypes
+    first, and CPU tensors are enough to reach every assertion.  With right arguments the device check is what refuses them."""
+    n, nb, G, V, T = 2, 4, 2, 16, 3
+    units = n * G if builder == "beam_group_step_desc" else n
+    head = (torch.zeros(n * nb, V), V, n, nb) + ((G, 0) if builder == "beam_group_step_desc" else (0,))
+    good = dict(scores=torch.zeros(n, nb), done=torch.zeros(units, dtype=torch.uint8), length=torch.zeros(units, dtype=torch.int32),
+                tokens=torch.zeros(n * nb, dtype=torch.int64), src=torch.zeros(n * nb, dtype=torch.int32),
+                hist_parents=torch.zeros(T, n, nb, dtype=torch.int32), hist_tokens=torch.zeros(T, n, nb, dtype=torch.int32),
+                hist_scores=torch.zeros(T, n, nb), ws=torch.zeros(n * nb * 8 * nb * 2))
+    if builder == "beam_pool_step_desc":
+        good.update(w=torch.ones(T + 2), params=torch.zeros(2, dtype=torch.int32), **ops.beam_pool(n, nb, "cpu"))
+    build = getattr(ops, builder)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        build(*head, **good)
+    for wrong in (dict(done=torch.zeros(2 * units, dtype=torch.uint8)[::2]),
+                  dict(length=torch.zeros(units, dtype=torch.int64)),
+                  dict(hist_tokens=torch.zeros(T + 1, n, nb, dtype=torch.int32))):
+        with pytest.raises(AssertionError):
+            build(*head, **dict(good, **wrong))
+
+
 def test_abi_is_declared_and_sized():
     assert "univl_beam_group_step" in _lib.EXPORTED and "univl_beam_group_step_sizeof" in _lib.EXPORTED
     assert _lib.BeamGroupStep not in _lib._STRUCTS and len(_lib._STRUCTS) == 12          # the numbered tables keep their length

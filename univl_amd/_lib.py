@@ -186,46 +186,20 @@ def lib():
                  "univl_beam_pool_step"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
-    L.univl_caption_overlap_sizeof.argtypes = []
-    L.univl_caption_overlap_sizeof.restype = i32
-    if L.univl_caption_overlap_sizeof() != C.sizeof(CaptionOverlap):
-        raise RuntimeError("ABI mismatch for CaptionOverlap: library %d bytes, ctypes %d"
-                           % (L.univl_caption_overlap_sizeof(), C.sizeof(CaptionOverlap)))
-    L.univl_ngram_df_sizeof.argtypes = []
-    L.univl_ngram_df_sizeof.restype = i32
-    if L.univl_ngram_df_sizeof() != C.sizeof(NgramDf):
-        raise RuntimeError("ABI mismatch for NgramDf: library %d bytes, ctypes %d" % (L.univl_ngram_df_sizeof(), C.sizeof(NgramDf)))
+    for name, st in (("univl_caption_overlap_sizeof", CaptionOverlap), ("univl_ngram_df_sizeof", NgramDf),
+                     ("univl_vocab_ce_weighted_sizeof", VocabCEW), ("univl_vocab_ce_smooth_sizeof", VocabCES),
+                     ("univl_decode_constrain_sizeof", DecodeConstrain), ("univl_beam_group_step_sizeof", BeamGroupStep),
+                     ("univl_beam_pool_step_sizeof", BeamPoolStep)):
+        f = getattr(L, name)
+        f.argtypes, f.restype = [], i32
+        if f() != C.sizeof(st):
+            raise RuntimeError("ABI mismatch for %s: library %d bytes, ctypes %d" % (st.__name__, f(), C.sizeof(st)))
     L.univl_ngram_df_tile.argtypes = []
     L.univl_ngram_df_tile.restype = i32
     if L.univl_ngram_df_tile() != NGRAM_DF_TILE:
         raise RuntimeError("univl_ngram_df: the library's tile is %d keys, the binding's %d" % (L.univl_ngram_df_tile(), NGRAM_DF_TILE))
     L.univl_ngram_df_ws_bytes.argtypes = [i32, i32]
     L.univl_ngram_df_ws_bytes.restype = i64
-    L.univl_vocab_ce_weighted_sizeof.argtypes = []
-    L.univl_vocab_ce_weighted_sizeof.restype = i32
-    if L.univl_vocab_ce_weighted_sizeof() != C.sizeof(VocabCEW):
-        raise RuntimeError("ABI mismatch for VocabCEW: library %d bytes, ctypes %d"
-                           % (L.univl_vocab_ce_weighted_sizeof(), C.sizeof(VocabCEW)))
-    L.univl_vocab_ce_smooth_sizeof.argtypes = []
-    L.univl_vocab_ce_smooth_sizeof.restype = i32
-    if L.univl_vocab_ce_smooth_sizeof() != C.sizeof(VocabCES):
-        raise RuntimeError("ABI mismatch for VocabCES: library %d bytes, ctypes %d"
-                           % (L.univl_vocab_ce_smooth_sizeof(), C.sizeof(VocabCES)))
-    L.univl_decode_constrain_sizeof.argtypes = []
-    L.univl_decode_constrain_sizeof.restype = i32
-    if L.univl_decode_constrain_sizeof() != C.sizeof(DecodeConstrain):
-        raise RuntimeError("ABI mismatch for DecodeConstrain: library %d bytes, ctypes %d"
-                           % (L.univl_decode_constrain_sizeof(), C.sizeof(DecodeConstrain)))
-    L.univl_beam_group_step_sizeof.argtypes = []
-    L.univl_beam_group_step_sizeof.restype = i32
-    if L.univl_beam_group_step_sizeof() != C.sizeof(BeamGroupStep):
-        raise RuntimeError("ABI mismatch for BeamGroupStep: library %d bytes, ctypes %d"
-                           % (L.univl_beam_group_step_sizeof(), C.sizeof(BeamGroupStep)))
-    L.univl_beam_pool_step_sizeof.argtypes = []
-    L.univl_beam_pool_step_sizeof.restype = i32
-    if L.univl_beam_pool_step_sizeof() != C.sizeof(BeamPoolStep):
-        raise RuntimeError("ABI mismatch for BeamPoolStep: library %d bytes, ctypes %d"
-                           % (L.univl_beam_pool_step_sizeof(), C.sizeof(BeamPoolStep)))
     L.univl_beam_pool_finish.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.univl_beam_pool_finish.restype = i32
     L.univl_caption_advantage.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, vp, vp]

@@ -9,6 +9,9 @@
 //   phase 2  one wave per instance: the n_bm best of the (1 or n_bm) x slices x n_bm pairs, then parents / tokens / state / history.
 // Order of candidates everywhere: larger value first, equal values by LOWER flat index b * V + v first (`better`, ranked.h).
 //
+// The select kernels of the three steps are built from the same stages, each a function below: write_frozen, stage_pairs,
+// best_rounds, write_winner; the walk-backs from clamp_len and walk_back.  On the host step_args states the common argument rule.
+//
 // univl_beam_group_step is Diverse Beam Search (Vijayakumar et al.: beam groups, Hamming diversity) on the same two launches.  The G
 // groups of width k' = n_bm / G of an instance are the pseudo-instances i * G + g of an ordinary search of width k': `done`, `length`
 // and the history are laid out that way, and phase 1 is the scan above with the frozen test reading done[row / k'] (its `stride`) while
@@ -24,10 +27,9 @@
 //
 // univl_beam_pool_step / univl_beam_pool_finish are beam search with a pool of finished hypotheses, a length penalty and an
 // early-stopping switch, on the same two launches per position (include/univl_hip.h states the rule).  Live beams never hold the end
-// token: phase 1 is the scan above with the end column left out (beam_scan_kernel<NB, true>), the workspace that of univl_beam_step,
-// and phase 2 (beam_pool_select_kernel, which carries the sufficiency argument) reads the n_bm end-column values itself, ranks them
-// among all candidates and offers those of rank < n_bm to the instance's pool, kept in the LDS of its one wave.  Keys are
-// raw * w[len] with w a HOST-filled table: no powf on the device.  With no end token (eos < 0) the step is univl_beam_step bit for bit.
+// token: phase 1 is the scan above with the end column left out (beam_scan_kernel<NB, true>), and phase 2 (beam_pool_select_kernel,
+// which carries the sufficiency argument) reads the n_bm end-column values itself.  Keys are raw * w[len] with w a HOST-filled table:
+// no powf on the device.  With no end token (eos < 0) the step is univl_beam_step bit for bit.
 #include <cmath>
 
 #include "common.h"
@@ -121,6 +123,67 @@ struct BeamOut {
     int32_t* hist_parents; int32_t* hist_tokens; float* hist_scores;
 };
 
+__device__ __forceinline__ int clamp_len(int len, int Tmax) { return len < 0 ? 0 : (len > Tmax ? Tmax : len); }
+
+// ---- the stages of phase 2; one wave, `lane` its thread.  A unit is what freezes together: an instance, or a group of one.
+// A frozen unit of `width` beams from state slot s0: the state stays, the history row repeats it under identity parents.
+__device__ __forceinline__ void write_frozen(const BeamOut& o, long hist_row, long s0, int width, int lane) {
+    if (lane < width) {
+        o.src[s0 + lane] = (int32_t)(s0 + lane);
+        o.hist_parents[hist_row + s0 + lane] = lane;
+        o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
+        o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
+    }
+}
+
+// The ncand workspace pairs from `at` on (per_row per row, the first of them the instance's beam b0) into LDS as (value, flat index
+// b * V + column); also(c, value, column) sees every pair on its way (the group step's ranked value).
+template <class Also>
+__device__ __forceinline__ void stage_pairs(const float* ws_val, const int* ws_idx, long at, int ncand, int per_row,
+                                            int b0, int V, float* cv, int* ci, int lane, Also also) {
+    for (int c = lane; c < ncand; c += 64) {
+        const int col = ws_idx[at + c];
+        const float v = ws_val[at + c];
+        cv[c] = v;
+        also(c, v, col);
+        ci[c] = col == RANK_NONE ? RANK_NONE : (b0 + c / per_row) * V + col;
+    }
+}
+
+// n rounds of the wave's best (key, index) among the staged pairs; the lane that owns a round's winner (flat indices are unique: one
+// owner) retires its slot.  take(r, v, i, at, own): what the kernel does with round r's winner (v, i), which every lane holds; `own`
+// is true in the owner, whose slot it was at `at`.  i == RANK_NONE: nothing comparable was left.
+template <class Take>
+__device__ __forceinline__ void best_rounds(int n, float* key, int* ci, int ncand, int lane, Take take) {
+    for (int r = 0; r < n; ++r) {
+        float v = -INFINITY;
+        int i = RANK_NONE, at = -1;
+        for (int c = lane; c < ncand; c += 64)
+            if (better(key[c], ci[c], v, i)) { v = key[c]; i = ci[c]; at = c; }
+        const int mine = i;
+        wave_best(v, i);
+        const bool own = i != RANK_NONE && mine == i;
+        if (own) { key[at] = -INFINITY; ci[at] = RANK_NONE; }
+        take(r, v, i, at, own);
+    }
+}
+
+// Winner (v, i) into slot `lane` of the unit whose first state slot is s0 and whose first beam within the instance is b0; the
+// history's parent is local to the unit.  Returns the token.  Fewer comparable candidates than slots (NaN rows: unspecified result)
+// must still leave in-range indices behind: an empty winner stands for column 0 of the slot's own row.
+// (The pointer parameters of these stages carry no __restrict__ and the sums are spelled s0 + lane on purpose: with either changed
+// the plain kernel's instructions change.)
+__device__ __forceinline__ int write_winner(const BeamOut& o, long hist_row, long s0, int b0, int lane, float v, int i, int V) {
+    const int flat = i == RANK_NONE ? (b0 + lane) * V : i, parent = flat / V, token = flat % V;
+    o.scores[s0 + lane] = v;
+    o.tokens[s0 + lane] = token;
+    o.src[s0 + lane] = (int32_t)(s0 - b0 + parent);
+    o.hist_parents[hist_row + s0 + lane] = parent - b0;
+    o.hist_tokens[hist_row + s0 + lane] = token;
+    o.hist_scores[hist_row + s0 + lane] = v;
+    return token;
+}
+
 // one wave per instance; at most 8 x 8 x 8 = 512 pairs
 __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx, int n_bm, int V, int slices,
                                                          int first_step, int eos, const int32_t* __restrict__ eos_dev, long hist_row, BeamOut o) {
@@ -130,46 +193,32 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict
     __shared__ int win_i[8];
     const int inst = blockIdx.x, lane = threadIdx.x;
     const long s0 = (long)inst * n_bm;                        // first row / state slot of the instance
-    if (o.done[inst]) {                                       // frozen: state untouched, the history row repeats it
-        if (lane < n_bm) {
-            o.src[s0 + lane] = (int32_t)(s0 + lane);
-            o.hist_parents[hist_row + s0 + lane] = lane;
-            o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
-            o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
-        }
-        return;
-    }
+    if (o.done[inst]) { write_frozen(o, hist_row, s0, n_bm, lane); return; }
     const int per_row = slices * n_bm, ncand = (first_step ? 1 : n_bm) * per_row;
-    for (int c = lane; c < ncand; c += 64) {
-        const int b = c / per_row, col = ws_idx[s0 * per_row + c];
-        cv[c] = ws_val[s0 * per_row + c];
-        ci[c] = col == RANK_NONE ? RANK_NONE : b * V + col;
-    }
+    stage_pairs(ws_val, ws_idx, s0 * per_row, ncand, per_row, 0, V, cv, ci, lane, [](int, float, int) {});
     __syncthreads();
-    for (int r = 0; r < n_bm; ++r) {
-        float v = -INFINITY;
-        int i = RANK_NONE, at = -1;
-        for (int c = lane; c < ncand; c += 64)
-            if (better(cv[c], ci[c], v, i)) { v = cv[c]; i = ci[c]; at = c; }
-        const int mine = i;
-        wave_best(v, i);
-        if (i != RANK_NONE && mine == i) { cv[at] = -INFINITY; ci[at] = RANK_NONE; }      // flat indices are unique: one owner
+    best_rounds(n_bm, cv, ci, ncand, lane, [&](int r, float v, int i, int, bool) {
         if (lane == 0) { win_v[r] = v; win_i[r] = i; }
         __syncthreads();
-    }
+    });
     if (lane < n_bm) {
-        // fewer than n_bm comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
-        const int flat = win_i[lane] == RANK_NONE ? lane * V : win_i[lane], parent = flat / V, token = flat % V;
-        o.scores[s0 + lane] = win_v[lane];
-        o.tokens[s0 + lane] = token;
-        o.src[s0 + lane] = (int32_t)(s0 + parent);
-        o.hist_parents[hist_row + s0 + lane] = parent;
-        o.hist_tokens[hist_row + s0 + lane] = token;
-        o.hist_scores[hist_row + s0 + lane] = win_v[lane];
+        const int token = write_winner(o, hist_row, s0, 0, lane, win_v[lane], win_i[lane], V);
         if (lane == 0) {
             o.length[inst] += 1;
             if (token == (eos_dev ? *eos_dev : eos)) o.done[inst] = 1;               // beam.py:84: the TOP beam emitted EOS
         }
+    }
+}
+
+// Row e of hyp: the len tokens that end in beam b of the instance at position len - 1, walked back through the history; -1 past them.
+__device__ __forceinline__ void walk_back(const int32_t* __restrict__ hp, const int32_t* __restrict__ ht, int n_inst, int inst, int n_bm, int b,
+                                          int len, int Tmax, int32_t* __restrict__ out) {
+    for (int j = len; j < Tmax; ++j) out[j] = -1;
+    for (int j = len - 1; j >= 0; --j) {
+        b = b < 0 ? 0 : (b >= n_bm ? n_bm - 1 : b);            // a corrupt history (or pool) must not walk out of the arrays
+        const long at = ((long)j * n_inst + inst) * n_bm + b;
+        out[j] = ht[at];
+        b = hp[at];
     }
 }
 
@@ -179,17 +228,7 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(const int32_t* __res
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= n_inst * n_best) return;
     const int inst = e / n_best, k = e % n_best;
-    int len = length[inst];
-    len = len < 0 ? 0 : (len > Tmax ? Tmax : len);
-    int32_t* out = hyp + (long)e * Tmax;
-    for (int j = len; j < Tmax; ++j) out[j] = -1;
-    int b = k;
-    for (int j = len - 1; j >= 0; --j) {
-        const long at = ((long)j * n_inst + inst) * n_bm + b;
-        out[j] = ht[at];
-        b = hp[at];
-        b = b < 0 ? 0 : (b >= n_bm ? n_bm - 1 : b);            // a corrupt history must not walk out of the arrays
-    }
+    walk_back(hp, ht, n_inst, inst, n_bm, k, clamp_len(length[inst], Tmax), Tmax, hyp + (long)e * Tmax);
     hyp_scores[e] = scores[(long)inst * n_bm + k];
 }
 
@@ -201,8 +240,7 @@ __global__ __launch_bounds__(256) void beam_captions_kernel(const int32_t* hyp, 
                                                             int32_t* __restrict__ cap_len) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;                                  // whole waves leave: the ballots below see full rows only
-    int len = length[row / n_best];
-    len = len < 0 ? 0 : (len > Tmax ? Tmax : len);
+    const int len = clamp_len(length[row / n_best], Tmax);
     const int end = eos_dev ? *eos_dev : eos;
     const int32_t* in = hyp + (long)row * Tmax;
     int32_t* out = cap_tokens + (long)row * Tmax;
@@ -221,7 +259,7 @@ __global__ __launch_bounds__(256) void beam_captions_kernel(const int32_t* hyp, 
     if (lane == 0) cap_len[row] = cut;
 }
 
-// Phase 2 of univl_beam_group_step: one wave per instance, its G groups in order.  A stage stages the (value, flat index) pairs of
+// Phase 2 of univl_beam_group_step: one wave per instance, its G groups in order.  A group stages the (value, flat index) pairs of
 // its own k' rows (at most 8 x 8 x 8 = 512 for G = 1) together with their ranked value, takes k' rounds of wave_best on `ranked`,
 // re-sorts the k' winners by their unpenalised value and appends their tokens to pen_tok, the list the later stages count c(v) in
 // (at most n_bm - k' entries when it is read; a token chosen by several beams stands there once per beam, so the count is the
@@ -249,40 +287,18 @@ __global__ __launch_bounds__(64) void beam_group_select_kernel(const float* __re
     for (int g = 0; g < n_groups; ++g) {
         const int grp = inst * n_groups + g, b0 = g * kp;     // the pseudo-instance; the group's first beam within the instance
         const long s0 = (long)inst * n_bm + b0;               // its first row / state slot
-        if (o.done[grp]) {                                    // frozen (wave-uniform): as a frozen instance of beam_select_kernel
-            if (lane < kp) {
-                o.src[s0 + lane] = (int32_t)(s0 + lane);
-                o.hist_parents[hist_row + s0 + lane] = lane;
-                o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
-                o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
-            }
-            continue;
-        }
+        if (o.done[grp]) { write_frozen(o, hist_row, s0, kp, lane); continue; }          // wave-uniform
         const int ncand = (first_step ? 1 : kp) * per_row;
-        for (int c = lane; c < ncand; c += 64) {
-            const int col = ws_idx[s0 * per_row + c];
-            const float v = ws_val[s0 * per_row + c];
+        stage_pairs(ws_val, ws_idx, s0 * per_row, ncand, per_row, b0, V, cv, ci, lane, [&](int c, float v, int col) {
             int cnt = 0;
             for (int j = 0; j < npen; ++j) cnt += pen_tok[j] == col ? 1 : 0;
-            cv[c] = v;
             rk[c] = ranked_value(v, lambda, cnt);
-            ci[c] = col == RANK_NONE ? RANK_NONE : (b0 + c / per_row) * V + col;
-        }
+        });
         // a lane reads back only the slots it wrote (c = lane mod 64): no barrier until the winners are exchanged
-        for (int r = 0; r < kp; ++r) {
-            float v = -INFINITY;
-            int i = RANK_NONE, at = -1;
-            for (int c = lane; c < ncand; c += 64)
-                if (better(rk[c], ci[c], v, i)) { v = rk[c]; i = ci[c]; at = c; }
-            const int mine = i;
-            wave_best(v, i);
-            if (i == RANK_NONE) {
-                if (lane == 0) { win_v[r] = -INFINITY; win_i[r] = RANK_NONE; }
-            } else if (mine == i) {                            // flat indices are unique: one owner
-                win_v[r] = cv[at]; win_i[r] = i;
-                rk[at] = -INFINITY; ci[at] = RANK_NONE;
-            }
-        }
+        best_rounds(kp, rk, ci, ncand, lane, [&](int r, float, int i, int at, bool own) {
+            if (own) { win_v[r] = cv[at]; win_i[r] = i; }      // selected by the ranked value, stored with the unpenalised one
+            else if (i == RANK_NONE && lane == 0) { win_v[r] = -INFINITY; win_i[r] = RANK_NONE; }
+        });
         __syncthreads();
         if (lane < kp) {                                      // place among the k' winners by (value, flat index); slot order settles empty ones
             const float mv = win_v[lane];
@@ -294,14 +310,7 @@ __global__ __launch_bounds__(64) void beam_group_select_kernel(const float* __re
         }
         __syncthreads();
         if (lane < kp) {
-            // fewer than k' comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
-            const int flat = srt_i[lane] == RANK_NONE ? (b0 + lane) * V : srt_i[lane], parent = flat / V, token = flat % V;
-            o.scores[s0 + lane] = srt_v[lane];
-            o.tokens[s0 + lane] = token;
-            o.src[s0 + lane] = (int32_t)((long)inst * n_bm + parent);
-            o.hist_parents[hist_row + s0 + lane] = parent - b0;           // local to the group: the pseudo-instance view
-            o.hist_tokens[hist_row + s0 + lane] = token;
-            o.hist_scores[hist_row + s0 + lane] = srt_v[lane];
+            const int token = write_winner(o, hist_row, s0, b0, lane, srt_v[lane], srt_i[lane], V);
             pen_tok[npen + lane] = token;
             if (lane == 0) {
                 o.length[grp] += 1;
@@ -380,23 +389,11 @@ __global__ __launch_bounds__(64) void beam_pool_select_kernel(const float* __res
     __shared__ int cnt_s;
     const int inst = blockIdx.x, lane = threadIdx.x;
     const long s0 = (long)inst * n_bm;                        // first row / state slot / pool slot of the instance
-    if (o.done[inst]) {                                       // frozen as in beam_select_kernel; the pool is untouched too
-        if (lane < n_bm) {
-            o.src[s0 + lane] = (int32_t)(s0 + lane);
-            o.hist_parents[hist_row + s0 + lane] = lane;
-            o.hist_tokens[hist_row + s0 + lane] = (int32_t)o.tokens[s0 + lane];
-            o.hist_scores[hist_row + s0 + lane] = o.scores[s0 + lane];
-        }
-        return;
-    }
+    if (o.done[inst]) { write_frozen(o, hist_row, s0, n_bm, lane); return; }          // the pool is untouched too
     const int end = eos_dev ? *eos_dev : eos, nrows = first_step ? 1 : n_bm;
     const bool has_end = end >= 0 && end < V;
     const int per_row = slices * n_bm, ncand = nrows * per_row;
-    for (int c = lane; c < ncand; c += 64) {
-        const int b = c / per_row, col = ws_idx[s0 * per_row + c];
-        cv[c] = ws_val[s0 * per_row + c];
-        ci[c] = col == RANK_NONE ? RANK_NONE : b * V + col;
-    }
+    stage_pairs(ws_val, ws_idx, s0 * per_row, ncand, per_row, 0, V, cv, ci, lane, [](int, float, int) {});
     if (lane < 8) {                                           // the end candidates, formed as the scan forms a candidate
         float v = -INFINITY;
         if (has_end && lane < nrows) {
@@ -407,17 +404,10 @@ __global__ __launch_bounds__(64) void beam_pool_select_kernel(const float* __res
     }
     int cnt = pool_load(q, p, s0, inst, n_bm, lane);
     __syncthreads();
-    for (int r = 0; r < n_bm; ++r) {                          // the live beams: beam_select_kernel's rounds
-        float v = -INFINITY;
-        int i = RANK_NONE, at = -1;
-        for (int c = lane; c < ncand; c += 64)
-            if (better(cv[c], ci[c], v, i)) { v = cv[c]; i = ci[c]; at = c; }
-        const int mine = i;
-        wave_best(v, i);
-        if (i != RANK_NONE && mine == i) { cv[at] = -INFINITY; ci[at] = RANK_NONE; }
+    best_rounds(n_bm, cv, ci, ncand, lane, [&](int r, float v, int i, int, bool) {        // the live beams: beam_select_kernel's rounds
         if (lane == 0) { win_v[r] = v; win_i[r] = i; }
         __syncthreads();
-    }
+    });
     // lane b: the rank of end candidate b; the taken ones, in candidate order, into ord[]
     bool taken = false;
     if (lane < nrows) {
@@ -433,16 +423,7 @@ __global__ __launch_bounds__(64) void beam_pool_select_kernel(const float* __res
     }
     const int ntaken = __popcll(__ballot(taken));
     __syncthreads();
-    if (lane < n_bm) {
-        // fewer than n_bm comparable candidates (NaN rows: unspecified result) must still leave in-range indices behind
-        const int flat = win_i[lane] == RANK_NONE ? lane * V : win_i[lane], parent = flat / V, token = flat % V;
-        o.scores[s0 + lane] = win_v[lane];
-        o.tokens[s0 + lane] = token;
-        o.src[s0 + lane] = (int32_t)(s0 + parent);
-        o.hist_parents[hist_row + s0 + lane] = parent;
-        o.hist_tokens[hist_row + s0 + lane] = token;
-        o.hist_scores[hist_row + s0 + lane] = win_v[lane];
-    }
+    if (lane < n_bm) write_winner(o, hist_row, s0, 0, lane, win_v[lane], win_i[lane], V);
     if (lane == 0) {
         const float wl = p.w[t + 1];                          // len = t + 1 <= Tmax
         for (int k = 0; k < ntaken; ++k) {
@@ -451,8 +432,7 @@ __global__ __launch_bounds__(64) void beam_pool_select_kernel(const float* __res
         }
         o.length[inst] += 1;
         if (cnt == n_bm) {
-            int lmax = p.params[1];
-            lmax = lmax < 0 ? 0 : (lmax > Tmax + 1 ? Tmax + 1 : lmax);
+            const int lmax = clamp_len(p.params[1], Tmax + 1);
             if (p.params[0] != 0 || win_v[0] * p.w[lmax] <= q.key[pool_last(q, cnt)]) o.done[inst] = 1;
         }
         p.count[inst] = cnt;
@@ -483,8 +463,7 @@ __global__ __launch_bounds__(64) void beam_pool_finish_kernel(int n_inst, int n_
     __syncthreads();
     if (lane == 0) {
         if (!done[inst]) {
-            int len = length[inst];
-            len = len < 0 ? 0 : (len > Tmax ? Tmax : len);
+            const int len = clamp_len(length[inst], Tmax);
             const float wl = p.w[len];
             for (int b = 0; b < n_bm; ++b) pool_offer(q, cnt, n_bm, scores[s0 + b] * wl, scores[s0 + b], len, b, 0);
         }
@@ -510,17 +489,8 @@ __global__ __launch_bounds__(64) void beam_pool_finish_kernel(int n_inst, int n_
         h.raw[e] = -INFINITY; h.key[e] = -INFINITY; h.len[e] = 0; h.fin[e] = 0;
         return;
     }
-    const int s = srt[lane], fin = q.fin[s] ? 1 : 0;
-    int ntok = q.end_t[s];
-    ntok = ntok < 0 ? 0 : (ntok > Tmax ? Tmax : ntok);
-    for (int j = ntok; j < Tmax; ++j) out[j] = -1;
-    int b = q.beam[s];
-    for (int j = ntok - 1; j >= 0; --j) {
-        b = b < 0 ? 0 : (b >= n_bm ? n_bm - 1 : b);            // a corrupt history must not walk out of the arrays
-        const long at = ((long)j * n_inst + inst) * n_bm + b;
-        out[j] = ht[at];
-        b = hp[at];
-    }
+    const int s = srt[lane], fin = q.fin[s] ? 1 : 0, ntok = clamp_len(q.end_t[s], Tmax);
+    walk_back(hp, ht, n_inst, inst, n_bm, q.beam[s], ntok, Tmax, out);
     if (fin && ntok < Tmax) out[ntok] = eos_dev ? *eos_dev : eos;        // the end token that finished it: the row holds len tokens
     h.raw[e] = q.raw[s]; h.key[e] = q.key[s]; h.fin[e] = (uint8_t)fin;
     h.len[e] = fin && ntok < Tmax ? ntok + 1 : ntok;
@@ -565,31 +535,56 @@ int scan_rows(const Scan& a, int n_bm, void* ws, float** ws_val, int** ws_idx, h
     return slices;
 }
 
+// The range that every descriptor entry point shares.
+template <class D>
+bool beam_dims_ok(const D* d) {
+    return d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2;
+}
+
+// What a step entry point works with once step_args has accepted its descriptor; `scan` is the plain step's, the caller adjusts it.
+struct Step {
+    int64_t rows; long hist_row; int first_step; BeamOut o; Scan scan;
+};
+
+// The argument rule of UnivlBeamStep's fields, which UnivlBeamGroupStep and UnivlBeamPoolStep begin with in its order; `who` is the
+// entry point's name.  UNIVL_OK, or UNIVL_EINVAL with the error text set.
+template <class D>
+int step_args(const char* who, const D* d, Step* s) {
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
+    UNIVL_CHECK_ARG(beam_dims_ok(d) && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V && d->V <= INT_MAX / UNIVL_BEAM_MAX, UNIVL_EINVAL,
+                    "%s: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", who, d->n_inst, d->n_bm, d->V, (long long)d->ld,
+                    UNIVL_BEAM_MAX);
+    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "%s: history row t=%d of Tmax=%d", who, d->t, d->Tmax);
+    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
+                    d->ws, UNIVL_EINVAL, "%s: null pointer", who);
+    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
+    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
+    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
+                    "%s: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); got %lld", who,
+                    (long long)need, (long long)d->ws_bytes);
+    const int first_step = d->first_step ? 1 : 0;
+    *s = Step{rows, (long)d->t * rows, first_step,
+              BeamOut{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores},
+              Scan{d->lp, (long)d->ld, d->V, first_step, d->scores, d->done, d->n_inst, d->n_bm}};
+    return UNIVL_OK;
+}
+
+BeamPool pool_of(const UnivlBeamPoolStep* d) {
+    return BeamPool{d->w, d->params, d->pool_key, d->pool_raw, d->pool_end_t, d->pool_beam, d->pool_finished, d->pool_count};
+}
+
 }  // namespace
 
 extern "C" int univl_beam_step(const UnivlBeamStep* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_step: null descriptor");
-    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V &&
-                    d->V <= INT_MAX / UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
-                    "univl_beam_step: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", d->n_inst, d->n_bm, d->V,
-                    (long long)d->ld, UNIVL_BEAM_MAX);
-    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "univl_beam_step: history row t=%d of Tmax=%d", d->t, d->Tmax);
-    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
-                    d->ws, UNIVL_EINVAL, "univl_beam_step: null pointer");
-    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
-    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
-    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
-                    "univl_beam_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); got %lld",
-                    (long long)need, (long long)d->ws_bytes);
+    Step s;
+    if (const int rc = step_args("univl_beam_step", d, &s)) return rc;
     float* ws_val;
     int* ws_idx;
-    const Scan a{d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores, d->done, d->n_inst, d->n_bm};
-    const int slices = scan_rows(a, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
+    const int slices = scan_rows(s.scan, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
     UNIVL_LAUNCH_CHECK();
-    BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
-    hipLaunchKernelGGL(beam_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->V, slices, d->first_step ? 1 : 0,
-                       d->eos, d->eos_dev, (long)d->t * rows, o);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->V, slices, s.first_step, d->eos,
+                       d->eos_dev, s.hist_row, s.o);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
@@ -598,32 +593,21 @@ extern "C" int univl_beam_group_step_sizeof(void) { return (int)sizeof(UnivlBeam
 
 extern "C" int univl_beam_group_step(const UnivlBeamGroupStep* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_group_step: null descriptor");
-    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V &&
-                    d->V <= INT_MAX / UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
-                    "univl_beam_group_step: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", d->n_inst, d->n_bm, d->V,
-                    (long long)d->ld, UNIVL_BEAM_MAX);
+    Step s;
+    if (const int rc = step_args("univl_beam_group_step", d, &s)) return rc;
     UNIVL_CHECK_ARG(d->n_groups >= 1 && d->n_groups <= d->n_bm && d->n_bm % d->n_groups == 0, UNIVL_EINVAL,
                     "univl_beam_group_step: n_groups=%d does not divide n_bm=%d (1 <= n_groups <= n_bm)", d->n_groups, d->n_bm);
     UNIVL_CHECK_ARG(d->diversity_dev != nullptr || (std::isfinite(d->diversity) && d->diversity >= 0.f), UNIVL_EINVAL,
                     "univl_beam_group_step: diversity=%g, expected finite and >= 0 (the per-row top-n_bm lists hold every winner only then)",
                     (double)d->diversity);
-    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "univl_beam_group_step: history row t=%d of Tmax=%d", d->t, d->Tmax);
-    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
-                    d->ws, UNIVL_EINVAL, "univl_beam_group_step: null pointer");
-    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
-    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
-    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
-                    "univl_beam_group_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); "
-                    "got %lld", (long long)need, (long long)d->ws_bytes);
+    s.scan.n_units = d->n_inst * d->n_groups;                 // a group freezes on its own
+    s.scan.stride = d->n_bm / d->n_groups;
     float* ws_val;
     int* ws_idx;
-    const Scan a{d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores, d->done, d->n_inst * d->n_groups, d->n_bm / d->n_groups};
-    const int slices = scan_rows(a, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
+    const int slices = scan_rows(s.scan, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
     UNIVL_LAUNCH_CHECK();
-    BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
     hipLaunchKernelGGL(beam_group_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->n_bm, d->n_groups, d->V, slices,
-                       d->first_step ? 1 : 0, d->eos, d->eos_dev, d->diversity, d->diversity_dev, (long)d->t * rows, o);
+                       s.first_step, d->eos, d->eos_dev, d->diversity, d->diversity_dev, s.hist_row, s.o);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
@@ -632,30 +616,18 @@ extern "C" int univl_beam_pool_step_sizeof(void) { return (int)sizeof(UnivlBeamP
 
 extern "C" int univl_beam_pool_step(const UnivlBeamPoolStep* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_pool_step: null descriptor");
-    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && d->V >= 1 && d->n_bm <= d->V && d->ld >= d->V &&
-                    d->V <= INT_MAX / UNIVL_BEAM_MAX && (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
-                    "univl_beam_pool_step: n_inst=%d n_bm=%d V=%d ld=%lld (1 <= n_bm <= %d, n_bm <= V <= ld)", d->n_inst, d->n_bm, d->V,
-                    (long long)d->ld, UNIVL_BEAM_MAX);
-    UNIVL_CHECK_ARG(d->t >= 0 && d->t < d->Tmax, UNIVL_EINVAL, "univl_beam_pool_step: history row t=%d of Tmax=%d", d->t, d->Tmax);
-    UNIVL_CHECK_ARG(d->lp && d->scores && d->done && d->length && d->tokens && d->src && d->hist_parents && d->hist_tokens && d->hist_scores &&
-                    d->ws, UNIVL_EINVAL, "univl_beam_pool_step: null pointer");
+    Step s;
+    if (const int rc = step_args("univl_beam_pool_step", d, &s)) return rc;
     UNIVL_CHECK_ARG(d->w && d->params && d->pool_key && d->pool_raw && d->pool_end_t && d->pool_beam && d->pool_finished && d->pool_count,
                     UNIVL_EINVAL, "univl_beam_pool_step: null pointer (w, params or a pool array)");
-    const int64_t rows = (int64_t)d->n_inst * d->n_bm;
-    const int64_t need = rows * UNIVL_BEAM_SLICES * d->n_bm * 8;
-    UNIVL_CHECK_ARG(d->ws_bytes >= need && aligned16(d->ws), UNIVL_EINVAL,
-                    "univl_beam_pool_step: workspace of %lld bytes, 16-byte aligned, needed (n_inst * n_bm * UNIVL_BEAM_SLICES * n_bm * 8); "
-                    "got %lld", (long long)need, (long long)d->ws_bytes);
+    s.scan.eos = d->eos;                                      // the scan leaves the end column out
+    s.scan.eos_dev = d->eos_dev;
     float* ws_val;
     int* ws_idx;
-    const Scan a{d->lp, (long)d->ld, d->V, d->first_step ? 1 : 0, d->scores, d->done, d->n_inst, d->n_bm, d->eos, d->eos_dev};
-    const int slices = scan_rows<true>(a, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
+    const int slices = scan_rows<true>(s.scan, d->n_bm, d->ws, &ws_val, &ws_idx, stream);
     UNIVL_LAUNCH_CHECK();
-    BeamOut o{d->scores, d->done, d->length, d->tokens, d->src, d->hist_parents, d->hist_tokens, d->hist_scores};
-    BeamPool p{d->w, d->params, d->pool_key, d->pool_raw, d->pool_end_t, d->pool_beam, d->pool_finished, d->pool_count};
     hipLaunchKernelGGL(beam_pool_select_kernel, dim3(d->n_inst), dim3(64), 0, stream, ws_val, ws_idx, d->lp, (long)d->ld, d->n_bm, d->V, slices,
-                       d->first_step ? 1 : 0, d->eos, d->eos_dev, d->t, d->Tmax, (long)d->t * rows, o, p);
+                       s.first_step, d->eos, d->eos_dev, d->t, d->Tmax, s.hist_row, s.o, pool_of(d));
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }
@@ -664,17 +636,15 @@ extern "C" int univl_beam_pool_finish(const UnivlBeamPoolStep* d, int32_t n_best
                                       uint8_t* hyp_finished, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_beam_pool_finish: null descriptor");
-    UNIVL_CHECK_ARG(d->n_inst >= 1 && d->n_bm >= 1 && d->n_bm <= UNIVL_BEAM_MAX && n_best >= 1 && n_best <= d->n_bm && d->Tmax >= 1 &&
-                    (int64_t)d->n_inst * d->n_bm <= INT_MAX / 2, UNIVL_EINVAL,
+    UNIVL_CHECK_ARG(beam_dims_ok(d) && n_best >= 1 && n_best <= d->n_bm && d->Tmax >= 1, UNIVL_EINVAL,
                     "univl_beam_pool_finish: n_inst=%d n_bm=%d n_best=%d Tmax=%d (1 <= n_best <= n_bm <= %d)", d->n_inst, d->n_bm, n_best, d->Tmax,
                     UNIVL_BEAM_MAX);
     UNIVL_CHECK_ARG(d->scores && d->done && d->length && d->hist_parents && d->hist_tokens && d->w && d->pool_key && d->pool_raw &&
                     d->pool_end_t && d->pool_beam && d->pool_finished && d->pool_count && hyp && hyp_raw && hyp_key && hyp_len && hyp_finished,
                     UNIVL_EINVAL, "univl_beam_pool_finish: null pointer");
-    BeamPool p{d->w, d->params, d->pool_key, d->pool_raw, d->pool_end_t, d->pool_beam, d->pool_finished, d->pool_count};
     PoolHyp h{hyp, hyp_raw, hyp_key, hyp_len, hyp_finished};
     hipLaunchKernelGGL(beam_pool_finish_kernel, dim3(d->n_inst), dim3(64), 0, stream, d->n_inst, d->n_bm, n_best, d->Tmax, d->eos, d->eos_dev,
-                       d->scores, d->done, d->length, d->hist_parents, d->hist_tokens, p, h);
+                       d->scores, d->done, d->length, d->hist_parents, d->hist_tokens, pool_of(d), h);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

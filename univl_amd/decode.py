@@ -38,6 +38,9 @@ Three layers, each naming what it owns:
                           (score.CaptionScorer builds on this layer alone);
   CachedDecoder           the row decoder: encoder K/V, the per-row cache, the (position, form) plans, the loop over the positions;
   CaptionBeamSearch       the beam state, its history and the beam step (sample.CaptionSampler: the sampling state and the sample step).
+                          _beam_step(t) is the one statement of the step's arguments: (op name, descriptor) of the plain, the group
+                          or the pooled step, for the tail of a position's plan and for the pooled finish.
+BeamResult and PoolBeamResult share _BeamHistory (the history rows and steps_run).
 """
 import math
 
@@ -65,7 +68,18 @@ def check_beam_groups(n_bm, beam_groups=1, diversity_penalty=0.0):
     return beam_groups, n_bm // beam_groups, pen
 
 
-class BeamResult:
+class _BeamHistory:
+    """What both results of CaptionBeamSearch.decode hold of the run: parents / step_tokens / step_scores [steps_run, n, n_bm]."""
+
+    def __init__(self, parents, step_tokens, step_scores):
+        self.parents, self.step_tokens, self.step_scores = parents, step_tokens, step_scores
+
+    @property
+    def steps_run(self):
+        return self.parents.shape[0]
+
+
+class BeamResult(_BeamHistory):
     """What CaptionBeamSearch.decode returns -- DEVICE tensors only:
       tokens  [n, n_best, Tmax] int32   the n_best best hypotheses of every instance, -1 padded
       scores  [n, n_best] fp32          their accumulated log-probabilities (non-increasing in k)
@@ -79,13 +93,9 @@ class BeamResult:
                                         their group."""
 
     def __init__(self, tokens, scores, lengths, parents, step_tokens, step_scores, groups=1):
+        super().__init__(parents, step_tokens, step_scores)
         self.tokens, self.scores, self.lengths = tokens, scores, lengths
-        self.parents, self.step_tokens, self.step_scores = parents, step_tokens, step_scores
         self.groups = groups
-
-    @property
-    def steps_run(self):
-        return self.parents.shape[0]
 
     def captions(self, eos, pad, eos_dev=None):
         """The reference's cut of every hypothesis at the first eos ("[SEP]"), then at the first pad ("[PAD]")
@@ -128,7 +138,7 @@ def check_length_penalty(length_penalty, early_stopping=False, beam_groups=1, be
     return float(length_penalty), int(bool(early_stopping))
 
 
-class PoolBeamResult:
+class PoolBeamResult(_BeamHistory):
     """What CaptionBeamSearch.decode returns in a session built with a length_penalty -- DEVICE tensors only:
       tokens      [n, n_best, Tmax] int32  the n_best best entries of every instance's pool, in pool order, -1 padded; a FINISHED
                                            hypothesis ends with the end token, as a plain search's does
@@ -143,12 +153,9 @@ class PoolBeamResult:
     groups = 1
 
     def __init__(self, tokens, scores, norm_scores, lengths, finished, positions, parents, step_tokens, step_scores):
+        super().__init__(parents, step_tokens, step_scores)
         self.tokens, self.scores, self.norm_scores, self.lengths, self.finished = tokens, scores, norm_scores, lengths, finished
-        self.positions, self.parents, self.step_tokens, self.step_scores = positions, parents, step_tokens, step_scores
-
-    @property
-    def steps_run(self):
-        return self.parents.shape[0]
+        self.positions = positions
 
     def captions(self, eos, pad, eos_dev=None):
         """BeamResult.captions on per-hypothesis lengths: (cap_tokens [n, n_best, Tmax] int32, cap_len [n, n_best] int32).  The rows
@@ -377,23 +384,19 @@ class CaptionBeamSearch(CachedDecoder):
             pl.add("univl_decode_constrain", ops.decode_constrain_desc(
                 self.head.logits, self.V, t, prefix_in=prefix[(t + 1) % 2], prefix_out=prefix[t % 2], src=self.src, last=self.ids,
                 done=self.done, done_stride=self.kp, eos_dev=self.eos_dev, params_dev=c.params_dev, suppress=c.suppress_dev))
-        if not beam:
-            return
+        if beam:
+            pl.add(*self._beam_step(t))
+
+    def _beam_step(self, t):
+        """The session's beam step at position t as (op name, descriptor): the pooled, the group or the plain one."""
+        lp = (self.head.logits, self.V, self.n_inst, self.n_bm)
         state = dict(scores=self.scores, done=self.done, length=self.length, tokens=self.ids, src=self.src, hist_parents=self.hist_par,
                      hist_tokens=self.hist_tok, hist_scores=self.hist_sc, ws=self.beam_ws, eos_dev=self.eos_dev)
         if self.pooled:
-            pl.add("univl_beam_pool_step", self._pool_desc(t))
-        elif self.G > 1:
-            pl.add("univl_beam_group_step", ops.beam_group_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, self.G, t,
-                                                                     diversity_dev=self.diversity_dev, **state))
-        else:
-            pl.add("univl_beam_step", ops.beam_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, t, **state))
-
-    def _pool_desc(self, t):
-        return ops.beam_pool_step_desc(self.head.logits, self.V, self.n_inst, self.n_bm, t, scores=self.scores, done=self.done,
-                                       length=self.length, tokens=self.ids, src=self.src, hist_parents=self.hist_par,
-                                       hist_tokens=self.hist_tok, hist_scores=self.hist_sc, ws=self.beam_ws, eos_dev=self.eos_dev,
-                                       w=self.pool_w, params=self.pool_params, **self.pool)
+            return "univl_beam_pool_step", ops.beam_pool_step_desc(*lp, t, w=self.pool_w, params=self.pool_params, **self.pool, **state)
+        if self.G > 1:
+            return "univl_beam_group_step", ops.beam_group_step_desc(*lp, self.G, t, diversity_dev=self.diversity_dev, **state)
+        return "univl_beam_step", ops.beam_step_desc(*lp, t, **state)
 
     # ------------------------------------------------------------------------------------------------- run
     def set_length_penalty(self, alpha, early_stopping=None):
@@ -463,7 +466,7 @@ class CaptionBeamSearch(CachedDecoder):
             self.hist_tok[ran:max_len] = self.hist_tok[ran - 1]
             self.hist_sc[ran:max_len] = self.hist_sc[ran - 1]
         if self.pooled:
-            tokens, raw, key, lens, fin = ops.beam_pool_finish(self._pool_desc(0), n_best)
+            tokens, raw, key, lens, fin = ops.beam_pool_finish(self._beam_step(0)[1], n_best)
             return PoolBeamResult(tokens[:m], raw[:m], key[:m], lens[:m], fin[:m], self.length[:m].clone(), self.hist_par[:max_len, :m].clone(),
                                   self.hist_tok[:max_len, :m].clone(), self.hist_sc[:max_len, :m].clone())
         # the walk-back on the (n * G, k') view: the history's parents are local to their group (G = 1: the tensors as they are)

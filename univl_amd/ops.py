@@ -362,28 +362,37 @@ def beam_ws(n_inst, n_bm, device):
     return torch.empty(n_inst * n_bm * _lib.BEAM_SLICES * n_bm * 2, dtype=torch.float32, device=device)
 
 
-def beam_step_desc(lp, V, n_inst, n_bm, t, *, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos=-1,
-                   eos_dev=None, first_step=None):
-    """lp: [n_inst * n_bm, ld] fp32 view (row stride ld >= V); state / outputs as in include/univl_hip.h: UnivlBeamStep.  first_step
-    defaults to t == 0.  Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
-    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev)
+def _beam_common(d, n_units, lp, V, n_inst, n_bm, t, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos,
+                 eos_dev, first_step):
+    """The part of a beam step descriptor that UnivlBeamStep, UnivlBeamGroupStep and UnivlBeamPoolStep share: checks the shapes and
+    dtypes of the common arguments (the builders' own, in their order) and fills d's common fields.  n_units: the entries of done /
+    length (n_inst, or n_inst * n_groups).  Shapes and dtypes are looked at before the device, so a wrong argument is an
+    AssertionError wherever the tensors live.  Returns d."""
     R = n_inst * n_bm
     assert lp.dtype == torch.float32 and lp.dim() == 2 and lp.stride(1) == 1 and lp.shape[0] >= R
     assert scores.dtype == torch.float32 and scores.numel() == R and scores.is_contiguous()
-    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == n_inst
-    assert length.dtype == torch.int32 and length.numel() == n_inst
+    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == n_units and done.is_contiguous()
+    assert length.dtype == torch.int32 and length.numel() == n_units and length.is_contiguous()
     assert tokens.dtype == torch.int64 and tokens.numel() == R and src.dtype == torch.int32 and src.numel() == R
     Tmax = hist_parents.shape[0]
     for h, dt_ in ((hist_parents, torch.int32), (hist_tokens, torch.int32), (hist_scores, torch.float32)):
         assert h.dtype == dt_ and h.is_contiguous() and h.shape[0] == Tmax and h.numel() == Tmax * R
     assert eos_dev is None or eos_dev.dtype == torch.int32
-    d = _lib.BeamStep()
+    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev)
     d.lp, d.ld, d.n_inst, d.n_bm, d.V = _p(lp), lp.stride(0), n_inst, n_bm, V
     d.first_step, d.eos, d.eos_dev, d.t, d.Tmax = int(t == 0 if first_step is None else first_step), int(eos), _p(eos_dev), t, Tmax
     d.scores, d.done, d.length, d.tokens, d.src = _p(scores), _p(done), _p(length), _p(tokens), _p(src)
     d.hist_parents, d.hist_tokens, d.hist_scores = _p(hist_parents), _p(hist_tokens), _p(hist_scores)
     d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
     return d
+
+
+def beam_step_desc(lp, V, n_inst, n_bm, t, *, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos=-1,
+                   eos_dev=None, first_step=None):
+    """lp: [n_inst * n_bm, ld] fp32 view (row stride ld >= V); state / outputs as in include/univl_hip.h: UnivlBeamStep.  first_step
+    defaults to t == 0.  Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
+    return _beam_common(_lib.BeamStep(), n_inst, lp, V, n_inst, n_bm, t, scores, done, length, tokens, src, hist_parents, hist_tokens,
+                        hist_scores, ws, eos, eos_dev, first_step)
 
 
 def beam_step(*a, **kw):
@@ -396,24 +405,10 @@ def beam_group_step_desc(lp, V, n_inst, n_bm, n_groups, t, *, scores, done, leng
     """beam_step_desc for n_groups groups of n_bm // n_groups beams (include/univl_hip.h: UnivlBeamGroupStep): done and length have
     n_inst * n_groups entries, one per (instance, group); diversity_dev: fp32 device word read instead of diversity.  ws: beam_ws(n_inst,
     n_bm).  Shapes and dtypes are checked here; the argument RANGE is the library's to refuse."""
-    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev, diversity_dev)
-    R, P = n_inst * n_bm, n_inst * n_groups
-    assert lp.dtype == torch.float32 and lp.dim() == 2 and lp.stride(1) == 1 and lp.shape[0] >= R
-    assert scores.dtype == torch.float32 and scores.numel() == R and scores.is_contiguous()
-    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == P and done.is_contiguous()
-    assert length.dtype == torch.int32 and length.numel() == P and length.is_contiguous()
-    assert tokens.dtype == torch.int64 and tokens.numel() == R and src.dtype == torch.int32 and src.numel() == R
-    Tmax = hist_parents.shape[0]
-    for h, dt_ in ((hist_parents, torch.int32), (hist_tokens, torch.int32), (hist_scores, torch.float32)):
-        assert h.dtype == dt_ and h.is_contiguous() and h.shape[0] == Tmax and h.numel() == Tmax * R
-    assert eos_dev is None or eos_dev.dtype == torch.int32
+    d = _beam_common(_lib.BeamGroupStep(), n_inst * n_groups, lp, V, n_inst, n_bm, t, scores, done, length, tokens, src, hist_parents,
+                     hist_tokens, hist_scores, ws, eos, eos_dev, first_step)
     assert diversity_dev is None or (diversity_dev.dtype == torch.float32 and diversity_dev.numel() == 1)
-    d = _lib.BeamGroupStep()
-    d.lp, d.ld, d.n_inst, d.n_bm, d.V = _p(lp), lp.stride(0), n_inst, n_bm, V
-    d.first_step, d.eos, d.eos_dev, d.t, d.Tmax = int(t == 0 if first_step is None else first_step), int(eos), _p(eos_dev), t, Tmax
-    d.scores, d.done, d.length, d.tokens, d.src = _p(scores), _p(done), _p(length), _p(tokens), _p(src)
-    d.hist_parents, d.hist_tokens, d.hist_scores = _p(hist_parents), _p(hist_tokens), _p(hist_scores)
-    d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
+    _require_gpu(diversity_dev)
     d.n_groups, d.diversity, d.diversity_dev = int(n_groups), float(diversity), _p(diversity_dev)
     return d
 
@@ -445,30 +440,15 @@ def beam_pool_step_desc(lp, V, n_inst, n_bm, t, *, scores, done, length, tokens,
     """beam_step_desc for the pooled search (include/univl_hip.h: UnivlBeamPoolStep).  w: fp32 [Tmax + 2] device table
     (length_weights); params: int32 [2] device words {early_stopping, Lmax}; pool_*: [n_inst, n_bm] (beam_pool).  Shapes and dtypes
     are checked here; the argument RANGE is the library's to refuse."""
-    _require_gpu(lp, scores, done, length, tokens, src, hist_parents, hist_tokens, hist_scores, ws, eos_dev, w, params, pool_key, pool_raw,
-                 pool_end_t, pool_beam, pool_finished, pool_count)
-    R = n_inst * n_bm
-    assert lp.dtype == torch.float32 and lp.dim() == 2 and lp.stride(1) == 1 and lp.shape[0] >= R
-    assert scores.dtype == torch.float32 and scores.numel() == R and scores.is_contiguous()
-    assert done.dtype in (torch.uint8, torch.bool) and done.numel() == n_inst
-    assert length.dtype == torch.int32 and length.numel() == n_inst
-    assert tokens.dtype == torch.int64 and tokens.numel() == R and src.dtype == torch.int32 and src.numel() == R
-    Tmax = hist_parents.shape[0]
-    for h, dt_ in ((hist_parents, torch.int32), (hist_tokens, torch.int32), (hist_scores, torch.float32)):
-        assert h.dtype == dt_ and h.is_contiguous() and h.shape[0] == Tmax and h.numel() == Tmax * R
-    assert eos_dev is None or eos_dev.dtype == torch.int32
-    assert w.dtype == torch.float32 and w.numel() == Tmax + 2 and w.is_contiguous()
+    d = _beam_common(_lib.BeamPoolStep(), n_inst, lp, V, n_inst, n_bm, t, scores, done, length, tokens, src, hist_parents, hist_tokens,
+                     hist_scores, ws, eos, eos_dev, first_step)
+    assert w.dtype == torch.float32 and w.numel() == d.Tmax + 2 and w.is_contiguous()
     assert params.dtype == torch.int32 and params.numel() == 2 and params.is_contiguous()
     for h, dt_ in ((pool_key, torch.float32), (pool_raw, torch.float32), (pool_end_t, torch.int32), (pool_beam, torch.int32),
                    (pool_finished, torch.uint8)):
-        assert h.dtype == dt_ and h.numel() == R and h.is_contiguous()
+        assert h.dtype == dt_ and h.numel() == n_inst * n_bm and h.is_contiguous()
     assert pool_count.dtype == torch.int32 and pool_count.numel() == n_inst and pool_count.is_contiguous()
-    d = _lib.BeamPoolStep()
-    d.lp, d.ld, d.n_inst, d.n_bm, d.V = _p(lp), lp.stride(0), n_inst, n_bm, V
-    d.first_step, d.eos, d.eos_dev, d.t, d.Tmax = int(t == 0 if first_step is None else first_step), int(eos), _p(eos_dev), t, Tmax
-    d.scores, d.done, d.length, d.tokens, d.src = _p(scores), _p(done), _p(length), _p(tokens), _p(src)
-    d.hist_parents, d.hist_tokens, d.hist_scores = _p(hist_parents), _p(hist_tokens), _p(hist_scores)
-    d.ws, d.ws_bytes = _p(ws), ws.numel() * ws.element_size()
+    _require_gpu(w, params, pool_key, pool_raw, pool_end_t, pool_beam, pool_finished, pool_count)
     d.w, d.params = _p(w), _p(params)
     d.pool_key, d.pool_raw, d.pool_end_t, d.pool_beam = _p(pool_key), _p(pool_raw), _p(pool_end_t), _p(pool_beam)
     d.pool_finished, d.pool_count = _p(pool_finished), _p(pool_count)
