@@ -796,6 +796,65 @@ typedef struct UnivlSimTopk {
 } UnivlSimTopk;
 int univl_sim_topk(const UnivlSimTopk* d, hipStream_t stream);
 int64_t univl_sim_topk_workspace(int32_t Nq, int32_t Ng, int32_t k, int32_t slices);
+/* ---------------------------------------------------------------------------------------- query-bank normalised search
+ * Search-time normalisation against hubness (QB-Norm's dynamic inverted softmax, dual-softmax inference): a gallery row that a BANK of
+ * other queries already claims strongly is marked down.  With s(a, g) the score of univl_sim_topk (its SCORE CONTRACT, the same
+ * accumulator chain), a bank of Nb >= 1 rows b and a finite beta > 0:
+ *   column term       c_j = m_j + log(sum_b exp(beta * (s(b, j) - m_j))) / beta,   m_j = max_b s(b, j)      (never overflows)
+ *   normalised score  s'(i, j) = gate_i ? s(i, j) - c_j : s(i, j)                  (ONE fp32 subtraction; ranking by s' is ranking
+ *                     by exp(beta s(i, j)) / sum_b exp(beta s(b, j)))
+ *   hub set           hub[j] = 1 iff j is among the hub_k best gallery rows of some bank row (raw score, TIE RULE of univl_sim_topk)
+ *   dynamic gate      gate_i = hub[raw top-1 of query i]                            (static: every gate is 1)
+ * univl_sim_colstat computes c[Ng] without the [Nb, Ng] matrix.  Two launches, no host read, capturable:
+ *   scan   grid (gallery tiles of 32 rows, bank slices), 512 threads: univl_sim_topk's scan with the roles swapped -- the gallery
+ *          tile stays in LDS, bank tiles of 128 rows are streamed into the MFMA operands, and instead of a ranked list every gallery
+ *          row keeps a running (max, sum of exp) pair: one partial per bank tile, reduced over its 128 rows in a fixed tree, folded
+ *          into the running pair in ascending tile order; a slice's pair goes to the workspace;
+ *   merge  one thread per gallery row folds the slices' pairs in ascending order and writes c.
+ * PURITY: the bits of c_j depend on g_j, the bank (its rows and their order) and beta, and on nothing else -- not on Ng, the row's
+ * place in the gallery or a tile, or deterministic mode; there are no float atomics.  The slice rule is a function of Nb alone:
+ * T = ceil(Nb / 128) bank tiles, ceil(T / UNIVL_COLSTAT_SLICES) tiles per slice, S = ceil(T / that) slices.  A gallery normalised
+ * in pieces is therefore the gallery normalised whole, element for element, and s' is a pure function of (q_i, g_j, bank, beta,
+ * gate_i): the tie rule, eq and the exact merging of gallery pieces hold for the normalised search as they do for the plain one.
+ * Range: H == 768, Nb >= 1, Ng >= 1, beta finite and > 0, ldb / ldg >= H, rows 16-byte aligned (UNIVL_EALIGN), workspace of
+ * univl_sim_colstat_workspace(Nb, Ng) = 8 * S * Ng bytes (host only; < 0 for arguments univl_sim_colstat would refuse). */
+#define UNIVL_COLSTAT_SLICES 32
+typedef struct UnivlSimColstat {
+    const float* bank; int64_t ldb;  /* [Nb, ldb] fp32 bank rows                                                                  */
+    const float* g; int64_t ldg;     /* [Ng, ldg] fp32 gallery                                                                    */
+    int32_t Nb, Ng, H;               /* H must be 768                                                                             */
+    float beta;                      /* finite, > 0                                                                               */
+    float* c;                        /* [Ng] written                                                                              */
+    void* ws; int64_t ws_bytes;      /* 16-byte aligned scratch, univl_sim_colstat_workspace                                      */
+} UnivlSimColstat;
+int univl_sim_colstat_sizeof(void);
+int univl_sim_colstat(const UnivlSimColstat* d, hipStream_t stream);
+int64_t univl_sim_colstat_workspace(int32_t Nb, int32_t Ng);
+/* univl_sim_topk on s': UnivlSimTopk's fields with UnivlSimTopk's meaning, range, workspace and refusals, then the column term and the
+ * gates.  Everything univl_sim_topk states about s holds for s': the sorted lists with the tie rule, the -1 / -inf padding, gt / eq
+ * against target, whose score is s(i, target[i]) - c[target[i]] by the same subtraction, k == 0, the bit-exact merging of gallery
+ * pieces (each piece with its piece of col_bias).  The same scan kernel (its NORM instantiation; univl_sim_topk is the other one):
+ * the bias is read once per tile and lane where the scores leave the LDS score buffer.  A NULL col_bias is UNIVL_EINVAL. */
+typedef struct UnivlSimTopkNorm {
+    const float* q; int64_t ldq;
+    const float* g; int64_t ldg;
+    int32_t Nq, Ng, H, k;
+    int32_t slices;
+    int32_t reserved;
+    int32_t* idx; float* score;
+    const int32_t* target;
+    int32_t* gt; int32_t* eq;
+    void* ws; int64_t ws_bytes;      /* univl_sim_topk_workspace(Nq, Ng, k, slices)                                               */
+    const float* col_bias;           /* ... then [Ng] fp32: c_j (any finite values: the kernel subtracts what it is given)        */
+    const int32_t* row_gate;         /* optional [Nq] int32: 0 leaves the query's scores untouched; NULL: every gate is 1         */
+} UnivlSimTopkNorm;
+int univl_sim_topk_norm_sizeof(void);
+int univl_sim_topk_norm(const UnivlSimTopkNorm* d, hipStream_t stream);
+/* hub[idx[e]] = 1 for every e < n with 0 <= idx[e] < Ng (plain stores of 1; duplicates and the -1 padding of univl_sim_topk are
+ * harmless).  hub is NOT cleared: the caller zeroes it, so that several lists may be scattered into one set. */
+int univl_hub_flags(const int32_t* idx, int64_t n, int32_t Ng, int32_t* hub, hipStream_t stream);
+/* gate[i] = hub[top1[i * ld]] != 0 for i < Nq (0 for an index outside [0, Ng)): top1 is the first column of univl_sim_topk's idx. */
+int univl_hub_gate(const int32_t* top1, int64_t ld, int32_t Nq, const int32_t* hub, int32_t Ng, int32_t* gate, hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

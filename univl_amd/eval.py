@@ -62,20 +62,32 @@ def eval_retrieval(model, batches, device="cuda"):
 
 
 @torch.no_grad()
-def eval_retrieval_streamed(model, text_batches, video_batches, targets, device="cuda", capacity=1024):
+def eval_retrieval_streamed(model, text_batches, video_batches, targets, device="cuda", capacity=1024, bank_batches=None, beta=20.0,
+                            hub_k=1, dynamic=True):
     """Retrieval metrics without the N_t x N_v matrix and without a paired test set.  video_batches: iterable of (video, video_mask);
     text_batches: iterable of (input_ids, input_mask, segment_ids), the loader's order (main_task_retrieval.py:396); targets: for
     every text row, in order, the gallery row (= position among all videos added) that is its ground truth -- several texts may name
     one video, and the number of texts need not be the number of videos.  The videos go into a retrieval.VideoIndex, every text batch
     is searched for its two rank counts only (univl_sim_topk with k = 0), and R@1 / R@5 / R@10 / MR come from the counts through
-    metrics.compute_metrics.  Joint-head similarity only (what VideoIndex holds).  Returns (metrics dict, (gt, eq) host arrays)."""
-    from .retrieval import VideoIndex
+    metrics.compute_metrics.  Joint-head similarity only (what VideoIndex holds).  Returns (metrics dict, (gt, eq) host arrays).
+    bank_batches: an iterable of text batches like text_batches (training captions, say); they fill a retrieval.QueryBank(beta, hub_k,
+    dynamic) and the counts, hence the metrics, are those of the query-bank normalised score.  None: the raw score, as ever."""
+    from .retrieval import QueryBank, VideoIndex, check_bank_args
+    if bank_batches is not None:
+        check_bank_args(beta, hub_k)
     was_training = model.training
     model.eval()
     try:
         index = VideoIndex(model, capacity=capacity)
         for video, video_mask in video_batches:
             index.add(video.to(device), video_mask.to(device))
+        bank = None
+        if bank_batches is not None:
+            bank = QueryBank(index, beta=beta, hub_k=hub_k, dynamic=dynamic)
+            for batch in bank_batches:
+                input_ids, input_mask, segment_ids = [t.to(device) for t in batch[:3]]
+                bank.add(input_ids, segment_ids, input_mask)
+            bank.fit()
         targets = torch.as_tensor(targets).reshape(-1).to(device=device, dtype=torch.int32)
         if targets.numel() and (int(targets.min()) < 0 or int(targets.max()) >= len(index)):
             raise ValueError("eval_retrieval_streamed: targets must lie in [0, %d)" % len(index))
@@ -85,7 +97,7 @@ def eval_retrieval_streamed(model, text_batches, video_batches, targets, device=
             n = input_ids.numel() // input_ids.shape[-1]
             if row + n > targets.numel():
                 raise ValueError("eval_retrieval_streamed: more text rows than targets (%d)" % targets.numel())
-            gt, eq = index.search(input_ids, segment_ids, input_mask, k=0, targets=targets[row:row + n])
+            gt, eq = index.search(input_ids, segment_ids, input_mask, k=0, targets=targets[row:row + n], bank=bank)
             gts.append(gt)
             eqs.append(eq)
             row += n

@@ -700,13 +700,17 @@ def sim_topk(q, g, k, *, target=None, slices=0):
     [Nq] int32 gallery rows; slices: 0 = the library chooses.  Returns (scores [Nq, k] fp32 descending, indices [Nq, k] int32; equal
     scores by lower index first, -inf / -1 past the gallery's end), followed by (gt, eq) int32 [Nq] -- the rank counts against
     target -- when target is given.  k = 0: only (gt, eq)."""
+    return _sim_topk(_lib.SimTopk(), "sim_topk", q, g, k, target, slices)
+
+
+def _sim_topk(d, what, q, g, k, target, slices):
+    """sim_topk and sim_topk_norm: d is the descriptor (SimTopk's fields; the caller has set the ones past them), what the entry point."""
     _require_gpu(q, g, target)
     assert q.dtype == torch.float32 and g.dtype == torch.float32 and q.dim() == 2 and g.dim() == 2
-    d = _lib.SimTopk()
     d.q, d.ldq, d.g, d.ldg = _p(q), _ld(q), _p(g), _ld(g)
     d.Nq, d.Ng, d.H, d.k, d.slices = q.shape[0], g.shape[0], q.shape[1], int(k), int(slices)
     if g.shape[1] != q.shape[1]:
-        raise RuntimeError("sim_topk: q is %d wide, g %d" % (q.shape[1], g.shape[1]))
+        raise RuntimeError("%s: q is %d wide, g %d" % (what, q.shape[1], g.shape[1]))
     dev = q.device
     need = _lib.lib().univl_sim_topk_workspace(d.Nq, d.Ng, d.k, d.slices)
     ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
@@ -721,10 +725,64 @@ def sim_topk(q, g, k, *, target=None, slices=0):
         gt = torch.empty(d.Nq, dtype=torch.int32, device=dev)
         eq = torch.empty(d.Nq, dtype=torch.int32, device=dev)
         d.target, d.gt, d.eq = _p(target), _p(gt), _p(eq)
-    _lib.check(_lib.lib().univl_sim_topk(_BYREF(d), _stream()), "sim_topk")     # refuses what the workspace query refused, with its message
+    _lib.check(getattr(_lib.lib(), "univl_" + what)(_BYREF(d), _stream()), what)     # refuses what the workspace query refused, with its message
     if d.k == 0:
         return gt, eq
     return (score, idx) if target is None else (score, idx, gt, eq)
+
+
+def sim_topk_norm(q, g, k, col_bias, *, row_gate=None, target=None, slices=0):
+    """sim_topk on the query-bank normalised score s'(i, j) = s(i, j) - col_bias[j] where row_gate[i] != 0 (everywhere when row_gate
+    is None), s(i, j) untouched where it is 0 (include/univl_hip.h: univl_sim_topk_norm).  col_bias: [Ng] fp32 (sim_colstat), row_gate:
+    optional [Nq] int32 (hub_gate).  Arguments and results otherwise as sim_topk's; the scores returned are s'."""
+    _require_gpu(col_bias, row_gate)
+    assert col_bias.dtype == torch.float32 and col_bias.numel() == g.shape[0] and col_bias.is_contiguous()
+    assert row_gate is None or (row_gate.dtype == torch.int32 and row_gate.numel() == q.shape[0] and row_gate.is_contiguous())
+    d = _lib.SimTopkNorm()
+    d.col_bias, d.row_gate = _p(col_bias), _p(row_gate)
+    return _sim_topk(d, "sim_topk_norm", q, g, k, target, slices)
+
+
+def sim_colstat(bank, g, beta=20.0, *, out=None):
+    """The column term of query-bank normalisation, c[j] = log-sum-exp over the bank rows b of beta * s(b, j), divided by beta, without
+    the [Nb, Ng] matrix (include/univl_hip.h: univl_sim_colstat).  bank: [Nb, 768], g: [Ng, 768] fp32 row-major views as sim_topk's;
+    beta: finite, > 0; out: optional [Ng] fp32 to write.  Returns c [Ng] fp32."""
+    _require_gpu(bank, g, out)
+    assert bank.dtype == torch.float32 and g.dtype == torch.float32 and bank.dim() == 2 and g.dim() == 2
+    if g.shape[1] != bank.shape[1]:
+        raise RuntimeError("sim_colstat: bank is %d wide, g %d" % (bank.shape[1], g.shape[1]))
+    d = _lib.SimColstat()
+    d.bank, d.ldb, d.g, d.ldg = _p(bank), _ld(bank), _p(g), _ld(g)
+    d.Nb, d.Ng, d.H, d.beta = bank.shape[0], g.shape[0], bank.shape[1], float(beta)
+    c = torch.empty(d.Ng, dtype=torch.float32, device=g.device) if out is None else out
+    assert c.dtype == torch.float32 and c.numel() == d.Ng and c.is_contiguous()
+    need = _lib.lib().univl_sim_colstat_workspace(d.Nb, d.Ng)
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=g.device)
+    d.c, d.ws, d.ws_bytes = _p(c), _p(ws), ws.numel()
+    _lib.check(_lib.lib().univl_sim_colstat(_BYREF(d), _stream()), "sim_colstat")
+    return c
+
+
+def hub_flags(idx, Ng, *, out=None):
+    """hub[j] = 1 for every gallery row j that idx names (int32, any shape: the bank rows' best lists from sim_topk; -1 is skipped).
+    out: an [Ng] int32 set to add to; default a new one, zeroed.  Returns hub [Ng] int32."""
+    _require_gpu(idx, out)
+    assert idx.dtype == torch.int32 and idx.is_contiguous()
+    hub = torch.zeros(int(Ng), dtype=torch.int32, device=idx.device) if out is None else out
+    assert hub.dtype == torch.int32 and hub.numel() == int(Ng) and hub.is_contiguous()
+    _lib.check(_lib.lib().univl_hub_flags(_p(idx), idx.numel(), int(Ng), _p(hub), _stream()), "hub_flags")
+    return hub
+
+
+def hub_gate(top1, hub):
+    """gate[i] = 1 where hub[top1[i]] is set.  top1: [Nq] int32, or sim_topk's [Nq, k] indices, whose first column is taken in place;
+    hub: [Ng] int32 (hub_flags).  Returns gate [Nq] int32, the row_gate of sim_topk_norm."""
+    _require_gpu(top1, hub)
+    assert top1.dtype == torch.int32 and hub.dtype == torch.int32 and hub.is_contiguous() and top1.dim() in (1, 2)
+    ld = top1.stride(0) if top1.shape[0] > 1 else 1
+    gate = torch.empty(top1.shape[0], dtype=torch.int32, device=top1.device)
+    _lib.check(_lib.lib().univl_hub_gate(_p(top1), ld, top1.shape[0], _p(hub), hub.numel(), _p(gate), _stream()), "hub_gate")
+    return gate
 
 
 class AdamTables:

@@ -7,7 +7,15 @@ when full; a query is pooled the same way get_similarity_logits pools it (modeli
 with video vectors through search_vectors.
 
 Stage-two / train_sim_after_cross models score a pair through the cross encoder; search(..., rerank=True) runs only the k joint-head
-candidates of every query through it (queries x k pairs instead of queries x gallery) and re-sorts each row by the cross score."""
+candidates of every query through it (queries x k pairs instead of queries x gallery) and re-sorts each row by the cross score.
+
+QueryBank is the search-time remedy against hubness (query-bank normalisation, the dynamic inverted softmax): a bank of other texts
+-- training captions, say -- states how strongly every video is already claimed, and search(..., bank=) ranks by the score minus that
+column term (include/univl_hip.h: univl_sim_colstat, univl_sim_topk_norm).  No retraining, and no [bank, gallery] matrix."""
+import ctypes
+import math
+import numbers
+
 import torch
 
 from . import _lib, ops
@@ -104,32 +112,42 @@ class VideoIndex:
         return q, so, am
 
     @torch.no_grad()
-    def search(self, input_ids, token_type_ids, attention_mask, k=10, targets=None, rerank=False, chunk_rows=5):
+    def search(self, input_ids, token_type_ids, attention_mask, k=10, targets=None, rerank=False, chunk_rows=5, bank=None):
         """The k best videos for every text.  Returns (scores [Nq, k] fp32, indices [Nq, k] int32) on the device, rows sorted by
         descending score, equal scores by lower row id first, -inf / -1 past the end of a gallery smaller than k.  With targets
         ([Nq] gallery rows) it also returns (gt, eq), the rank counts of every query's target (k = 0: only those).
         rerank=True (keep_frames=True, a model with a cross encoder, k <= len(index)): the k joint-head candidates are scored by
-        the cross encoder, chunk_rows queries at a time; returns the cross scores and the re-ordered row ids."""
+        the cross encoder, chunk_rows queries at a time; returns the cross scores and the re-ordered row ids.
+        bank: a fitted QueryBank of this index; scores, order and rank counts are then those of the normalised score (QueryBank),
+        and rerank=True takes its candidates from the normalised search.  A bank whose fit() is stale is a ValueError."""
+        if bank is not None:
+            bank.check_fitted(self)
         q, so, am = self.pool_text(input_ids, token_type_ids, attention_mask)
         if rerank:
             if targets is not None:
                 raise ValueError("VideoIndex.search: rank counts are taken from the joint head; call without rerank for them")
-            return self._rerank(q, so, am, int(k), int(chunk_rows))
-        return self.search_vectors(q, k, targets)
+            return self._rerank(q, so, am, int(k), int(chunk_rows), bank)
+        return self.search_vectors(q, k, targets, bank)
 
     @torch.no_grad()
-    def search_vectors(self, q, k, targets=None):
+    def search_vectors(self, q, k, targets=None, bank=None):
         """search() for pooled query vectors the caller already holds ([Nq, 768] fp32 on the index's device)."""
         if self._n == 0:
             raise ValueError("VideoIndex: the index is empty")
+        if bank is not None:
+            bank.check_fitted(self)
         q = q.reshape(-1, H).to(torch.float32)
         if q.stride(1) != 1 or q.stride(0) % 4 or q.data_ptr() % 16:
             q = q.contiguous()
         if targets is not None:
             targets = torch.as_tensor(targets).reshape(-1).to(device=q.device, dtype=torch.int32).contiguous()
-        return ops.sim_topk(q, self.vectors, int(k), target=targets)
+        if bank is None:
+            return ops.sim_topk(q, self.vectors, int(k), target=targets)
+        # plain top-1 -> gate -> normalised scan; a static bank has no gates and is the last launch pair alone
+        gate = ops.hub_gate(ops.sim_topk(q, self.vectors, 1)[1], bank.hub) if bank.dynamic else None
+        return ops.sim_topk_norm(q, self.vectors, int(k), bank.c, row_gate=gate, target=targets)
 
-    def _rerank(self, q, so, am, K, chunk_rows):
+    def _rerank(self, q, so, am, K, chunk_rows, bank=None):
         from .steps import EvalSession, PoolerSim
         model = self.model
         if model.cross is None:
@@ -138,7 +156,7 @@ class VideoIndex:
             raise ValueError("VideoIndex.search(rerank=True) needs an index built with keep_frames=True")
         if not 1 <= K <= min(self._n, _lib.TOPK_MAX):
             raise ValueError("VideoIndex.search(rerank=True): k=%d, need 1 <= k <= min(len(index), %d)" % (K, _lib.TOPK_MAX))
-        _, idx = ops.sim_topk(q, self.vectors, K)
+        _, idx = self.search_vectors(q, K, None, bank)
         Nq, W = so.shape[0], so.shape[1]
         F = self._frames.shape[1]
         cross = torch.empty(Nq, K, device=q.device, dtype=torch.float32)
@@ -158,3 +176,126 @@ class VideoIndex:
         ids, perm = torch.sort(idx.long(), dim=1, stable=True)
         sc, perm2 = torch.sort(cross.gather(1, perm), dim=1, descending=True, stable=True)
         return sc, ids.gather(1, perm2).to(torch.int32)
+
+
+class QueryBank:
+    """A bank of pooled text vectors that normalises the searches of ONE VideoIndex.  With s the index's raw score and b the bank rows,
+      c[j]     = log(sum_b exp(beta * s(b, j))) / beta           the column term of gallery row j (ops.sim_colstat)
+      hub[j]   = 1 iff j is among the hub_k best rows of some bank row (raw score, ties by lower row id first)
+      s'(i, j) = s(i, j) - c[j]  where gate_i is set,  s(i, j)  otherwise
+    and gate_i = hub[raw top-1 of query i] (dynamic=True: only queries whose best video is one the bank already claims are
+    normalised) or 1 for every query (dynamic=False).  Ranking by s' is ranking by exp(beta s(i, j)) / sum_b exp(beta s(b, j)).
+    Fill it with add() / add_vectors(), call fit(), pass it as search(..., bank=).  c[j] depends on gallery row j and the bank alone,
+    so fit() after the index grew computes the new rows only and equals a fresh fit() bit for bit; more bank rows recompute all."""
+
+    def __init__(self, index, beta=20.0, hub_k=1, dynamic=True):
+        check_bank_args(beta, hub_k)
+        self.index, self.beta, self.hub_k, self.dynamic = index, float(beta), int(hub_k), bool(dynamic)
+        self._buf, self._n = None, 0
+        self._invalidate()
+
+    def _invalidate(self):
+        self._covered = 0                     # index rows that c, the lists and hub cover
+        self._c = self._top_score = self._top_idx = self._hub = None
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def vectors(self):
+        """[len(bank), 768] fp32 view of the bank rows."""
+        return self._buf[:self._n]
+
+    @property
+    def c(self):
+        """[len(index)] fp32 column terms, as of the last fit() (ValueError before the first, or after more bank rows)."""
+        self._need_fit()
+        return self._c[:self._covered]
+
+    @property
+    def hub(self):
+        """[len(index)] int32 hub flags, as of the last fit() (ValueError before the first, or after more bank rows)."""
+        self._need_fit()
+        return self._hub
+
+    def _need_fit(self):
+        if self._c is None:
+            raise ValueError("QueryBank: nothing is fitted yet (or the bank changed since); call bank.fit()")
+
+    @torch.no_grad()
+    def add(self, input_ids, token_type_ids, attention_mask):
+        """Pools the texts as VideoIndex.pool_text does and appends them.  Returns the number of bank rows."""
+        return self.add_vectors(self.index.pool_text(input_ids, token_type_ids, attention_mask)[0])
+
+    @torch.no_grad()
+    def add_vectors(self, q):
+        """Appends pooled vectors the caller already holds ([b, 768] on the index's device).  Invalidates fit()."""
+        dev = torch.device(self.index._device())
+        if q.device.type != dev.type or (dev.index is not None and q.device.index != dev.index):
+            raise ValueError("QueryBank.add_vectors: vectors on %s, the index is on %s" % (q.device, dev))
+        q = q.reshape(-1, H)
+        b = q.shape[0]
+        if b == 0:
+            return self._n
+        cap = 0 if self._buf is None else self._buf.shape[0]
+        if self._n + b > cap:
+            new = torch.empty(max(2 * cap, self._n + b, 64), H, device=q.device, dtype=torch.float32)
+            if self._n:
+                new[:self._n].copy_(self._buf[:self._n])
+            self._buf = new
+        self._buf[self._n:self._n + b].copy_(q)
+        self._n += b
+        self._invalidate()
+        return self._n
+
+    @torch.no_grad()
+    def fit(self):
+        """Column terms and hub flags for the index rows not covered yet (all of them after the bank changed).  Returns self."""
+        if self._n == 0:
+            raise ValueError("QueryBank.fit: the bank is empty; add() texts first")
+        n = len(self.index)
+        if n == 0:
+            raise ValueError("QueryBank.fit: the index is empty")
+        lo = self._covered
+        if lo == n:
+            return self
+        bank, piece = self.vectors, self.index.vectors[lo:n]
+        if self._c is None or self._c.numel() < n:
+            c = torch.empty(max(n, self.index._cap), device=bank.device, dtype=torch.float32)
+            if lo:
+                c[:lo].copy_(self._c[:lo])
+            self._c = c
+        ops.sim_colstat(bank, piece, self.beta, out=self._c[lo:n])
+        # every bank row's hub_k best (score, row): the piece's list, merged exactly with the one kept so far -- rows ascending, then
+        # a stable sort by descending score is the kernel's own order
+        score, idx = ops.sim_topk(bank, piece, self.hub_k)
+        idx = torch.where(idx < 0, torch.full_like(idx, _NO_ROW), idx + lo)
+        if lo:
+            idx, perm = torch.sort(torch.cat([self._top_idx, idx], 1), dim=1, stable=True)
+            score, perm2 = torch.sort(torch.cat([self._top_score, score], 1).gather(1, perm), dim=1, descending=True, stable=True)
+            score, idx = score[:, :self.hub_k].contiguous(), idx.gather(1, perm2)[:, :self.hub_k].contiguous()
+        self._top_score, self._top_idx = score, idx
+        self._hub = ops.hub_flags(idx, n)                 # _NO_ROW lies outside every gallery: skipped
+        self._covered = n
+        return self
+
+    def check_fitted(self, index):
+        """ValueError unless fit() covers `index` as it stands."""
+        if index is not self.index:
+            raise ValueError("QueryBank: this bank belongs to another VideoIndex")
+        if self._n == 0 or self._covered != len(index):
+            raise ValueError("QueryBank: the bank or the index changed since the last fit (%d of %d index rows covered); call bank.fit()"
+                             % (self._covered, len(index)))
+
+
+_NO_ROW = 2 ** 31 - 1      # an empty slot of a best list (the -1 of ops.sim_topk), made to sort last
+
+
+def check_bank_args(beta, hub_k):
+    """The ValueErrors of QueryBank(beta=, hub_k=), before any device work."""
+    ok = isinstance(beta, numbers.Real) and not isinstance(beta, bool)
+    b32 = ctypes.c_float(beta).value if ok else 0.0           # beta travels as fp32
+    if not (math.isfinite(b32) and b32 > 0):
+        raise ValueError("QueryBank: beta=%r, need a finite fp32 number > 0" % (beta,))
+    if isinstance(hub_k, bool) or not isinstance(hub_k, numbers.Integral) or not 1 <= hub_k <= _lib.TOPK_MAX:
+        raise ValueError("QueryBank: hub_k=%r, need an integer in [1, %d]" % (hub_k, _lib.TOPK_MAX))
