@@ -230,7 +230,12 @@ typedef struct UnivlAttention {
     void* dk; int64_t lddk;
     void* dv; int64_t lddv;
     /* optional batch strides (elements) of k and v: 0 = Sk*ld (densely packed rows).  A key/value cache of capacity
-     * Tmax >= Sk per sequence (incremental caption decoding, main_task_caption.py:434-470) passes Tmax*ld. */
+     * Tmax >= Sk per sequence (incremental caption decoding, main_task_caption.py:434-470) passes Tmax*ld.  Rows >= Sk of a
+     * sequence's slots are never read.  The strides cover READS only: univl_attention_bwd reads k and v at bsk / bsv and
+     * writes dk and dv densely, batch row b at row b*Sk of [B*Sk, lddk] / [B*Sk, lddv] -- the gradient of the prefix, not a
+     * cache-shaped buffer (tests/test_attention_edges_gpu.py pins both).
+     * Bias semantics at the edges: a key that is masked AND (causal) ahead of the query carries ONE -10000, so a fully
+     * masked batch row is softmax(raw scores) over all Sk real keys, causal or not; causal is key > q for any Sq, Sk. */
     int64_t bsk, bsv;
     void* out_lo;             /* fwd, optional, bf16: lo half of the output pair, [B*Sq, ldo] (UnivlGemm.A_lo of the output projection) */
 } UnivlAttention;

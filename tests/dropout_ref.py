@@ -93,10 +93,14 @@ def attn_scale(seed, offset, B, H, Sq, Sk, p):
 
 
 # ----------------------------------------------------------------------------------------- fp64 references
-def attention_ref(q, k, v, add_mask, nh, scale=None):
+def attention_ref(q, k, v, add_mask, nh, scale=None, parts=False, rnd=None):
     """softmax(Q K^T / sqrt(d) + add_mask) * scale @ V, heads merged.  q [B,Sq,nh*d], k / v [B,Sk,nh*d], add_mask broadcastable to
     [B,nh,Sq,Sk], scale [B,nh,Sq,Sk] (mask * 1/(1-p)) or None.  Written out on its own: at scale=None it must equal the oracle's
-    attention_core (tests/test_dropout_ref_cpu.py)."""
+    attention_core (tests/test_dropout_ref_cpu.py).
+
+    The arithmetic runs in the operands' dtype.  rnd: applied to the (scaled) probabilities before they meet V -- the rounding of a
+    kernel's P operand (tests/attention_ref.py's precision model); None: none.  parts=True: -> (out, lse [B,nh,Sq], probs [B,nh,Sq,Sk]
+    before scale and rnd) with lse = max + log(sum exp(. - max)), the row log-sum-exp of the biased scores."""
     B, Sq, HD = q.shape
     Sk = k.shape[1]
     d = HD // nh
@@ -104,12 +108,18 @@ def attention_ref(q, k, v, add_mask, nh, scale=None):
     kl = k.reshape(B, Sk, nh, d).permute(0, 2, 1, 3)
     vl = v.reshape(B, Sk, nh, d).permute(0, 2, 1, 3)
     s = ql @ kl.transpose(-1, -2) / math.sqrt(d) + add_mask
-    s = s - s.max(-1, keepdim=True).values
+    mx = s.max(-1, keepdim=True).values
+    s = s - mx
     e = torch.exp(s)
-    probs = e / e.sum(-1, keepdim=True)
-    if scale is not None:
-        probs = probs * scale
-    return (probs @ vl).permute(0, 2, 1, 3).reshape(B, Sq, HD)
+    den = e.sum(-1, keepdim=True)
+    probs = e / den
+    pv = probs if scale is None else probs * scale
+    if rnd is not None:
+        pv = rnd(pv)
+    out = (pv @ vl).permute(0, 2, 1, 3).reshape(B, Sq, HD)
+    if parts:
+        return out, (mx + torch.log(den)).squeeze(-1), probs
+    return out
 
 
 def layernorm_ref(x, gamma, beta, residual=None, rowpos=None, scale_pre=None, scale_post=None, eps=1e-12):

@@ -921,7 +921,8 @@ def test_attention_fwd_bwd(dtype, B, Sq, Sk, causal):
     assert rel_err(dkv.float()[:, H * D:].reshape(B, Sk, -1), v.grad) < t
 
 
-@pytest.mark.parametrize("B,S,p_drop,masked", [(4, 48, 0.1, False), (4, 48, 0.0, True), (3, 20, 0.1, True), (2, 64, 0.0, False), (5, 33, 0.1, True)])
+@pytest.mark.parametrize("B,S,p_drop,masked", [(4, 48, 0.1, False), (4, 48, 0.0, True), (3, 20, 0.1, True), (2, 64, 0.0, False), (5, 33, 0.1, True),
+                                               (4, 1, 0.1, True), (3, 17, 0.0, True), (2, 63, 0.1, True)])
 def test_attention_bwd_with_the_output_dgrad_inside_equals_the_two_launches(B, S, p_drop, masked):
     """univl_attention_bwd_fused (round 5): every workgroup of the attention backward first multiplies the 64 x 64 block of
     dctx = dY . W_o that belongs to its (batch row, head) and works on it from LDS.  Same chunk order per output element, same bf16
@@ -984,7 +985,8 @@ def test_attention_bwd_with_the_output_dgrad_inside_equals_the_two_launches(B, S
 
 
 @pytest.mark.parametrize("B,S,p_drop,masked", [(4, 48, 0.1, False), (4, 48, 0.0, True), (3, 20, 0.1, True), (2, 64, 0.0, False), (5, 33, 0.1, True),
-                                               (4, 128, 0.1, False), (4, 96, 0.0, True), (3, 100, 0.1, True), (2, 65, 0.0, True), (6, 112, 0.1, False)])
+                                               (4, 128, 0.1, False), (4, 96, 0.0, True), (3, 100, 0.1, True), (2, 65, 0.0, True), (6, 112, 0.1, False),
+                                               (4, 1, 0.1, True), (2, 63, 0.0, True), (3, 65, 0.1, True), (2, 127, 0.1, True)])
 def test_attention_fwd_with_the_qkv_projection_inside_equals_the_two_launches(B, S, p_drop, masked):
     """univl_attention_fwd_fused (round 5): the workgroup of a (batch row, head) multiplies its 64 x 192 block of q | k | v, stores it
     and attends on it from LDS.  The qkv buffer, the attention output and the log-sum-exp are BIT-IDENTICAL to univl_gemm +
