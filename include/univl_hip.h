@@ -860,6 +860,53 @@ int univl_sim_topk_norm(const UnivlSimTopkNorm* d, hipStream_t stream);
 int univl_hub_flags(const int32_t* idx, int64_t n, int32_t Ng, int32_t* hub, hipStream_t stream);
 /* gate[i] = hub[top1[i * ld]] != 0 for i < Nq (0 for an index outside [0, Ng)): top1 is the first column of univl_sim_topk's idx. */
 int univl_hub_gate(const int32_t* top1, int64_t ld, int32_t Nq, const int32_t* hub, int32_t Ng, int32_t* gate, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- moment search
+ * WHERE in a retrieved video a text matches: the best window of frames.  The model defines the score -- _mean_pooling_for_similarity
+ * over the window, F.normalize unless use_mil, the inner product with the pooled text (modeling.py:377-391 with the video mask narrowed
+ * to the window); here every window of a video is scored in one launch.
+ * For a query vector q, gallery row v with frames x_0 .. x_{F-1} (768 wide) and mask m, a window (s, L) covers frames s .. s + L - 1.
+ *   candidate   iff lmin <= L <= lmax, 0 <= s, s + L <= F and every frame in it has m != 0: a padded tail or a hole in the mask never
+ *               lies inside a window
+ *   u(s, L)     = x_s + .. + x_{s + L - 1}
+ *   score       normalize = 1:  (q . u) / max(|u|, 1e-12 * L)     -- univl_pool_fwd's normalised value (eps 1e-12 on the mean) dotted with q
+ *               normalize = 0:  (q . u) / L                       -- use_mil models
+ *   ORDER       larger score first; equal scores by lower s; then by smaller L
+ *   result      per pair: start (int32), length (int32), score (fp32); (-1, 0, -inf) for a pair without a candidate window and for a
+ *               candidate id outside [0, N) -- the -1 padding of univl_sim_topk among them; such a pair reads nothing of the gallery
+ * univl_window_norms writes |u(s, L)| of every window of N rows into wnorm [N][F][F] fp32, indexed (s, L - 1): 0 from the first window
+ * of a start that holds a frame with m == 0 on, 0 past the row's end (s + L > F).  Independent of lmin / lmax and of any query: it
+ * depends on the video alone and is computed once per row.  Not needed with normalize = 0.  One wave owns a start and extends u frame
+ * by frame in registers (12 columns per lane); the frames are read from L2, never staged (a row of 128 frames is 393 KB).
+ * univl_moment_localize scores, for each of the P = Nq * K pairs (query row p / K, gallery row rows[p]), every candidate window and
+ * reduces them to the best under ORDER.  One workgroup per pair: the F frame products d_f = q . x_f, then one thread per start grows
+ * the numerators d_s + .. + d_{s + L - 1} and divides by the table entry (or L).  One launch each, no host read, capturable.
+ * PURITY: the score is a function of q, the row's frames and mask, (s, L) and normalize only -- not of the pair's position in the
+ * launch, the grid, the other pairs, N, or deterministic mode; |u(s, L)| likewise of frames s .. s + L - 1 alone.  Equal scores are
+ * therefore meaningful.  Every reduction runs in a fixed order (768 columns: 12 per lane as one fmaf chain in column order, then the xor
+ * butterfly of the wave); there are no float atomics.  q . u and |u| are built BY EXTENSION from the window's start, never as a
+ * difference of prefix sums: LayerNorm outputs have |x_f|^2 near 768, and a summed-area table in fp32 loses about 1e-4 relative on a
+ * one-frame window.
+ * Range: H == 768, 1 <= F <= UNIVL_MOMENT_F_MAX, N >= 1, ld_row >= F * 768, normalize 0 or 1; localize also 1 <= lmin <= lmax <= F,
+ * Nq >= 1, K >= 1, ldq >= 768; otherwise, or for a NULL pointer, UNIVL_EINVAL.  Rows of frames and q (base and leading dimension)
+ * must be 16-byte aligned (UNIVL_EALIGN).  Behaviour on NaN values: unspecified. */
+#define UNIVL_MOMENT_F_MAX 128
+typedef struct UnivlMoment {
+    const float* frames; int64_t ld_row; /* [N, F, 768] fp32 frames of the gallery rows, ld_row floats between rows               */
+    const int64_t* mask;                 /* [N, F] int64, contiguous: 0 = not a frame                                             */
+    float* wnorm;                        /* [N, F, F] fp32: written by univl_window_norms, read by univl_moment_localize           */
+    int32_t N, F, H;                     /* H must be 768                                                                         */
+    int32_t normalize;                   /* 1: divide by max(|u|, 1e-12 L); 0: by L (wnorm may be NULL)                           */
+    /* univl_moment_localize only */
+    const float* q; int64_t ldq;         /* [Nq, ldq] fp32 pooled queries                                                         */
+    const int32_t* rows;                 /* [Nq, K] candidate gallery rows; outside [0, N): (-1, 0, -inf)                          */
+    int32_t Nq, K;
+    int32_t lmin, lmax;
+    int32_t* start; int32_t* length;     /* [Nq, K] each, written                                                                 */
+    float* score;                        /* [Nq, K] written                                                                       */
+} UnivlMoment;
+int univl_moment_sizeof(void);
+int univl_window_norms(const UnivlMoment* d, hipStream_t stream);
+int univl_moment_localize(const UnivlMoment* d, hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

@@ -1,0 +1,221 @@
+// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize): the best-matching window of frames of a
+// gallery video for a pooled text vector, every window of the video scored in ONE launch.
+//
+// A window (s, L) covers frames s .. s + L - 1 of a row; u(s, L) is the sum of its frame vectors.  The score is the model's own --
+// the masked mean over the window, L2-normalised unless use_mil, dotted with the query -- written without the mean:
+//   normalising   (q . u) / max(|u|, 1e-12 L)          use_mil   (q . u) / L
+//
+// Two kernels, no host read, no LDS staging of frames, no float atomics, capturable:
+//   norms      |u(s, L)| of every window of a row, a [F][F] table indexed (s, L - 1).  It depends on the video alone, so an index
+//              computes it once per row.  ONE WAVE OWNS A START s: lane l keeps the 12 columns 4 l + 256 j + c (j < 3, c < 4) of the
+//              running sum u(s, .) in registers, adds frame s + L - 1 to it (three 16-byte loads per lane, the next frame's already in
+//              flight) and squares what it holds: 12 fmaf in column order, then the xor butterfly over the wave.  The frames of a row
+//              are read F / 2 times over, from L2: a row is 144 KB at 48 frames and 393 KB at 128, more than the LDS holds, and a
+//              column slice of it in LDS would need one cross-lane reduction per window AND slice instead of one per window.  A wave
+//              takes start `slot` and then start F - 1 - slot, F + 1 steps in all, so the waves of a row finish together.
+//   localize   one workgroup of 256 threads per (query, candidate) pair.  Wave w computes the frame products d_f = q . x_f of frames
+//              w, w + 4, .. (the lane split and reduction tree of the norms kernel; four frames in flight per wave) into LDS.  Thread s
+//              < F then owns start s: it grows the numerator d_s + .. + d_{s + L - 1} one frame at a time, stops at the first masked
+//              frame or past lmax, divides by the table entry (or by L) and keeps its best window, the shortest among equals.  The F
+//              starts' bests are reduced under the total order (score descending, start ascending, length ascending), so the shape of
+//              that reduction cannot matter.
+//
+// PURITY.  |u(s, L)| is a function of the row's frames s .. s + L - 1 alone, d_f of (q, x_f) alone, a numerator of d_s .. d_{s+L-1}
+// in ascending order: no value depends on the grid, the pair's place in the launch, the other pairs or deterministic mode.  Every sum
+// is built BY EXTENSION from its start; nothing is a difference of prefix sums.
+#include <float.h>
+#include <limits.h>
+#include <stddef.h>
+#include "common.h"
+#include "univl_hip.h"
+
+namespace {
+
+constexpr int MM_H = 768;                    // frame width (the hidden size)
+constexpr int MM_NO_WINDOW = INT_MAX;        // the key of "no candidate window": sorts after every (start, length)
+
+// the lane's 12 columns of one frame: 4 lane + 256 j + c
+__device__ __forceinline__ void load12(f32x4_t (&x)[3], const float* frame, int lane) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) x[j] = *reinterpret_cast<const f32x4_t*>(frame + 4 * lane + 256 * j);
+}
+
+// sum over the wave's 768 columns of a * b: the lane's 12 products as one fmaf chain in column order, then the xor butterfly -- the
+// ONLY reduction over columns in this file, so that every value built on it has one fixed order
+__device__ __forceinline__ float dot768(const f32x4_t (&a)[3], const f32x4_t (&b)[3]) {
+    float p = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) p = fmaf(a[j][c], b[j][c], p);
+    }
+    return wave_sum(p);
+}
+
+// table row s of one gallery row: |u(s, L)| for L = 1 .. F - s while every frame of the window is valid, 0 from the first window that
+// holds a masked frame on, 0 for the lengths past the row's end
+__device__ __forceinline__ void norms_from(const float* __restrict__ x, const int64_t* __restrict__ m, float* __restrict__ t, int F, int s,
+                                           int lane) {
+    f32x4_t u[3], cur[3], nxt[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) u[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    load12(cur, x + (long)s * MM_H, lane);
+    int e = s;
+    for (; e < F; ++e) {
+        if (m[e] == 0) break;                                             // wave-uniform
+        load12(nxt, x + (long)min(e + 1, F - 1) * MM_H, lane);            // the next frame (the last one again at the end: a valid address)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) u[j] += cur[j];
+        const float n2 = dot768(u, u);
+        if (lane == 0) t[e - s] = sqrtf(n2);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cur[j] = nxt[j];
+    }
+    for (int c = e - s + lane; c < F; c += 64) t[c] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void window_norms_kernel(const float* __restrict__ frames, long ld_row, const int64_t* __restrict__ mask,
+                                                           float* __restrict__ wnorm, int F, int bpr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x / bpr, slot = (blockIdx.x % bpr) * 4 + wave;
+    if (slot >= (F + 1) / 2) return;                                      // wave-uniform; the kernel has no barrier
+    const float* x = frames + (long)row * ld_row;
+    const int64_t* m = mask + (long)row * F;
+    float* t = wnorm + (long)row * F * F;
+    norms_from(x, m, t + (long)slot * F, F, slot, lane);
+    const int s2 = F - 1 - slot;
+    if (s2 != slot) norms_from(x, m, t + (long)s2 * F, F, s2, lane);
+}
+
+struct LocArgs {
+    const float* q; long ldq;
+    const float* frames; long ld_row;
+    const int64_t* mask;
+    const float* wnorm;
+    const int32_t* rows;
+    int N, F, K, lmin, lmax, normalize;
+    int32_t* start; int32_t* length; float* score;
+};
+
+// (score, key) order of the contract: larger score first, then the lower key = 256 start + length
+__device__ __forceinline__ void keep_better(float& v, int& k, float v2, int k2) {
+    if (v2 > v || (v2 == v && k2 < k)) { v = v2; k = k2; }
+}
+
+__global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
+    __shared__ float d[UNIVL_MOMENT_F_MAX];          // frame products
+    __shared__ int valid[UNIVL_MOMENT_F_MAX];
+    __shared__ float bv[UNIVL_MOMENT_F_MAX];         // every start's best window
+    __shared__ int bk[UNIVL_MOMENT_F_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = a.F;
+    const long p = blockIdx.x;
+    const int cand = a.rows[p];
+    if (cand < 0 || cand >= a.N) {                                        // block-uniform: nothing of the gallery is read
+        if (tid == 0) { a.start[p] = -1; a.length[p] = 0; a.score[p] = -INFINITY; }
+        return;
+    }
+    const float* x = a.frames + (long)cand * a.ld_row;
+    f32x4_t qv[3];
+    load12(qv, a.q + (p / a.K) * a.ldq, lane);
+    for (int f0 = wave; f0 < F; f0 += 16) {
+        f32x4_t xv[4][3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) load12(xv[r], x + (long)min(f0 + 4 * r, F - 1) * MM_H, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float s = dot768(qv, xv[r]);
+            if (lane == 0 && f0 + 4 * r < F) d[f0 + 4 * r] = s;
+        }
+    }
+    if (tid < UNIVL_MOMENT_F_MAX) valid[tid] = (tid < F && a.mask[(long)cand * F + tid] != 0) ? 1 : 0;
+    __syncthreads();
+
+    if (tid < UNIVL_MOMENT_F_MAX) {
+        float best = -INFINITY;
+        int key = MM_NO_WINDOW;
+        if (tid < F) {
+            const int s = tid;
+            const float* t = a.normalize ? a.wnorm + ((long)cand * F + s) * F : nullptr;
+            float num = 0.f;
+            for (int e = s; e < F && e - s < a.lmax && valid[e]; ++e) {
+                num += d[e];
+                const int L = e - s + 1;
+                if (L < a.lmin) continue;
+                const float den = a.normalize ? fmaxf(t[L - 1], 1e-12f * (float)L) : (float)L;
+                const float sc = num / den;
+                if (key == MM_NO_WINDOW || sc > best) { best = sc; key = 256 * s + L; }      // the shortest among equals stays
+            }
+        }
+        bv[tid] = best; bk[tid] = key;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float v = bv[lane];
+        int k = bk[lane];
+        keep_better(v, k, bv[lane + 64], bk[lane + 64]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(v, o, 64);
+            const int k2 = __shfl_xor(k, o, 64);
+            keep_better(v, k, v2, k2);
+        }
+        if (lane == 0) {
+            const bool none = k == MM_NO_WINDOW;
+            a.start[p] = none ? -1 : k >> 8;
+            a.length[p] = none ? 0 : k & 255;
+            a.score[p] = none ? -INFINITY : v;
+        }
+    }
+}
+
+// the checks both entry points share: the gallery side of the descriptor
+int check_gallery(const char* who, const UnivlMoment* d) {
+    UNIVL_CHECK_ARG(d->H == MM_H, UNIVL_EINVAL, "%s: H=%d (must be 768)", who, d->H);
+    UNIVL_CHECK_ARG(d->F >= 1 && d->F <= UNIVL_MOMENT_F_MAX, UNIVL_EINVAL, "%s: F=%d (1 <= F <= %d)", who, d->F, UNIVL_MOMENT_F_MAX);
+    UNIVL_CHECK_ARG(d->N >= 1 && d->N <= INT_MAX / 16, UNIVL_EINVAL, "%s: N=%d (>= 1)", who, d->N);
+    UNIVL_CHECK_ARG(d->normalize == 0 || d->normalize == 1, UNIVL_EINVAL, "%s: normalize=%d (0 or 1)", who, d->normalize);
+    UNIVL_CHECK_ARG(d->frames && d->mask, UNIVL_EINVAL, "%s: null pointer (frames, mask)", who);
+    UNIVL_CHECK_ARG(d->ld_row >= (int64_t)d->F * MM_H, UNIVL_EINVAL, "%s: ld_row=%lld (>= F * 768)", who, (long long)d->ld_row);
+    UNIVL_CHECK_ARG(aligned16(d->frames) && d->ld_row % 4 == 0, UNIVL_EALIGN, "%s: rows of frames must be 16-byte aligned", who);
+    return UNIVL_OK;
+}
+
+}  // namespace
+
+extern "C" int univl_moment_sizeof(void) { return (int)sizeof(UnivlMoment); }
+
+extern "C" int univl_window_norms(const UnivlMoment* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_window_norms: null descriptor");
+    const int rc = check_gallery("univl_window_norms", d);
+    if (rc != UNIVL_OK) return rc;
+    UNIVL_CHECK_ARG(d->wnorm != nullptr, UNIVL_EINVAL, "univl_window_norms: null pointer (wnorm)");
+    const int bpr = ((d->F + 1) / 2 + 3) / 4;                             // four waves per block, a wave per pair of starts
+    hipLaunchKernelGGL(window_norms_kernel, dim3((unsigned)d->N * bpr), dim3(256), 0, stream, d->frames, (long)d->ld_row, d->mask, d->wnorm, d->F,
+                       bpr);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_moment_localize(const UnivlMoment* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_moment_localize: null descriptor");
+    const int rc = check_gallery("univl_moment_localize", d);
+    if (rc != UNIVL_OK) return rc;
+    const char* who = "univl_moment_localize";
+    UNIVL_CHECK_ARG(d->lmin >= 1 && d->lmin <= d->lmax && d->lmax <= d->F, UNIVL_EINVAL, "%s: lmin=%d lmax=%d (1 <= lmin <= lmax <= F=%d)", who,
+                    d->lmin, d->lmax, d->F);
+    UNIVL_CHECK_ARG(d->Nq >= 1 && d->K >= 1 && (int64_t)d->Nq * d->K <= INT_MAX, UNIVL_EINVAL, "%s: Nq=%d K=%d (both >= 1, Nq * K < 2^31)", who,
+                    d->Nq, d->K);
+    UNIVL_CHECK_ARG(d->q && d->rows && d->start && d->length && d->score, UNIVL_EINVAL, "%s: null pointer (q, rows, start, length, score)", who);
+    UNIVL_CHECK_ARG(!d->normalize || d->wnorm != nullptr, UNIVL_EINVAL, "%s: null pointer (wnorm with normalize)", who);
+    UNIVL_CHECK_ARG(d->ldq >= MM_H, UNIVL_EINVAL, "%s: ldq=%lld (>= 768)", who, (long long)d->ldq);
+    UNIVL_CHECK_ARG(aligned16(d->q) && d->ldq % 4 == 0, UNIVL_EALIGN, "%s: rows of q must be 16-byte aligned", who);
+    LocArgs a;
+    a.q = d->q; a.ldq = (long)d->ldq; a.frames = d->frames; a.ld_row = (long)d->ld_row; a.mask = d->mask; a.wnorm = d->wnorm; a.rows = d->rows;
+    a.N = d->N; a.F = d->F; a.K = d->K; a.lmin = d->lmin; a.lmax = d->lmax; a.normalize = d->normalize;
+    a.start = d->start; a.length = d->length; a.score = d->score;
+    hipLaunchKernelGGL(moment_localize_kernel, dim3((unsigned)(d->Nq * d->K)), dim3(256), 0, stream, a);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}

@@ -13,7 +13,10 @@ host once.
 
 Caption likelihood: eval_caption_loss is the validation loss the caption task's training never reports -- the teacher-forced
 CrossEntropyLoss(ignore_index=-1) of modeling.py:246-254 over a whole loader, with perplexity and token accuracy, around ONE scoring
-session (univl_amd.score.CaptionScorer)."""
+session (univl_amd.score.CaptionScorer).
+
+Localisation: eval_localization scores where in its own video every text is found (retrieval.VideoIndex.localize) against annotated
+segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices."""
 import math
 import os
 
@@ -107,6 +110,56 @@ def eval_retrieval_streamed(model, text_batches, video_batches, targets, device=
         model.train(was_training)
     gt, eq = torch.cat(gts).cpu().numpy(), torch.cat(eqs).cpu().numpy()
     return compute_metrics((gt, eq)), (gt, eq)
+
+
+@torch.no_grad()
+def eval_localization(model, index, text_batches, targets, gt_start, gt_len, window, device="cuda"):
+    """Step localisation: every text is localised in ITS OWN video and the window found is compared with the annotated one.
+    index: a retrieval.VideoIndex(model, keep_frames=True) holding the videos; text_batches: iterable of (input_ids, input_mask,
+    segment_ids), the loader's order; targets / gt_start / gt_len: for every text row, in order, its gallery row and its annotated
+    segment, frames gt_start .. gt_start + gt_len - 1 (gt_len >= 1); window = (lmin, lmax): the lengths searched
+    (VideoIndex.localize).  Temporal IoU over frame indices; a threshold is decided in integers (10 * inter >= 3 * union, ...), so no
+    rounding enters a count.  A text whose video has no candidate window counts as IoU 0 and is reported in n_empty.
+    Returns {"mIoU", "R1@0.3", "R1@0.5", "R1@0.7"} (fractions of the n texts; mIoU a float64 mean taken on the host), "n", "n_empty"."""
+    if index.model is not model:
+        raise ValueError("eval_localization: the index belongs to another model")
+    as_i32 = lambda x: torch.as_tensor(x).reshape(-1).to(device=device, dtype=torch.int32)
+    targets, gt_start, gt_len = as_i32(targets), as_i32(gt_start), as_i32(gt_len)
+    n = targets.numel()
+    if gt_start.numel() != n or gt_len.numel() != n:
+        raise ValueError("eval_localization: %d targets, %d gt_start, %d gt_len" % (n, gt_start.numel(), gt_len.numel()))
+    if n and (int(targets.min()) < 0 or int(targets.max()) >= len(index) or int(gt_len.min()) < 1 or int(gt_start.min()) < 0):
+        raise ValueError("eval_localization: targets must lie in [0, %d), gt_start >= 0 and gt_len >= 1" % len(index))
+    was_training = model.training
+    model.eval()
+    try:
+        starts, lengths, row = [], [], 0
+        for batch in text_batches:
+            input_ids, input_mask, segment_ids = [t.to(device) for t in batch[:3]]
+            b = input_ids.numel() // input_ids.shape[-1]
+            if row + b > n:
+                raise ValueError("eval_localization: more text rows than targets (%d)" % n)
+            s, l, _ = index.localize(input_ids, segment_ids, input_mask, targets[row:row + b].reshape(b, 1), window)
+            starts.append(s.reshape(-1))
+            lengths.append(l.reshape(-1))
+            row += b
+        if row != n:
+            raise ValueError("eval_localization: %d text rows for %d targets" % (row, n))
+    finally:
+        model.train(was_training)
+    if n == 0:
+        raise ValueError("eval_localization: no texts")
+    s, l = torch.cat(starts), torch.cat(lengths)                          # an empty result is (-1, 0): it meets no frame
+    inter = (torch.minimum(s + l, gt_start + gt_len) - torch.maximum(s, gt_start)).clamp_(min=0)
+    inter = torch.where(l > 0, inter, torch.zeros_like(inter))
+    union = l + gt_len - inter
+    host = torch.stack([inter, union, l]).cpu().numpy().astype(np.int64)  # the one host read
+    inter, union, l = host
+    out = {"mIoU": float(np.mean(inter.astype(np.float64) / union.astype(np.float64)))}
+    for name, num in (("R1@0.3", 3), ("R1@0.5", 5), ("R1@0.7", 7)):
+        out[name] = float(np.sum(10 * inter >= num * union)) / n
+    out["n"], out["n_empty"] = n, int(np.sum(l == 0))
+    return out
 
 
 def ids_to_caption(tokenizer, ids):

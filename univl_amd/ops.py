@@ -785,6 +785,59 @@ def hub_gate(top1, hub):
     return gate
 
 
+def _moment_gallery(frames, mask, normalize):
+    """The gallery side of a Moment descriptor (window_norms and moment_localize)."""
+    _require_gpu(frames, mask)
+    assert frames.dtype == torch.float32 and frames.dim() == 3 and frames.stride(2) == 1 and frames.stride(1) == frames.shape[2]
+    assert mask.dtype == torch.int64 and mask.shape == frames.shape[:2] and mask.is_contiguous()
+    d = _lib.Moment()
+    d.N, d.F, d.H, d.normalize = frames.shape[0], frames.shape[1], frames.shape[2], 1 if normalize else 0
+    d.frames, d.ld_row, d.mask = _p(frames), frames.stride(0) if d.N > 1 else d.F * d.H, _p(mask)     # one row: its stride means nothing
+    return d
+
+
+def window_norms(frames, mask, *, out=None):
+    """|u(s, L)| of every window of every gallery row, u the sum of frames s .. s + L - 1 (include/univl_hip.h: univl_window_norms).
+    frames: [N, F, 768] fp32 (frames contiguous, rows 16-byte aligned), F <= MOMENT_F_MAX; mask: [N, F] int64, 0 = not a frame; out:
+    optional [N, F, F] fp32 to write.  Returns the table [N, F, F] fp32 indexed (s, L - 1): 0 where the window holds a masked frame
+    or runs past the row's end.  It depends on the videos alone: compute it once per row, for models that normalise."""
+    d = _moment_gallery(frames, mask, True)
+    t = torch.empty(d.N, d.F, d.F, dtype=torch.float32, device=frames.device) if out is None else out
+    _require_gpu(t)
+    assert t.dtype == torch.float32 and t.shape == (d.N, d.F, d.F) and t.is_contiguous()
+    d.wnorm = _p(t)
+    _lib.check(_lib.lib().univl_window_norms(_BYREF(d), _stream()), "window_norms")
+    return t
+
+
+def moment_localize(q, frames, mask, rows, lmin, lmax, *, wnorm=None, normalize=True):
+    """The best window of frames of gallery row rows[i, j] for query row i, every window scored in one launch (include/univl_hip.h:
+    univl_moment_localize).  q: [Nq, 768] fp32 row-major view (row stride >= 768, rows 16-byte aligned); frames, mask: as
+    window_norms'; rows: [Nq, K] int32 contiguous gallery rows (sim_topk's indices, say); 1 <= lmin <= lmax <= F: the window lengths
+    searched; wnorm: window_norms' table of the same gallery, needed when normalize; normalize: False for use_mil models (the score
+    is then the mean's inner product).  Returns (start, length, score), [Nq, K] int32, int32, fp32: the window with the largest score,
+    equal scores by lower start, then by smaller length; (-1, 0, -inf) where no window lies inside the valid frames or the row id is
+    outside the gallery (the -1 of sim_topk)."""
+    d = _moment_gallery(frames, mask, normalize)
+    _require_gpu(q, rows, wnorm)
+    assert q.dtype == torch.float32 and q.dim() == 2
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == q.shape[0] and rows.is_contiguous()
+    if q.shape[1] != frames.shape[2]:
+        raise RuntimeError("moment_localize: q is %d wide, the frames %d" % (q.shape[1], frames.shape[2]))
+    if normalize:
+        if wnorm is None:
+            raise RuntimeError("moment_localize: normalize=True needs wnorm (window_norms)")
+        assert wnorm.dtype == torch.float32 and wnorm.shape == (d.N, d.F, d.F) and wnorm.is_contiguous()
+        d.wnorm = _p(wnorm)
+    d.q, d.ldq, d.rows, d.Nq, d.K, d.lmin, d.lmax = _p(q), _ld(q), _p(rows), rows.shape[0], rows.shape[1], int(lmin), int(lmax)
+    start = torch.empty(d.Nq, d.K, dtype=torch.int32, device=q.device)
+    length = torch.empty(d.Nq, d.K, dtype=torch.int32, device=q.device)
+    score = torch.empty(d.Nq, d.K, dtype=torch.float32, device=q.device)
+    d.start, d.length, d.score = _p(start), _p(length), _p(score)
+    _lib.check(_lib.lib().univl_moment_localize(_BYREF(d), _stream()), "moment_localize")
+    return start, length, score
+
+
 class AdamTables:
     """Device copies of a UnivlSeg[] and a chunk table (adam_tables); keeps the tensors alive for the descriptors that point at them."""
 

@@ -11,7 +11,11 @@ candidates of every query through it (queries x k pairs instead of queries x gal
 
 QueryBank is the search-time remedy against hubness (query-bank normalisation, the dynamic inverted softmax): a bank of other texts
 -- training captions, say -- states how strongly every video is already claimed, and search(..., bank=) ranks by the score minus that
-column term (include/univl_hip.h: univl_sim_colstat, univl_sim_topk_norm).  No retraining, and no [bank, gallery] matrix."""
+column term (include/univl_hip.h: univl_sim_colstat, univl_sim_topk_norm).  No retraining, and no [bank, gallery] matrix.
+
+Moment search says WHERE in a video a text matches: VideoIndex(keep_frames=True).localize() scores every window of frames of a
+candidate video the way get_similarity_logits scores the whole video (include/univl_hip.h: univl_window_norms,
+univl_moment_localize) and returns the best one; search_moments() does that for the best videos of a search and ranks the moments."""
 import ctypes
 import math
 import numbers
@@ -32,6 +36,7 @@ class VideoIndex:
         self.model, self.keep_frames = model, bool(keep_frames)
         self._cap, self._n = int(capacity), 0
         self._buf = self._frames = self._fmask = None
+        self._wnorm, self._wnorm_rows = None, 0          # localize(): the window-norm table and how many rows of it are filled
 
     def __len__(self):
         return self._n
@@ -68,6 +73,10 @@ class VideoIndex:
                     frames[:self._n].copy_(self._frames[:self._n])
                     fmask[:self._n].copy_(self._fmask[:self._n])
                 self._frames, self._fmask = frames, fmask
+                if self._wnorm is not None:
+                    wnorm = torch.empty(cap, F, F, device=dev, dtype=torch.float32)
+                    wnorm[:self._wnorm_rows].copy_(self._wnorm[:self._wnorm_rows])
+                    self._wnorm = wnorm
         self._cap = cap
         return self._buf
 
@@ -176,6 +185,70 @@ class VideoIndex:
         ids, perm = torch.sort(idx.long(), dim=1, stable=True)
         sc, perm2 = torch.sort(cross.gather(1, perm), dim=1, descending=True, stable=True)
         return sc, ids.gather(1, perm2).to(torch.int32)
+
+    # ------------------------------------------------------------------------------------------ moment search
+    def _window_norms(self):
+        """[len(index), F, F] window norms (ops.window_norms), filled lazily: the table depends on the videos alone, so the rows added
+        since the last call are computed and the others kept.  Allocated by the first localisation of a normalising model."""
+        F = self._frames.shape[1]
+        if self._wnorm is None:
+            self._wnorm = torch.empty(self._cap, F, F, device=self._device(), dtype=torch.float32)
+        lo, n = self._wnorm_rows, self._n
+        if lo < n:
+            ops.window_norms(self._frames[lo:n], self._fmask[lo:n], out=self._wnorm[lo:n])
+            self._wnorm_rows = n
+        return self._wnorm[:n]
+
+    @torch.no_grad()
+    def localize(self, input_ids, token_type_ids, attention_mask, rows, window):
+        """The best-matching window of frames of gallery row rows[i, j] for text i.  rows: [Nq, K] int32 gallery rows, search()'s
+        indices say; window = (lmin, lmax): the lengths searched, in frames.  Returns (start, length, score), each [Nq, K] on the
+        device: the window whose masked mean -- normalised unless use_mil, as get_similarity_logits scores a whole video -- has the
+        largest inner product with the pooled text; equal scores by lower start, then smaller length; (-1, 0, -inf) where no window of
+        these lengths lies inside the valid frames, and for the -1 rows of a short search.  Needs keep_frames=True."""
+        return self.localize_vectors(self.pool_text(input_ids, token_type_ids, attention_mask)[0], rows, window)
+
+    @torch.no_grad()
+    def localize_vectors(self, q, rows, window):
+        """localize() for pooled query vectors the caller already holds ([Nq, 768] fp32 on the index's device)."""
+        if not self.keep_frames or self._frames is None:
+            raise ValueError("VideoIndex.localize needs an index built with keep_frames=True, with videos in it")
+        F = self._frames.shape[1]
+        lmin, lmax = (int(w) for w in window)
+        if not 1 <= lmin <= lmax <= F:
+            raise ValueError("VideoIndex.localize: window=(%d, %d), need 1 <= lmin <= lmax <= %d frames" % (lmin, lmax, F))
+        if F > _lib.MOMENT_F_MAX:
+            raise ValueError("VideoIndex.localize: videos of %d frames, at most %d" % (F, _lib.MOMENT_F_MAX))
+        q = q.reshape(-1, H).to(torch.float32)
+        if q.stride(1) != 1 or q.stride(0) % 4 or q.data_ptr() % 16:
+            q = q.contiguous()
+        rows = torch.as_tensor(rows).to(device=q.device, dtype=torch.int32).reshape(q.shape[0], -1).contiguous()
+        wnorm = self._window_norms() if self.normalize else None
+        return ops.moment_localize(q, self._frames[:self._n], self._fmask[:self._n], rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
+
+    @torch.no_grad()
+    def search_moments(self, input_ids, token_type_ids, attention_mask, k=10, window=(1, 1), shortlist=None, bank=None):
+        """The k best (video, window) moments for every text.  The `shortlist` (default k, at most TOPK_MAX) best videos by WHOLE-VIDEO
+        score come from search_vectors -- through `bank` if one is given -- each is localised, and the shortlist is re-ordered by window
+        score.  So the result is exhaustive over the index when shortlist >= len(index) and otherwise what it says: the best moments
+        among the videos a whole-video search ranks first; a moment in a video that scores poorly as a whole is not found.
+        Returns (score, idx, start, length), each [Nq, k] on the device, rows by descending window score, equal scores by lower row
+        id first; videos without a candidate window come last (start -1, length 0, score -inf), the -1 rows of a short gallery after
+        them."""
+        k = int(k)
+        shortlist = k if shortlist is None else int(shortlist)
+        if not 1 <= k <= shortlist <= _lib.TOPK_MAX:
+            raise ValueError("VideoIndex.search_moments: k=%d shortlist=%d, need 1 <= k <= shortlist <= %d" % (k, shortlist, _lib.TOPK_MAX))
+        if not self.keep_frames:
+            raise ValueError("VideoIndex.search_moments needs an index built with keep_frames=True")
+        q = self.pool_text(input_ids, token_type_ids, attention_mask)[0]
+        _, idx = self.search_vectors(q, shortlist, None, bank)
+        start, length, score = self.localize_vectors(q, idx, window)
+        # each row by descending window score, equal scores by lower row id first: ids ascending, then a stable sort by score (_rerank)
+        ids, perm = torch.sort(torch.where(idx < 0, torch.full_like(idx, _NO_ROW), idx).long(), dim=1, stable=True)
+        sc, perm2 = torch.sort(score.gather(1, perm), dim=1, descending=True, stable=True)
+        order = perm.gather(1, perm2)[:, :k]
+        return sc[:, :k].contiguous(), idx.gather(1, order), start.gather(1, order), length.gather(1, order)
 
 
 class QueryBank:
