@@ -6,8 +6,10 @@ written to an .npz: run it once per build of the library, each in a fresh proces
 Entry points: univl_beam_step (a first and a later step, n_bm = 5), univl_beam_group_step (G = 2, lambda = 0.5, a first and a later
 step), univl_beam_pool_step over a run of tests/pool_beam_ref.py (n_bm = 5) with univl_beam_pool_finish (n_best = 3), univl_beam_backtrack
 -- each at (V, ld) = (37, 40) and (30522, 30528) with one of 3 instances preset done --, univl_sample_step (k = 50), univl_sim_topk (Nq = 33, Ng = 300,
-k = 10, with a target), univl_vocab_score, univl_vocab_ce_fwd / _bwd.  Every input set holds engineered ties: equal values whose
-order only the tie rule (lower index first) decides."""
+k = 10, with a target), univl_sim_colstat (Nb = 129, Ng = 33), univl_hub_flags / univl_hub_gate, univl_sim_topk_norm (Nq = 17, Ng = 65,
+k = 10, gated and with a target), univl_window_norms and univl_moment_localize (F = 8 and 50, a masked frame, candidates outside the
+gallery), univl_vocab_score, univl_vocab_ce_fwd / _bwd.  Every input set holds engineered ties: equal values whose order only the tie
+rule (lower index first) decides."""
 import os
 import sys
 
@@ -122,6 +124,44 @@ def main(lib_path, out_path):
         keep("sim_topk.slices%d" % slices, score=score, idx=idx, gt=gt, eq=eq)
     score, idx = ops.sim_topk(q[:7].to(dev), g.to(dev), 64)         # one query block, the longest list
     keep("sim_topk.k64", score=score, idx=idx)
+
+    # ---- query-bank normalisation: univl_sim_colstat at Nb = 129 (two bank tiles, the second one row), Ng = 33 (two gallery blocks);
+    # univl_hub_flags / univl_hub_gate; univl_sim_topk_norm at Nq = 17, Ng = 65, k = 10 with a gate and a target.  Real-valued unit
+    # vectors for the column term (its exp / log are the point), the integer operands above for the normalised search (ties).
+    unit = lambda n, seed: torch.nn.functional.normalize(gen(n, 768, seed=seed), dim=-1)
+    bank, gal = unit(129, 19).to(dev), unit(33, 20).to(dev)
+    gal[7] = gal[30]
+    keep("sim_colstat.Nb129", c=ops.sim_colstat(bank, gal, 20.0), c_beta1=ops.sim_colstat(bank, gal, 1.0))
+    _, top = ops.sim_topk(bank, gal, 2)
+    hub = ops.hub_flags(top, 33)
+    _, top1 = ops.sim_topk(gal[:17], gal, 3)
+    keep("hub", top=top, flags=hub, gate=ops.hub_gate(top1, hub), gate_1d=ops.hub_gate(top1[:, 0].contiguous(), hub))
+    qn, gn = q[:17].to(dev), g[:65].to(dev)
+    bias = (torch.arange(65) % 7).float().to(dev)                      # integers: the normalised scores stay exact, and tie
+    gate = (torch.arange(17, dtype=torch.int32) % 3 != 1).to(torch.int32).to(dev)
+    tgt = ((torch.arange(17, dtype=torch.int32) * 5) % 65).to(dev)
+    score, idx, gt, eq = ops.sim_topk_norm(qn, gn, 10, bias, row_gate=gate, target=tgt)
+    keep("sim_topk_norm.gated", score=score, idx=idx, gt=gt, eq=eq)
+    score, idx = ops.sim_topk_norm(qn, gn, 10, bias)
+    keep("sim_topk_norm.static", score=score, idx=idx)
+
+    # ---- moment search: univl_window_norms and univl_moment_localize at F = 8 and F = 50, 5 gallery rows, a masked frame inside
+    # row 1 and a short row 2, candidates that name every row, a row twice, -1 and a row past the gallery; both score forms
+    for F in (8, 50):
+        frames = gen(5, F, 768, seed=21 + F).to(dev)
+        frames[3, 2] = frames[3, 1]                                    # equal frames: equal window scores, the tie rule decides
+        fmask = torch.ones(5, F, dtype=torch.int64)
+        fmask[1, F // 2] = 0
+        fmask[2, F - 3:] = 0
+        fmask = fmask.to(dev)
+        wn = ops.window_norms(frames, fmask)
+        qm = gen(3, 768, seed=23 + F).to(dev)
+        rows = torch.tensor([[0, 1, 2, 3], [4, 4, -1, 5], [3, 2, 1, 0]], dtype=torch.int32, device=dev)
+        for norm in (True, False):
+            st, ln, sc = ops.moment_localize(qm, frames, fmask, rows, 1, F, wnorm=wn if norm else None, normalize=norm)
+            st2, ln2, sc2 = ops.moment_localize(qm, frames, fmask, rows, 2, min(F, 5), wnorm=wn if norm else None, normalize=norm)
+            keep("moment.F%d.%s" % (F, "norm" if norm else "mil"), start=st, length=ln, score=sc, start_w=st2, length_w=ln2, score_w=sc2)
+        keep("window_norms.F%d" % F, wnorm=wn)
 
     # ---- the vocabulary head, both forms and the backward, fp32 (K = 32) and bf16 (K = 64): 130 rows x 1002 columns of integer
     # operands (exact logits), columns 3 / 130 / 1001 identical and lifted to the top on every third row; then real-valued operands at

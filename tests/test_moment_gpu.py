@@ -20,6 +20,7 @@ import torch
 from make_golden import case_config
 
 import moment_ref as R
+from retrieval_cases import batches as _batches, deterministic_models  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +29,6 @@ if torch.cuda.is_available():
     from univl_amd import _lib, ops
     from univl_amd import eval as uev
     from test_model_gpu import build
-    from test_retrieve_gpu import _batches, deterministic_models  # noqa: F401  (the fixture)
 
 DEV = "cuda"
 H = 768
@@ -443,3 +443,43 @@ def test_lazy_norms_growth_search_moments_and_eval_localization(deterministic_mo
     n_found = int(found.sum())
     assert m2["R1@0.3"] == m2["R1@0.5"] == n_found / 8 and m2["R1@0.7"] == 0.0 and m2["mIoU"] == 0.5 * n_found / 8
     assert m2 == R.iou_counts(f_start, f_length, np.where(found, f_start, 0), np.where(found, 2 * f_length, 1))
+
+
+def test_every_buffer_of_one_index_grows_in_the_same_run(deterministic_models):
+    """Vectors, frames, masks, the window-norm table and the bank's column terms all outgrow their buffers between two uses (capacity
+    2 -> 4 -> 8 in one add, the table and c partly filled); every result equals, bit for bit, the same five videos in an index that
+    never grew, under a fresh fit."""
+    from univl_amd.retrieval import QueryBank, VideoIndex
+    cfg, rows, dseed = case_config("joint_small")
+    model, _ = build(cfg, torch.float32)
+    model.eval()
+    bs = _batches(cfg, [2, 3], dseed)
+    cat = {k: torch.cat([b[k] for b in bs]) for k in bs[0]}
+    text = (cat["input_ids"], cat["token_type_ids"], cat["attention_mask"])
+    bank_text = (bs[1]["input_ids"], bs[1]["token_type_ids"], bs[1]["attention_mask"])          # 3 texts
+    F, W = cfg.max_frames, (1, min(3, cfg.max_frames))
+
+    def grown(capacity, stop_after_first):
+        index = VideoIndex(model, capacity=capacity, keep_frames=True)
+        bank = QueryBank(index, beta=20.0, hub_k=2)
+        bank.add(*bank_text)
+        index.add(bs[0]["video"], bs[0]["video_mask"])
+        if stop_after_first:
+            bank.fit()
+            short = index.search_moments(*text, k=5, window=W, shortlist=5, bank=bank)      # a gallery of 2: three empty slots per row
+            assert index._cap == 2 and index._wnorm.shape == (2, F, F) and index._wnorm_rows == 2 and bank._c.numel() == 2
+            assert torch.all(short[1][:, 2:] == -1) and torch.all(short[0][:, 2:] == NEG_INF)
+        index.add(bs[1]["video"], bs[1]["video_mask"])
+        if stop_after_first:
+            assert index._cap == 8 and index._wnorm.shape == (8, F, F) and index._wnorm_rows == 2 and bank._covered == 2
+            assert index._buf.shape[0] == index._frames.shape[0] == index._fmask.shape[0] == 8
+        bank.fit()
+        out = index.search_moments(*text, k=5, window=W, shortlist=5, bank=bank)
+        assert index._wnorm_rows == 5 and bank._c.numel() == 8 and bank._covered == 5
+        return out, bank.c.clone(), bank.hub.clone()
+
+    (got, c, hub), (want, c0, hub0) = grown(2, True), grown(8, False)
+    for a, b in zip(got, want):                                           # scores, ids, starts, lengths
+        assert a.shape == (5, 5) and torch.equal(a, b)
+    assert c.shape == (5,) and torch.equal(c, c0) and torch.equal(hub, hub0)
+    assert int(got[1].min()) >= 0 and sorted(got[1][0].tolist()) == [0, 1, 2, 3, 4]

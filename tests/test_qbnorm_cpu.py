@@ -16,6 +16,7 @@ from univl_amd import _lib, ops
 from univl_amd.retrieval import QueryBank, VideoIndex
 
 import qbnorm_ref as R
+from retrieval_cases import header_fields as _header_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "univl_hip.h")).read()
@@ -52,21 +53,6 @@ def test_entry_points_are_declared_exported_and_bound():
     assert all(t is C.c_int32 and p.startswith("int32_t ") for p, t in zip(params, fn.argtypes))
     for name in ("sim_colstat", "sim_topk_norm", "hub_flags", "hub_gate"):
         assert callable(getattr(ops, name))
-
-
-def _header_fields(struct):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), HEADER, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    kinds = {"int32_t": _lib.i32, "int64_t": _lib.i64, "float": _lib.f32, "ptr": _lib.vp}
-    want = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        m = re.match(r"(const\s+)?(\w+)\s*(\*?)\s*(.*)", decl)
-        for nm in m.group(4).split(","):
-            want.append((nm.strip(), kinds["ptr" if m.group(3) else m.group(2)]))
-    return want
 
 
 @needs_lib

@@ -22,6 +22,7 @@ import torch
 from make_golden import case_config
 
 import qbnorm_ref as R
+from retrieval_cases import batches as _batches, deterministic_models, int_gallery, padded as _padded  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,33 +41,11 @@ def _np(t):
     return t.cpu().numpy()
 
 
-def _padded(x, ld):
-    """x as a [rows, 768] device view with row stride ld; the padding must never enter a score."""
-    buf = torch.full((x.shape[0], ld), 77.0, dtype=torch.float32)
-    buf[:, :H] = x
-    return buf.to(DEV)[:, :H]
-
-
 @functools.lru_cache(maxsize=None)
 def _int_case(Nq, Ng):
     """Integer queries and gallery in [-8, 8] (every partial sum exact in fp32), built as tests/test_retrieve_gpu.py builds them: rows
     j = 5, 9, 13, ... duplicate row j % 3, targets sit on duplicated rows where there are any.  (q, g, targets, int64 scores)."""
-    gen = torch.Generator().manual_seed(1000 * Nq + Ng)
-    q = torch.randint(-8, 9, (Nq, H), generator=gen).float()
-    g = torch.randint(-8, 9, (Ng, H), generator=gen).float()
-    for j in range(5, Ng, 4):
-        g[j] = g[j % 3]
-    tgt = torch.tensor([(5 + 4 * i) % Ng if Ng > 5 else i % Ng for i in range(Nq)], dtype=torch.int32)
-    return q, g, tgt, (q.to(torch.int64) @ g.to(torch.int64).t()).numpy()
-
-
-def _batches(cfg, sizes, seed):
-    import univl_oracle as O
-    out = []
-    for n, b in enumerate(sizes):
-        bt = O.synthetic_batch(cfg, b, seed=seed + n)
-        out.append({k: bt[k].to(DEV) for k in ("input_ids", "attention_mask", "token_type_ids", "video", "video_mask")})
-    return out
+    return int_gallery(Nq, Ng)
 
 
 def _matrix(q, g):
@@ -296,14 +275,6 @@ def test_hub_case_normalisation_restores_the_true_video():
 
 
 # ------------------------------------------------------------------------------------------------ 7: the Python surface
-@pytest.fixture
-def deterministic_models():
-    was = univl_amd.deterministic()
-    univl_amd.set_deterministic(True)
-    yield
-    univl_amd.set_deterministic(was)
-
-
 def _counts(sp, targets):
     ts = sp[np.arange(sp.shape[0]), np.asarray(targets)]
     return (sp > ts[:, None]).sum(1), (sp == ts[:, None]).sum(1)

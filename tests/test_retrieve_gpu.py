@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from make_golden import case_config
+from retrieval_cases import batches as _batches, deterministic_models, int_gallery, padded as _padded  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,13 +34,6 @@ NEG_INF = float("-inf")
 
 
 # ------------------------------------------------------------------------------------------------ references
-def _padded(x, ld):
-    """x as a [rows, 768] device view with row stride ld."""
-    buf = torch.full((x.shape[0], ld), 77.0, dtype=torch.float32)         # the padding must never enter a score
-    buf[:, :H] = x
-    return buf.to(DEV)[:, :H]
-
-
 def _ref_topk(s, k):
     """s: [Nq, Ng] numpy scores.  (idx [Nq, k] int64 with -1 tails, the sorted order) under the tie rule: score descending, equal
     scores by lower index first."""
@@ -53,13 +47,7 @@ def _ref_topk(s, k):
 @functools.lru_cache(maxsize=None)
 def _int_case(Nq, Ng):
     """Integer queries and gallery; rows j with j % 4 == 1 duplicate an earlier row; targets sit on duplicated rows where there are any."""
-    gen = torch.Generator().manual_seed(1000 * Nq + Ng)
-    q = torch.randint(-8, 9, (Nq, H), generator=gen).float()
-    g = torch.randint(-8, 9, (Ng, H), generator=gen).float()
-    for j in range(5, Ng, 4):
-        g[j] = g[j % 3]
-    tgt = torch.tensor([(5 + 4 * i) % Ng if Ng > 5 else i % Ng for i in range(Nq)], dtype=torch.int32)
-    s = (q.to(torch.int64) @ g.to(torch.int64).t()).numpy()                # the int64 reference
+    q, g, tgt, s = int_gallery(Nq, Ng)                                     # s: the int64 reference
     ts = s[np.arange(Nq), tgt.numpy()]
     gt = (s > ts[:, None]).sum(1)
     eq = (s == ts[:, None]).sum(1)
@@ -234,24 +222,6 @@ def test_every_bad_argument_is_refused_with_a_message():
 
 
 # ------------------------------------------------------------------------------------------------ E: single-modality feature calls
-@pytest.fixture
-def deterministic_models():
-    """Models built inside the test run in deterministic mode (the mode of tests/test_model_gpu.py); restored afterwards."""
-    was = univl_amd.deterministic()
-    univl_amd.set_deterministic(True)
-    yield
-    univl_amd.set_deterministic(was)
-
-
-def _batches(cfg, sizes, seed):
-    import univl_oracle as O
-    out = []
-    for n, b in enumerate(sizes):
-        bt = O.synthetic_batch(cfg, b, seed=seed + n)
-        out.append({k: bt[k].to(DEV) for k in ("input_ids", "attention_mask", "token_type_ids", "video", "video_mask")})
-    return out
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_single_modality_outputs_equal_the_halves_of_the_joint_call(dtype, deterministic_models):
     from test_model_gpu import GATES

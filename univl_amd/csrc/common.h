@@ -49,6 +49,10 @@ void univl_set_error(const char* fmt, ...);
     } while (0)
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// THE rule for a 768-wide fp32 row operand (q, g, bank, frames of retrieve.hip and moment.hip, read 16 bytes at a time): rows at least
+// 768 floats apart, and every row 16-byte aligned.  The entry points word the refusals; these are the conditions.
+static inline bool rows768_pitch(int64_t ld) { return ld >= 768; }
+static inline bool rows768_aligned(const void* p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
 
 // ------------------------------------------------------------------------------------------- devices
 // Entry points take the DEVICE FROM THEIR STREAM ARGUMENT (hipStreamGetDevice), never from the calling thread's

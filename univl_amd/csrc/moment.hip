@@ -168,15 +168,16 @@ __global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
     }
 }
 
-// the checks both entry points share: the gallery side of the descriptor
+// the checks both entry points share: the descriptor itself and its gallery side
 int check_gallery(const char* who, const UnivlMoment* d) {
+    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
     UNIVL_CHECK_ARG(d->H == MM_H, UNIVL_EINVAL, "%s: H=%d (must be 768)", who, d->H);
     UNIVL_CHECK_ARG(d->F >= 1 && d->F <= UNIVL_MOMENT_F_MAX, UNIVL_EINVAL, "%s: F=%d (1 <= F <= %d)", who, d->F, UNIVL_MOMENT_F_MAX);
     UNIVL_CHECK_ARG(d->N >= 1 && d->N <= INT_MAX / 16, UNIVL_EINVAL, "%s: N=%d (>= 1)", who, d->N);
     UNIVL_CHECK_ARG(d->normalize == 0 || d->normalize == 1, UNIVL_EINVAL, "%s: normalize=%d (0 or 1)", who, d->normalize);
     UNIVL_CHECK_ARG(d->frames && d->mask, UNIVL_EINVAL, "%s: null pointer (frames, mask)", who);
     UNIVL_CHECK_ARG(d->ld_row >= (int64_t)d->F * MM_H, UNIVL_EINVAL, "%s: ld_row=%lld (>= F * 768)", who, (long long)d->ld_row);
-    UNIVL_CHECK_ARG(aligned16(d->frames) && d->ld_row % 4 == 0, UNIVL_EALIGN, "%s: rows of frames must be 16-byte aligned", who);
+    UNIVL_CHECK_ARG(rows768_aligned(d->frames, d->ld_row), UNIVL_EALIGN, "%s: rows of frames must be 16-byte aligned", who);
     return UNIVL_OK;
 }
 
@@ -186,7 +187,6 @@ extern "C" int univl_moment_sizeof(void) { return (int)sizeof(UnivlMoment); }
 
 extern "C" int univl_window_norms(const UnivlMoment* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_window_norms: null descriptor");
     const int rc = check_gallery("univl_window_norms", d);
     if (rc != UNIVL_OK) return rc;
     UNIVL_CHECK_ARG(d->wnorm != nullptr, UNIVL_EINVAL, "univl_window_norms: null pointer (wnorm)");
@@ -199,7 +199,6 @@ extern "C" int univl_window_norms(const UnivlMoment* d, hipStream_t stream) {
 
 extern "C" int univl_moment_localize(const UnivlMoment* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_moment_localize: null descriptor");
     const int rc = check_gallery("univl_moment_localize", d);
     if (rc != UNIVL_OK) return rc;
     const char* who = "univl_moment_localize";
@@ -209,8 +208,8 @@ extern "C" int univl_moment_localize(const UnivlMoment* d, hipStream_t stream) {
                     d->Nq, d->K);
     UNIVL_CHECK_ARG(d->q && d->rows && d->start && d->length && d->score, UNIVL_EINVAL, "%s: null pointer (q, rows, start, length, score)", who);
     UNIVL_CHECK_ARG(!d->normalize || d->wnorm != nullptr, UNIVL_EINVAL, "%s: null pointer (wnorm with normalize)", who);
-    UNIVL_CHECK_ARG(d->ldq >= MM_H, UNIVL_EINVAL, "%s: ldq=%lld (>= 768)", who, (long long)d->ldq);
-    UNIVL_CHECK_ARG(aligned16(d->q) && d->ldq % 4 == 0, UNIVL_EALIGN, "%s: rows of q must be 16-byte aligned", who);
+    UNIVL_CHECK_ARG(rows768_pitch(d->ldq), UNIVL_EINVAL, "%s: ldq=%lld (>= 768)", who, (long long)d->ldq);
+    UNIVL_CHECK_ARG(rows768_aligned(d->q, d->ldq), UNIVL_EALIGN, "%s: rows of q must be 16-byte aligned", who);
     LocArgs a;
     a.q = d->q; a.ldq = (long)d->ldq; a.frames = d->frames; a.ld_row = (long)d->ld_row; a.mask = d->mask; a.wnorm = d->wnorm; a.rows = d->rows;
     a.N = d->N; a.F = d->F; a.K = d->K; a.lmin = d->lmin; a.lmax = d->lmax; a.normalize = d->normalize;

@@ -219,6 +219,10 @@ __global__ __launch_bounds__(64) void sim_topk_merge_kernel(const float* __restr
     }
 }
 
+// tiles per slice, then the slices that leaves, for `want` slices of `tiles` tiles: no empty slice, one tile each where want > tiles
+void slice_plan(int tiles, int want, int& tps, int& S) { tps = (tiles + want - 1) / want; S = (tiles + tps - 1) / tps; }
+bool rows_ok(int n) { return n >= 1 && n <= INT_MAX - 2 * RT_TILE; }     // the scans index up to two tiles past the last row, in int
+
 struct Plan { int nqb, qtiles, tiles, tps, S; };
 
 Plan make_plan(int Nq, int Ng, int slices) {
@@ -229,9 +233,7 @@ Plan make_plan(int Nq, int Ng, int slices) {
     // automatic: query tiles x slices fills the chip once -- a workgroup owns a compute unit's LDS, so a second round would only queue
     int want = slices > 0 ? slices : (RT_WGS + p.qtiles - 1) / p.qtiles;
     want = want > UNIVL_TOPK_SLICES_MAX ? UNIVL_TOPK_SLICES_MAX : want;
-    want = want > p.tiles ? p.tiles : want;
-    p.tps = (p.tiles + want - 1) / want;
-    p.S = (p.tiles + p.tps - 1) / p.tps;                              // no empty slice
+    slice_plan(p.tiles, want, p.tps, p.S);
     return p;
 }
 
@@ -248,7 +250,7 @@ void launch_scan(const ScanArgs& a, const Plan& p, hipStream_t stream) {
 template <bool NORM>
 int sim_topk_run(const char* who, const UnivlSimTopk* d, const float* bias, const int32_t* gate, hipStream_t stream) {
     UNIVL_CHECK_ARG(d->H == RT_H, UNIVL_EINVAL, "%s: H=%d (must be 768)", who, d->H);
-    UNIVL_CHECK_ARG(d->Nq >= 1 && d->Ng >= 1 && d->Ng <= INT_MAX - 2 * RT_TILE, UNIVL_EINVAL, "%s: Nq=%d Ng=%d (both >= 1)", who, d->Nq, d->Ng);
+    UNIVL_CHECK_ARG(d->Nq >= 1 && rows_ok(d->Ng), UNIVL_EINVAL, "%s: Nq=%d Ng=%d (both >= 1)", who, d->Nq, d->Ng);
     UNIVL_CHECK_ARG(d->k >= 0 && d->k <= UNIVL_TOPK_MAX, UNIVL_EINVAL, "%s: k=%d (0 <= k <= %d)", who, d->k, UNIVL_TOPK_MAX);
     UNIVL_CHECK_ARG(d->k > 0 || d->target != nullptr, UNIVL_EINVAL, "%s: k = 0 asks for the rank counts only and needs target", who);
     UNIVL_CHECK_ARG(d->slices >= 0 && d->slices <= UNIVL_TOPK_SLICES_MAX, UNIVL_EINVAL, "%s: slices=%d (0 = automatic, at most %d)", who,
@@ -257,12 +259,12 @@ int sim_topk_run(const char* who, const UnivlSimTopk* d, const float* bias, cons
     UNIVL_CHECK_ARG(!NORM || bias != nullptr, UNIVL_EINVAL, "%s: null pointer (col_bias)", who);
     UNIVL_CHECK_ARG(d->k == 0 || (d->idx && d->score), UNIVL_EINVAL, "%s: null pointer (idx, score)", who);
     UNIVL_CHECK_ARG(d->target == nullptr || (d->gt && d->eq), UNIVL_EINVAL, "%s: null pointer (gt, eq with target)", who);
-    UNIVL_CHECK_ARG(d->ldq >= RT_H && d->ldg >= RT_H, UNIVL_EINVAL, "%s: ldq=%lld ldg=%lld (both >= 768)", who, (long long)d->ldq,
+    UNIVL_CHECK_ARG(rows768_pitch(d->ldq) && rows768_pitch(d->ldg), UNIVL_EINVAL, "%s: ldq=%lld ldg=%lld (both >= 768)", who, (long long)d->ldq,
                     (long long)d->ldg);
-    UNIVL_CHECK_ARG(aligned16(d->q) && aligned16(d->g) && d->ldq % 4 == 0 && d->ldg % 4 == 0 && aligned16(d->ws), UNIVL_EALIGN,
+    UNIVL_CHECK_ARG(rows768_aligned(d->q, d->ldq) && rows768_aligned(d->g, d->ldg) && aligned16(d->ws), UNIVL_EALIGN,
                     "%s: rows of q and g and the workspace must be 16-byte aligned", who);
     const Plan p = make_plan(d->Nq, d->Ng, d->slices);
-    const int64_t need = (int64_t)d->Nq * p.S * (8 * (int64_t)d->k + 8);
+    const int64_t need = univl_sim_topk_workspace(d->Nq, d->Ng, d->k, d->slices);       // THE formula; its own refusals are the checks above
     UNIVL_CHECK_ARG(d->ws_bytes >= need, UNIVL_EINVAL, "%s: workspace of %lld bytes needed (univl_sim_topk_workspace), got %lld", who,
                     (long long)need, (long long)d->ws_bytes);
     ScanArgs a;
@@ -396,8 +398,7 @@ ColPlan make_col_plan(int Nb, int Ng) {
     ColPlan p;
     p.gtiles = (Ng + CS_QT - 1) / CS_QT;
     p.tiles = (Nb + RT_TILE - 1) / RT_TILE;
-    p.tps = (p.tiles + UNIVL_COLSTAT_SLICES - 1) / UNIVL_COLSTAT_SLICES;
-    p.S = (p.tiles + p.tps - 1) / p.tps;                              // no empty slice
+    slice_plan(p.tiles, UNIVL_COLSTAT_SLICES, p.tps, p.S);
     return p;
 }
 
@@ -419,12 +420,11 @@ __global__ __launch_bounds__(256) void hub_gate_kernel(const int32_t* __restrict
 }  // namespace
 
 extern "C" int64_t univl_sim_topk_workspace(int32_t Nq, int32_t Ng, int32_t k, int32_t slices) {
-    if (Nq < 1 || Ng < 1 || k < 0 || k > UNIVL_TOPK_MAX || slices < 0 || slices > UNIVL_TOPK_SLICES_MAX || Ng > INT_MAX - 2 * RT_TILE) {
+    if (Nq < 1 || !rows_ok(Ng) || k < 0 || k > UNIVL_TOPK_MAX || slices < 0 || slices > UNIVL_TOPK_SLICES_MAX) {
         univl_set_error("univl_sim_topk_workspace: Nq=%d Ng=%d k=%d slices=%d", Nq, Ng, k, slices);
         return UNIVL_EINVAL;
     }
-    const Plan p = make_plan(Nq, Ng, slices);
-    return (int64_t)Nq * p.S * (8 * (int64_t)k + 8);
+    return (int64_t)Nq * make_plan(Nq, Ng, slices).S * (8 * (int64_t)k + 8);       // [Nq][S] slots: k values, k indices, two counts
 }
 
 extern "C" int univl_sim_topk(const UnivlSimTopk* d, hipStream_t stream) {
@@ -448,7 +448,7 @@ extern "C" int univl_sim_topk_norm(const UnivlSimTopkNorm* d, hipStream_t stream
 extern "C" int univl_sim_colstat_sizeof(void) { return (int)sizeof(UnivlSimColstat); }
 
 extern "C" int64_t univl_sim_colstat_workspace(int32_t Nb, int32_t Ng) {
-    if (Nb < 1 || Ng < 1 || Nb > INT_MAX - 2 * RT_TILE || Ng > INT_MAX - 2 * RT_TILE) {
+    if (!rows_ok(Nb) || !rows_ok(Ng)) {
         univl_set_error("univl_sim_colstat_workspace: Nb=%d Ng=%d", Nb, Ng);
         return UNIVL_EINVAL;
     }
@@ -459,16 +459,15 @@ extern "C" int univl_sim_colstat(const UnivlSimColstat* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
     UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "univl_sim_colstat: null descriptor");
     UNIVL_CHECK_ARG(d->H == RT_H, UNIVL_EINVAL, "univl_sim_colstat: H=%d (must be 768)", d->H);
-    UNIVL_CHECK_ARG(d->Nb >= 1 && d->Ng >= 1 && d->Nb <= INT_MAX - 2 * RT_TILE && d->Ng <= INT_MAX - 2 * RT_TILE, UNIVL_EINVAL,
-                    "univl_sim_colstat: Nb=%d Ng=%d (both >= 1)", d->Nb, d->Ng);
+    UNIVL_CHECK_ARG(rows_ok(d->Nb) && rows_ok(d->Ng), UNIVL_EINVAL, "univl_sim_colstat: Nb=%d Ng=%d (both >= 1)", d->Nb, d->Ng);
     UNIVL_CHECK_ARG(d->beta > 0.f && d->beta <= FLT_MAX, UNIVL_EINVAL, "univl_sim_colstat: beta=%g (finite, > 0)", (double)d->beta);
     UNIVL_CHECK_ARG(d->bank && d->g && d->c && d->ws, UNIVL_EINVAL, "univl_sim_colstat: null pointer (bank, g, c, ws)");
-    UNIVL_CHECK_ARG(d->ldb >= RT_H && d->ldg >= RT_H, UNIVL_EINVAL, "univl_sim_colstat: ldb=%lld ldg=%lld (both >= 768)", (long long)d->ldb,
-                    (long long)d->ldg);
-    UNIVL_CHECK_ARG(aligned16(d->bank) && aligned16(d->g) && d->ldb % 4 == 0 && d->ldg % 4 == 0 && aligned16(d->ws), UNIVL_EALIGN,
+    UNIVL_CHECK_ARG(rows768_pitch(d->ldb) && rows768_pitch(d->ldg), UNIVL_EINVAL, "univl_sim_colstat: ldb=%lld ldg=%lld (both >= 768)",
+                    (long long)d->ldb, (long long)d->ldg);
+    UNIVL_CHECK_ARG(rows768_aligned(d->bank, d->ldb) && rows768_aligned(d->g, d->ldg) && aligned16(d->ws), UNIVL_EALIGN,
                     "univl_sim_colstat: rows of bank and g and the workspace must be 16-byte aligned");
     const ColPlan p = make_col_plan(d->Nb, d->Ng);
-    const int64_t need = 8 * (int64_t)p.S * d->Ng;
+    const int64_t need = univl_sim_colstat_workspace(d->Nb, d->Ng);                       // THE formula; its own refusals are the checks above
     UNIVL_CHECK_ARG(d->ws_bytes >= need, UNIVL_EINVAL, "univl_sim_colstat: workspace of %lld bytes needed (univl_sim_colstat_workspace), got %lld",
                     (long long)need, (long long)d->ws_bytes);
     ColArgs a;

@@ -17,6 +17,7 @@ session (univl_amd.score.CaptionScorer).
 
 Localisation: eval_localization scores where in its own video every text is found (retrieval.VideoIndex.localize) against annotated
 segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices."""
+import contextlib
 import math
 import os
 
@@ -49,19 +50,43 @@ def similarity_matrix(model, masks_t, masks_v, seq_outs, vis_outs):
 def eval_retrieval(model, batches, device="cuda"):
     """batches: iterable of (input_ids, input_mask, segment_ids, video, video_mask, ...) tuples in the reference
     loader's order (main_task_retrieval.py:396).  Returns (metrics dict, similarity matrix on the device)."""
+    masks_t, masks_v, seqs, viss = [], [], [], []
+    with _eval_mode(model):
+        for batch in batches:
+            input_ids, input_mask, segment_ids, video, video_mask = [t.to(device) for t in batch[:5]]
+            so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
+            seqs.append(so)
+            viss.append(vo)
+            masks_t.append(input_mask.reshape(-1, input_mask.shape[-1]))
+            masks_v.append(video_mask.reshape(-1, video_mask.shape[-1]))
+        sim = similarity_matrix(model, masks_t, masks_v, seqs, viss)
+    return compute_metrics(sim), sim
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """model.eval() for the block; model.training is put back however the block ends."""
     was_training = model.training
     model.eval()
-    masks_t, masks_v, seqs, viss = [], [], [], []
-    for batch in batches:
-        input_ids, input_mask, segment_ids, video, video_mask = [t.to(device) for t in batch[:5]]
-        so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
-        seqs.append(so)
-        viss.append(vo)
-        masks_t.append(input_mask.reshape(-1, input_mask.shape[-1]))
-        masks_v.append(video_mask.reshape(-1, video_mask.shape[-1]))
-    sim = similarity_matrix(model, masks_t, masks_v, seqs, viss)
-    model.train(was_training)
-    return compute_metrics(sim), sim
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def _text_rows(who, text_batches, n, device):
+    """The walk both target-per-text evaluators make: yields (input_ids, segment_ids, input_mask, row, b) for every text batch moved to
+    `device`, row the batch's first text row and b its rows.  ValueError, in `who`'s name, when the batches hold more or fewer than n rows."""
+    row = 0
+    for batch in text_batches:
+        input_ids, input_mask, segment_ids = [t.to(device) for t in batch[:3]]
+        b = input_ids.numel() // input_ids.shape[-1]
+        if row + b > n:
+            raise ValueError("%s: more text rows than targets (%d)" % (who, n))
+        yield input_ids, segment_ids, input_mask, row, b
+        row += b
+    if row != n:
+        raise ValueError("%s: %d text rows for %d targets" % (who, row, n))
 
 
 @torch.no_grad()
@@ -78,9 +103,7 @@ def eval_retrieval_streamed(model, text_batches, video_batches, targets, device=
     from .retrieval import QueryBank, VideoIndex, check_bank_args
     if bank_batches is not None:
         check_bank_args(beta, hub_k)
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         index = VideoIndex(model, capacity=capacity)
         for video, video_mask in video_batches:
             index.add(video.to(device), video_mask.to(device))
@@ -94,20 +117,11 @@ def eval_retrieval_streamed(model, text_batches, video_batches, targets, device=
         targets = torch.as_tensor(targets).reshape(-1).to(device=device, dtype=torch.int32)
         if targets.numel() and (int(targets.min()) < 0 or int(targets.max()) >= len(index)):
             raise ValueError("eval_retrieval_streamed: targets must lie in [0, %d)" % len(index))
-        gts, eqs, row = [], [], 0
-        for batch in text_batches:
-            input_ids, input_mask, segment_ids = [t.to(device) for t in batch[:3]]
-            n = input_ids.numel() // input_ids.shape[-1]
-            if row + n > targets.numel():
-                raise ValueError("eval_retrieval_streamed: more text rows than targets (%d)" % targets.numel())
-            gt, eq = index.search(input_ids, segment_ids, input_mask, k=0, targets=targets[row:row + n], bank=bank)
+        gts, eqs = [], []
+        for input_ids, segment_ids, input_mask, row, b in _text_rows("eval_retrieval_streamed", text_batches, targets.numel(), device):
+            gt, eq = index.search(input_ids, segment_ids, input_mask, k=0, targets=targets[row:row + b], bank=bank)
             gts.append(gt)
             eqs.append(eq)
-            row += n
-        if row != targets.numel():
-            raise ValueError("eval_retrieval_streamed: %d text rows for %d targets" % (row, targets.numel()))
-    finally:
-        model.train(was_training)
     gt, eq = torch.cat(gts).cpu().numpy(), torch.cat(eqs).cpu().numpy()
     return compute_metrics((gt, eq)), (gt, eq)
 
@@ -130,23 +144,12 @@ def eval_localization(model, index, text_batches, targets, gt_start, gt_len, win
         raise ValueError("eval_localization: %d targets, %d gt_start, %d gt_len" % (n, gt_start.numel(), gt_len.numel()))
     if n and (int(targets.min()) < 0 or int(targets.max()) >= len(index) or int(gt_len.min()) < 1 or int(gt_start.min()) < 0):
         raise ValueError("eval_localization: targets must lie in [0, %d), gt_start >= 0 and gt_len >= 1" % len(index))
-    was_training = model.training
-    model.eval()
-    try:
-        starts, lengths, row = [], [], 0
-        for batch in text_batches:
-            input_ids, input_mask, segment_ids = [t.to(device) for t in batch[:3]]
-            b = input_ids.numel() // input_ids.shape[-1]
-            if row + b > n:
-                raise ValueError("eval_localization: more text rows than targets (%d)" % n)
+    starts, lengths = [], []
+    with _eval_mode(model):
+        for input_ids, segment_ids, input_mask, row, b in _text_rows("eval_localization", text_batches, n, device):
             s, l, _ = index.localize(input_ids, segment_ids, input_mask, targets[row:row + b].reshape(b, 1), window)
             starts.append(s.reshape(-1))
             lengths.append(l.reshape(-1))
-            row += b
-        if row != n:
-            raise ValueError("eval_localization: %d text rows for %d targets" % (row, n))
-    finally:
-        model.train(was_training)
     if n == 0:
         raise ValueError("eval_localization: no texts")
     s, l = torch.cat(starts), torch.cat(lengths)                          # an empty result is (-1, 0): it meets no frame
@@ -227,10 +230,8 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
     if model._stage_one:
         return CaptionEvalResult([], [], [], torch.zeros(0, n_best), torch.zeros(0, dtype=torch.int32), None, None)
     bos, eos, pad = tokenizer.vocab["[CLS]"], tokenizer.vocab["[SEP]"], tokenizer.vocab["[PAD]"]
-    was_training = model.training
-    model.eval()
     hyps, refs, hyp_ids, scores, lengths = [], [], [], [], []
-    try:
+    with _eval_mode(model):
         for batch in batches:
             input_ids, input_mask, segment_ids, video, video_mask = [t.to(device, non_blocking=True) for t in batch[:5]]
             so, vo = model.get_sequence_visual_output(input_ids, segment_ids, input_mask, video, video_mask)
@@ -256,8 +257,6 @@ def eval_caption(model, batches, tokenizer, *, n_bm=5, n_best=1, max_len=None, s
             truth = batch[11]
             for row in truth.reshape(-1, truth.shape[-1]).cpu().tolist():
                 refs.append(ids_to_caption(tokenizer, row))
-    finally:
-        model.train(was_training)
     if output_dir is not None:
         with open(os.path.join(output_dir, "hyp.txt"), "w", encoding="utf-8") as writer:
             for txt in hyps:
@@ -306,10 +305,8 @@ def eval_caption_loss(model, batches, *, session=None, device="cuda"):
     from .score import CaptionScorer
     if model._stage_one:
         return CaptionLossResult([], [], [], None)
-    was_training = model.training
-    model.eval()
     packed = []
-    try:
+    with _eval_mode(model):
         for batch in batches:
             input_ids, input_mask, segment_ids, video, video_mask = [t.to(device, non_blocking=True) for t in batch[:5]]
             cap_in, cap_mask, cap_out = [t.to(device, non_blocking=True) for t in batch[9:12]]
@@ -331,8 +328,6 @@ def eval_caption_loss(model, batches, *, session=None, device="cuda"):
             # the one host copy of the batch: three words per item (the int32 counts travel as their bit patterns)
             packed.append(torch.stack([r.seq_logprob.reshape(-1), r.seq_tokens.reshape(-1).view(torch.float32),
                                        r.seq_correct.reshape(-1).view(torch.float32)]).cpu())
-    finally:
-        model.train(was_training)
     if not packed:
         return CaptionLossResult([], [], [], session)
     host = torch.cat(packed, dim=1)

@@ -42,6 +42,23 @@ def _ld(t):
     return t.stride(0)
 
 
+def _row_views(*ts):          # q, g, bank of the retrieval entry points; width, row stride and alignment are the library's to refuse
+    assert all(t.dtype == torch.float32 and t.dim() == 2 for t in ts)
+
+
+def _workspace(d, need, dev):
+    """d.ws / d.ws_bytes: a fresh workspace of `need` bytes (a query's refusal, < 0, gets the least one), alive as long as d is."""
+    d._ws_tensor = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+    d.ws, d.ws_bytes = _p(d._ws_tensor), d._ws_tensor.numel()
+
+
+def _status_word(status, dev):
+    """The optional status argument: the caller's int32 word, or a fresh zero."""
+    status = torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+    assert status.dtype == torch.int32 and status.numel() == 1
+    return status
+
+
 def probe_layouts():
     out = torch.zeros(1792, device="cuda", dtype=torch.float32)
     _lib.check(_lib.lib().univl_probe_layouts(_p(out), 1792, _stream()), "probe_layouts")
@@ -572,7 +589,7 @@ def caption_overlap(sym, length, hyp_row, ref_begin, ref_rows, n_refs, *, tables
                hyp_len=torch.empty(items, dtype=torch.int32, device=dev), ref_len=torch.empty(items, dtype=torch.int32, device=dev),
                lcs=torch.zeros(int(n_refs), dtype=torch.int32, device=dev), rouge_l=torch.empty(items, dtype=torch.float64, device=dev),
                cider=None, bleu=torch.empty(items, dtype=torch.float64, device=dev) if bleu else None,
-               status=torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status)
+               status=_status_word(status, dev))
     if tables is not None:
         df_keys, df_cnt, df_begin, n_docs = tables
         _require_gpu(df_keys, df_cnt)
@@ -582,7 +599,6 @@ def caption_overlap(sym, length, hyp_row, ref_begin, ref_rows, n_refs, *, tables
         for n in range(5):
             d.df_begin[n] = int(df_begin[n])
         out["cider"] = torch.empty(items, dtype=torch.float64, device=dev)
-    assert out["status"].dtype == torch.int32 and out["status"].numel() == 1
     d.guess, d.correct, d.hyp_len, d.ref_len, d.lcs = (_p(out[k]) for k in ("guess", "correct", "hyp_len", "ref_len", "lcs"))
     d.rouge_l, d.cider, d.bleu, d.status = _p(out["rouge_l"]), _p(out["cider"]), _p(out["bleu"]), _p(out["status"])
     _lib.check(_lib.lib().univl_caption_overlap(_BYREF(d), _stream()), "caption_overlap")
@@ -604,19 +620,15 @@ def ngram_df(sym, length, ref_begin, ref_rows, n_refs, *, capacity=None, status=
         assert h.dtype == torch.int32 and h.is_contiguous() and h.numel() == n
     if capacity is None:
         capacity = n_refs * 4 * T
-    need = int(_lib.lib().univl_ngram_df_ws_bytes(n_refs, T))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     df_keys = torch.empty(max(int(capacity), 0), dtype=torch.int64, device=dev)
     df_cnt = torch.empty(max(int(capacity), 0), dtype=torch.int32, device=dev)
     df_begin = torch.empty(5, dtype=torch.int32, device=dev)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    assert status.dtype == torch.int32 and status.numel() == 1
+    status = _status_word(status, dev)
     d = _lib.NgramDf()
     d.sym, d.ld, d.len, d.rows, d.T, d.items, d.n_refs = _p(sym), sym.stride(0), _p(length), rows, T, items, n_refs
     d.ref_begin, d.ref_rows = _p(ref_begin), _p(ref_rows)
     d.df_keys, d.df_cnt, d.df_begin, d.status, d.capacity = _p(df_keys), _p(df_cnt), _p(df_begin), _p(status), int(capacity)
-    d.ws, d.ws_bytes = _p(ws), ws.numel()
+    _workspace(d, _lib.lib().univl_ngram_df_ws_bytes(n_refs, T), dev)
     _lib.check(_lib.lib().univl_ngram_df(_BYREF(d), _stream()), "ngram_df")      # refuses what the workspace query refused, with its message
     return df_keys, df_cnt, df_begin, status
 
@@ -642,9 +654,7 @@ def caption_advantage(reward, baseline=None, scale=1.0, status=None):
     n, ns = reward.shape
     assert baseline is None or (baseline.dtype == torch.float64 and baseline.is_contiguous() and baseline.numel() == n)
     weight = torch.empty(n, ns, dtype=torch.float32, device=reward.device)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=reward.device)
-    assert status.dtype == torch.int32 and status.numel() == 1
+    status = _status_word(status, reward.device)
     _lib.check(_lib.lib().univl_caption_advantage(_p(reward), _p(baseline), n, ns, _lib.ADV_LOO if baseline is None else _lib.ADV_GIVEN,
                                                   float(scale), _p(weight), _p(status), _stream()), "caption_advantage")
     return weight, status
@@ -706,15 +716,13 @@ def sim_topk(q, g, k, *, target=None, slices=0):
 def _sim_topk(d, what, q, g, k, target, slices):
     """sim_topk and sim_topk_norm: d is the descriptor (SimTopk's fields; the caller has set the ones past them), what the entry point."""
     _require_gpu(q, g, target)
-    assert q.dtype == torch.float32 and g.dtype == torch.float32 and q.dim() == 2 and g.dim() == 2
+    _row_views(q, g)
     d.q, d.ldq, d.g, d.ldg = _p(q), _ld(q), _p(g), _ld(g)
     d.Nq, d.Ng, d.H, d.k, d.slices = q.shape[0], g.shape[0], q.shape[1], int(k), int(slices)
     if g.shape[1] != q.shape[1]:
         raise RuntimeError("%s: q is %d wide, g %d" % (what, q.shape[1], g.shape[1]))
     dev = q.device
-    need = _lib.lib().univl_sim_topk_workspace(d.Nq, d.Ng, d.k, d.slices)
-    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
-    d.ws, d.ws_bytes = _p(ws), ws.numel()
+    _workspace(d, _lib.lib().univl_sim_topk_workspace(d.Nq, d.Ng, d.k, d.slices), dev)
     idx = score = gt = eq = None
     if d.k > 0:
         idx = torch.empty(d.Nq, d.k, dtype=torch.int32, device=dev)
@@ -748,7 +756,7 @@ def sim_colstat(bank, g, beta=20.0, *, out=None):
     the [Nb, Ng] matrix (include/univl_hip.h: univl_sim_colstat).  bank: [Nb, 768], g: [Ng, 768] fp32 row-major views as sim_topk's;
     beta: finite, > 0; out: optional [Ng] fp32 to write.  Returns c [Ng] fp32."""
     _require_gpu(bank, g, out)
-    assert bank.dtype == torch.float32 and g.dtype == torch.float32 and bank.dim() == 2 and g.dim() == 2
+    _row_views(bank, g)
     if g.shape[1] != bank.shape[1]:
         raise RuntimeError("sim_colstat: bank is %d wide, g %d" % (bank.shape[1], g.shape[1]))
     d = _lib.SimColstat()
@@ -756,9 +764,8 @@ def sim_colstat(bank, g, beta=20.0, *, out=None):
     d.Nb, d.Ng, d.H, d.beta = bank.shape[0], g.shape[0], bank.shape[1], float(beta)
     c = torch.empty(d.Ng, dtype=torch.float32, device=g.device) if out is None else out
     assert c.dtype == torch.float32 and c.numel() == d.Ng and c.is_contiguous()
-    need = _lib.lib().univl_sim_colstat_workspace(d.Nb, d.Ng)
-    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=g.device)
-    d.c, d.ws, d.ws_bytes = _p(c), _p(ws), ws.numel()
+    d.c = _p(c)
+    _workspace(d, _lib.lib().univl_sim_colstat_workspace(d.Nb, d.Ng), g.device)
     _lib.check(_lib.lib().univl_sim_colstat(_BYREF(d), _stream()), "sim_colstat")
     return c
 
@@ -820,7 +827,7 @@ def moment_localize(q, frames, mask, rows, lmin, lmax, *, wnorm=None, normalize=
     outside the gallery (the -1 of sim_topk)."""
     d = _moment_gallery(frames, mask, normalize)
     _require_gpu(q, rows, wnorm)
-    assert q.dtype == torch.float32 and q.dim() == 2
+    _row_views(q)
     assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == q.shape[0] and rows.is_contiguous()
     if q.shape[1] != frames.shape[2]:
         raise RuntimeError("moment_localize: q is %d wide, the frames %d" % (q.shape[1], frames.shape[2]))

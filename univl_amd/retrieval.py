@@ -55,28 +55,19 @@ class VideoIndex:
 
     def _reserve(self, extra, F=None):
         """Room for `extra` more rows; growth copies the filled rows on the device."""
-        dev, cap = self._device(), self._cap
-        while self._n + extra > cap:
+        dev, cap, n = self._device(), self._cap, self._n
+        while n + extra > cap:
             cap *= 2
         if self._buf is None or cap != self._cap:
-            new = torch.empty(cap, H, device=dev, dtype=torch.float32)
-            if self._buf is not None:
-                new[:self._n].copy_(self._buf[:self._n])
-            self._buf = new
+            self._buf = _grown(self._buf, n, cap, H, device=dev)
         if self.keep_frames and F is not None:
             if self._frames is not None and self._frames.shape[1] != F:
                 raise ValueError("VideoIndex: videos of %d frames in an index of %d-frame videos" % (F, self._frames.shape[1]))
             if self._frames is None or self._frames.shape[0] != cap:
-                frames = torch.empty(cap, F, H, device=dev, dtype=torch.float32)
-                fmask = torch.zeros(cap, F, device=dev, dtype=torch.int64)
-                if self._frames is not None:
-                    frames[:self._n].copy_(self._frames[:self._n])
-                    fmask[:self._n].copy_(self._fmask[:self._n])
-                self._frames, self._fmask = frames, fmask
+                self._frames = _grown(self._frames, n, cap, F, H, device=dev)
+                self._fmask = _grown(self._fmask, n, cap, F, device=dev, dtype=torch.int64, zero=True)
                 if self._wnorm is not None:
-                    wnorm = torch.empty(cap, F, F, device=dev, dtype=torch.float32)
-                    wnorm[:self._wnorm_rows].copy_(self._wnorm[:self._wnorm_rows])
-                    self._wnorm = wnorm
+                    self._wnorm = _grown(self._wnorm, self._wnorm_rows, cap, F, F, device=dev)
         self._cap = cap
         return self._buf
 
@@ -145,9 +136,7 @@ class VideoIndex:
             raise ValueError("VideoIndex: the index is empty")
         if bank is not None:
             bank.check_fitted(self)
-        q = q.reshape(-1, H).to(torch.float32)
-        if q.stride(1) != 1 or q.stride(0) % 4 or q.data_ptr() % 16:
-            q = q.contiguous()
+        q = _query_rows(q)
         if targets is not None:
             targets = torch.as_tensor(targets).reshape(-1).to(device=q.device, dtype=torch.int32).contiguous()
         if bank is None:
@@ -181,10 +170,8 @@ class VideoIndex:
             feats.amask.copy_(am[lo:lo + n])
             ses.plan.run()
             cross[lo:lo + n].copy_(ses.head.sim.view(n, K))
-        # each row by descending cross score, equal scores by lower row id first: ids ascending, then a stable sort by score
-        ids, perm = torch.sort(idx.long(), dim=1, stable=True)
-        sc, perm2 = torch.sort(cross.gather(1, perm), dim=1, descending=True, stable=True)
-        return sc, ids.gather(1, perm2).to(torch.int32)
+        sc, order = _rank_rows(cross, idx)                # k <= len(index): no empty slot among the candidates
+        return sc, idx.gather(1, order)
 
     # ------------------------------------------------------------------------------------------ moment search
     def _window_norms(self):
@@ -192,7 +179,7 @@ class VideoIndex:
         since the last call are computed and the others kept.  Allocated by the first localisation of a normalising model."""
         F = self._frames.shape[1]
         if self._wnorm is None:
-            self._wnorm = torch.empty(self._cap, F, F, device=self._device(), dtype=torch.float32)
+            self._wnorm = _grown(None, 0, self._cap, F, F, device=self._device())
         lo, n = self._wnorm_rows, self._n
         if lo < n:
             ops.window_norms(self._frames[lo:n], self._fmask[lo:n], out=self._wnorm[lo:n])
@@ -219,9 +206,7 @@ class VideoIndex:
             raise ValueError("VideoIndex.localize: window=(%d, %d), need 1 <= lmin <= lmax <= %d frames" % (lmin, lmax, F))
         if F > _lib.MOMENT_F_MAX:
             raise ValueError("VideoIndex.localize: videos of %d frames, at most %d" % (F, _lib.MOMENT_F_MAX))
-        q = q.reshape(-1, H).to(torch.float32)
-        if q.stride(1) != 1 or q.stride(0) % 4 or q.data_ptr() % 16:
-            q = q.contiguous()
+        q = _query_rows(q)
         rows = torch.as_tensor(rows).to(device=q.device, dtype=torch.int32).reshape(q.shape[0], -1).contiguous()
         wnorm = self._window_norms() if self.normalize else None
         return ops.moment_localize(q, self._frames[:self._n], self._fmask[:self._n], rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
@@ -244,11 +229,8 @@ class VideoIndex:
         q = self.pool_text(input_ids, token_type_ids, attention_mask)[0]
         _, idx = self.search_vectors(q, shortlist, None, bank)
         start, length, score = self.localize_vectors(q, idx, window)
-        # each row by descending window score, equal scores by lower row id first: ids ascending, then a stable sort by score (_rerank)
-        ids, perm = torch.sort(torch.where(idx < 0, torch.full_like(idx, _NO_ROW), idx).long(), dim=1, stable=True)
-        sc, perm2 = torch.sort(score.gather(1, perm), dim=1, descending=True, stable=True)
-        order = perm.gather(1, perm2)[:, :k]
-        return sc[:, :k].contiguous(), idx.gather(1, order), start.gather(1, order), length.gather(1, order)
+        sc, order = _rank_rows(score, idx, k)
+        return sc, idx.gather(1, order), start.gather(1, order), length.gather(1, order)
 
 
 class QueryBank:
@@ -312,10 +294,7 @@ class QueryBank:
             return self._n
         cap = 0 if self._buf is None else self._buf.shape[0]
         if self._n + b > cap:
-            new = torch.empty(max(2 * cap, self._n + b, 64), H, device=q.device, dtype=torch.float32)
-            if self._n:
-                new[:self._n].copy_(self._buf[:self._n])
-            self._buf = new
+            self._buf = _grown(self._buf, self._n, max(2 * cap, self._n + b, 64), H, device=q.device)
         self._buf[self._n:self._n + b].copy_(q)
         self._n += b
         self._invalidate()
@@ -334,19 +313,15 @@ class QueryBank:
             return self
         bank, piece = self.vectors, self.index.vectors[lo:n]
         if self._c is None or self._c.numel() < n:
-            c = torch.empty(max(n, self.index._cap), device=bank.device, dtype=torch.float32)
-            if lo:
-                c[:lo].copy_(self._c[:lo])
-            self._c = c
+            self._c = _grown(self._c, lo, max(n, self.index._cap), device=bank.device)
         ops.sim_colstat(bank, piece, self.beta, out=self._c[lo:n])
-        # every bank row's hub_k best (score, row): the piece's list, merged exactly with the one kept so far -- rows ascending, then
-        # a stable sort by descending score is the kernel's own order
+        # every bank row's hub_k best (score, row): the piece's list, merged exactly with the one kept so far (_rank_rows)
         score, idx = ops.sim_topk(bank, piece, self.hub_k)
         idx = torch.where(idx < 0, torch.full_like(idx, _NO_ROW), idx + lo)
         if lo:
-            idx, perm = torch.sort(torch.cat([self._top_idx, idx], 1), dim=1, stable=True)
-            score, perm2 = torch.sort(torch.cat([self._top_score, score], 1).gather(1, perm), dim=1, descending=True, stable=True)
-            score, idx = score[:, :self.hub_k].contiguous(), idx.gather(1, perm2)[:, :self.hub_k].contiguous()
+            both = torch.cat([self._top_idx, idx], 1)
+            score, order = _rank_rows(torch.cat([self._top_score, score], 1), both, self.hub_k)
+            idx = both.gather(1, order)
         self._top_score, self._top_idx = score, idx
         self._hub = ops.hub_flags(idx, n)                 # _NO_ROW lies outside every gallery: skipped
         self._covered = n
@@ -362,6 +337,30 @@ class QueryBank:
 
 
 _NO_ROW = 2 ** 31 - 1      # an empty slot of a best list (the -1 of ops.sim_topk), made to sort last
+
+
+def _rank_rows(score, idx, keep=None):
+    """THE ranking rule, the kernels' own order: every row of score / idx [rows, n] by descending score, equal scores by lower row id
+    first, empty slots (idx < 0 or _NO_ROW) last -- ids ascending, then a stable sort by score.  Returns (sorted scores, order), cut
+    to `keep` columns: order[i, j] is the column ranked j-th, to gather idx and its companions with.  Two lists merge by ranking both."""
+    ids, perm = torch.sort(torch.where(idx < 0, torch.full_like(idx, _NO_ROW), idx).long(), dim=1, stable=True)
+    sc, perm2 = torch.sort(score.gather(1, perm), dim=1, descending=True, stable=True)
+    return sc[:, :keep].contiguous(), perm.gather(1, perm2)[:, :keep]
+
+
+def _query_rows(q):
+    """[Nq, 768] fp32 query rows as the kernels read them: copied only where columns are strided or rows not 16-byte aligned."""
+    q = q.reshape(-1, H).to(torch.float32)
+    return q.contiguous() if q.stride(1) != 1 or q.stride(0) % 4 or q.data_ptr() % 16 else q
+
+
+def _grown(buf, filled, cap, *shape, device, dtype=torch.float32, zero=False):
+    """THE growth of a device row buffer: a new [cap, *shape] one with buf[:filled] copied on the device (buf None: nothing to copy)
+    and the rest unspecified, or zero with zero=True.  When to grow and to what capacity is the owner's policy."""
+    new = (torch.zeros if zero else torch.empty)(cap, *shape, device=device, dtype=dtype)
+    if buf is not None and filled:
+        new[:filled].copy_(buf[:filled])
+    return new
 
 
 def check_bank_args(beta, hub_k):
