@@ -907,6 +907,54 @@ typedef struct UnivlMoment {
 int univl_moment_sizeof(void);
 int univl_window_norms(const UnivlMoment* d, hipStream_t stream);
 int univl_moment_localize(const UnivlMoment* d, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- ordered step alignment
+ * WHERE every step of an ORDERED list of texts happens in a video (action step localisation; with lmin = lmax = 1 the dynamic
+ * programme of CrossTask: one frame per step, frames strictly increasing).  The gallery side -- frames, ld_row, mask, wnorm, N, F, H,
+ * normalize -- is UnivlMoment's, and so is the score of one window for one step vector.
+ * For list i (its counts[i] = n step vectors q[i, 0 .. n - 1]; K is only the padding of a list) and gallery row v = rows[i, c]:
+ *   alignment   n windows (s_k, L_k), k < n, each a candidate window of univl_moment_localize (lmin <= L_k <= lmax, every frame valid
+ *               by the mask), with s_k + L_k <= s_{k+1}: in order, never overlapping.  Gaps may hold anything, masked frames too
+ *   w_k         the score of (s_k, L_k) for q[i, k], bit for bit univl_moment_localize's: the numerator grown by extension over the
+ *               same frame products, divided by max(wnorm, 1e-12 L) or by L
+ *   total       T_n = 0, T_k = w_k + T_{k+1} in fp32, the total is T_0: summed from the last step to the first
+ *   result      the alignment of largest total.  EQUAL totals are decided by this suffix programme, which is the contract:
+ *                 A[k][s] = max over L of w(k, s, L) + G[k+1][s + L], lengths ascending, a later one only if strictly larger
+ *                 G[k][t] = max over s >= t of A[k][s],   G[n][.] = 0
+ *                 walk from k = 0, t = 0: s_k = the lowest s >= t with A[k][s] == G[k][t], L_k its length, t = s_k + L_k
+ *               i.e. the lexicographically smallest (s_0, L_0, s_1, L_1, ..) among the alignments whose every suffix total T_k is the
+ *               largest one from its frame on (where the sums are exact: among all alignments of equal total)
+ *   outputs     start, length (int32), score (fp32) [Nl, C, K]; total (fp32) [Nl, C].  Slots k >= n: (-1, 0, -inf).  No alignment
+ *               (ALL OR NOTHING): every slot (-1, 0, -inf), total -inf.  A row outside [0, N) or counts[i] outside [1, K]: the same,
+ *               decided for the whole workgroup before anything of the gallery or of q is read.  q rows k >= counts[i] are never read
+ * One workgroup of 256 threads per (list, candidate): the frame products d[k][f] = q_k . x_f into LDS (a wave keeps four frames in
+ * registers and walks the list's vectors: the row's frames are read once per pair), then for k = n - 1 .. 0 thread s < F grows start
+ * s's numerators, adds G[k+1][s + L] and keeps A[k][s] with its length; one wave turns A[k] into G[k] and the first start that
+ * attains it (a suffix scan in registers); one thread walks forward.  The [K, F, F] window scores are never stored.  LDS: 16 KB of
+ * products, 8 KB of lengths and first starts, 2 KB of A, G and the mask.  One launch, no host read, no atomics, capturable.
+ * PURITY: a pair's result is a function of its n vectors, the row's frames, mask and table rows, (lmin, lmax) and normalize only --
+ * not of its place in the launch, the other pairs, K, C or deterministic mode.  With n = 1 the triple and the total are
+ * univl_moment_localize's triple, bit for bit (the total up to the sign of a zero).
+ * Range: UnivlMoment's for the gallery side and (lmin, lmax); 1 <= K <= UNIVL_STEP_K_MAX, Nl >= 1, C >= 1, Nl * C < 2^31,
+ * ldq >= 768 (a list's vectors are ldq floats apart, lists K * ldq); otherwise, or for a NULL pointer, UNIVL_EINVAL; rows of frames
+ * and q 16-byte aligned (UNIVL_EALIGN).  Behaviour on NaN values: unspecified. */
+#define UNIVL_STEP_K_MAX 32
+typedef struct UnivlStepAlign {
+    const float* frames; int64_t ld_row; /* [N, F, 768] fp32 frames of the gallery rows, ld_row floats between rows               */
+    const int64_t* mask;                 /* [N, F] int64, contiguous: 0 = not a frame                                             */
+    const float* wnorm;                  /* [N, F, F] fp32 from univl_window_norms (may be NULL with normalize = 0)               */
+    int32_t N, F, H;                     /* H must be 768                                                                         */
+    int32_t normalize;
+    const float* q; int64_t ldq;         /* [Nl, K, ldq] fp32 pooled step vectors                                                 */
+    const int32_t* counts;               /* [Nl] on the device: the steps of list i are its first counts[i] vectors               */
+    const int32_t* rows;                 /* [Nl, C] candidate gallery rows                                                        */
+    int32_t Nl, C, K;
+    int32_t lmin, lmax, reserved;
+    int32_t* start; int32_t* length;     /* [Nl, C, K] each, written                                                              */
+    float* score;                        /* [Nl, C, K] written                                                                    */
+    float* total;                        /* [Nl, C] written                                                                       */
+} UnivlStepAlign;
+int univl_step_align_sizeof(void);
+int univl_step_align(const UnivlStepAlign* d, hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

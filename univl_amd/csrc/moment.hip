@@ -1,11 +1,12 @@
-// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize): the best-matching window of frames of a
-// gallery video for a pooled text vector, every window of the video scored in ONE launch.
+// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize, univl_step_align): the best-matching
+// window of frames of a gallery video for a pooled text vector, every window of the video scored in ONE launch -- and, for an ORDERED
+// list of step vectors, the best in-order, non-overlapping windows of all of them at once.
 //
 // A window (s, L) covers frames s .. s + L - 1 of a row; u(s, L) is the sum of its frame vectors.  The score is the model's own --
 // the masked mean over the window, L2-normalised unless use_mil, dotted with the query -- written without the mean:
 //   normalising   (q . u) / max(|u|, 1e-12 L)          use_mil   (q . u) / L
 //
-// Two kernels, no host read, no LDS staging of frames, no float atomics, capturable:
+// Three kernels, no host read, no LDS staging of frames, no float atomics, capturable:
 //   norms      |u(s, L)| of every window of a row, a [F][F] table indexed (s, L - 1).  It depends on the video alone, so an index
 //              computes it once per row.  ONE WAVE OWNS A START s: lane l keeps the 12 columns 4 l + 256 j + c (j < 3, c < 4) of the
 //              running sum u(s, .) in registers, adds frame s + L - 1 to it (three 16-byte loads per lane, the next frame's already in
@@ -19,6 +20,13 @@
 //              frame or past lmax, divides by the table entry (or by L) and keeps its best window, the shortest among equals.  The F
 //              starts' bests are reduced under the total order (score descending, start ascending, length ascending), so the shape of
 //              that reduction cannot matter.
+//   align      one workgroup of 256 threads per (step list, candidate) pair.  The same frame products for every step vector of the list,
+//              d[k][f], into LDS: a wave holds four frames in registers and walks the list, so the row is read once per pair.  Then the
+//              suffix programme of the contract, step n - 1 down to step 0: thread s < F grows start s's numerators exactly as localize
+//              does, adds G[k+1][s + L] and keeps A[k][s] and its length; wave 0 scans A[k] from the right into G[k][t] and the lowest
+//              start >= t that attains it; thread 0 walks forward from (k, t) = (0, 0) and writes the windows, re-growing each chosen
+//              window's numerator (at most F additions in all).  Only the lengths and first starts are kept per step (one byte each):
+//              26 KB of LDS, of which the products are 16.  Two barriers per step.
 //
 // PURITY.  |u(s, L)| is a function of the row's frames s .. s + L - 1 alone, d_f of (q, x_f) alone, a numerator of d_s .. d_{s+L-1}
 // in ascending order: no value depends on the grid, the pair's place in the launch, the other pairs or deterministic mode.  Every sum
@@ -87,6 +95,48 @@ __global__ __launch_bounds__(256) void window_norms_kernel(const float* __restri
     if (s2 != slot) norms_from(x, m, t + (long)s2 * F, F, s2, lane);
 }
 
+// The frame products of one gallery row x for n query rows: d[k * ldd + f] = q_k . x_f, k < n, f < F.  Wave w takes frames w, w + 4, ..,
+// four of them in flight, and walks the query rows over what it holds: every frame is read once.  Each product is one dot768.
+__device__ __forceinline__ void frame_products(const float* __restrict__ q, long ldq, int n, const float* __restrict__ x, int F, float* d, int ldd,
+                                               int lane, int wave) {
+    f32x4_t q0[3], qv[3];
+    load12(q0, q, lane);                                                  // the first query row, often the only one, stays in registers
+    for (int f0 = wave; f0 < F; f0 += 16) {
+        f32x4_t xv[4][3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) load12(xv[r], x + (long)min(f0 + 4 * r, F - 1) * MM_H, lane);
+        for (int k = 0; k < n; ++k) {
+            if (k) {
+                load12(qv, q + k * ldq, lane);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) qv[j] = q0[j];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float s = dot768(qv, xv[r]);
+                if (lane == 0 && f0 + 4 * r < F) d[k * ldd + f0 + 4 * r] = s;
+            }
+        }
+    }
+}
+
+// The candidate windows of start s, shortest first: visit(L, score) for every lmin <= L <= lmax whose frames s .. s + L - 1 are all valid.
+// d: one query's frame products; t: the start's row of the norm table (unused with normalize = 0).  The numerator d_s + .. + d_{s+L-1} is
+// grown one frame at a time, in this order and no other.
+template <typename Visit>
+__device__ __forceinline__ void windows_from(const float* d, const int* valid, const float* __restrict__ t, int F, int s, int lmin, int lmax,
+                                             int normalize, Visit visit) {
+    float num = 0.f;
+    for (int e = s; e < F && e - s < lmax && valid[e]; ++e) {
+        num += d[e];
+        const int L = e - s + 1;
+        if (L < lmin) continue;
+        const float den = normalize ? fmaxf(t[L - 1], 1e-12f * (float)L) : (float)L;
+        visit(L, num / den);
+    }
+}
+
 struct LocArgs {
     const float* q; long ldq;
     const float* frames; long ld_row;
@@ -114,19 +164,7 @@ __global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
         if (tid == 0) { a.start[p] = -1; a.length[p] = 0; a.score[p] = -INFINITY; }
         return;
     }
-    const float* x = a.frames + (long)cand * a.ld_row;
-    f32x4_t qv[3];
-    load12(qv, a.q + (p / a.K) * a.ldq, lane);
-    for (int f0 = wave; f0 < F; f0 += 16) {
-        f32x4_t xv[4][3];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) load12(xv[r], x + (long)min(f0 + 4 * r, F - 1) * MM_H, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float s = dot768(qv, xv[r]);
-            if (lane == 0 && f0 + 4 * r < F) d[f0 + 4 * r] = s;
-        }
-    }
+    frame_products(a.q + (p / a.K) * a.ldq, a.ldq, 1, a.frames + (long)cand * a.ld_row, F, d, 0, lane, wave);
     if (tid < UNIVL_MOMENT_F_MAX) valid[tid] = (tid < F && a.mask[(long)cand * F + tid] != 0) ? 1 : 0;
     __syncthreads();
 
@@ -136,15 +174,9 @@ __global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
         if (tid < F) {
             const int s = tid;
             const float* t = a.normalize ? a.wnorm + ((long)cand * F + s) * F : nullptr;
-            float num = 0.f;
-            for (int e = s; e < F && e - s < a.lmax && valid[e]; ++e) {
-                num += d[e];
-                const int L = e - s + 1;
-                if (L < a.lmin) continue;
-                const float den = a.normalize ? fmaxf(t[L - 1], 1e-12f * (float)L) : (float)L;
-                const float sc = num / den;
+            windows_from(d, valid, t, F, s, a.lmin, a.lmax, a.normalize, [&](int L, float sc) {
                 if (key == MM_NO_WINDOW || sc > best) { best = sc; key = 256 * s + L; }      // the shortest among equals stays
-            }
+            });
         }
         bv[tid] = best; bk[tid] = key;
     }
@@ -168,8 +200,97 @@ __global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
     }
 }
 
-// the checks both entry points share: the descriptor itself and its gallery side
-int check_gallery(const char* who, const UnivlMoment* d) {
+struct AlignArgs {
+    const float* q; long ldq;
+    const float* frames; long ld_row;
+    const int64_t* mask;
+    const float* wnorm;
+    const int32_t* counts; const int32_t* rows;
+    int N, F, C, K, lmin, lmax, normalize;
+    int32_t* start; int32_t* length; float* score; float* total;
+};
+
+// suffix maximum with its first position: the pair at the lower index keeps its place unless the other value is strictly larger
+__device__ __forceinline__ void keep_first_max(float& v, int& i, float v2, int i2) {
+    if (v2 > v) { v = v2; i = i2; }
+}
+
+__global__ __launch_bounds__(256) void step_align_kernel(AlignArgs a) {
+    constexpr int FM = UNIVL_MOMENT_F_MAX, KM = UNIVL_STEP_K_MAX;
+    __shared__ float d[KM * FM];                     // d[k][f] = q_k . x_f                                      16 KB
+    __shared__ int valid[FM];
+    __shared__ float A[FM];                          // A[k][.] of the step at hand
+    __shared__ float G[2][FM + 1];                   // G[k][.] and G[k + 1][.], t = 0 .. FM
+    __shared__ unsigned char len[KM * FM];           // the length behind A[k][s]                                  4 KB
+    __shared__ unsigned char first[KM * FM];         // the lowest s >= t with A[k][s] == G[k][t]                  4 KB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = a.F, K = a.K;
+    const long p = blockIdx.x, list = p / a.C;
+    const int cand = a.rows[p], n = a.counts[list];
+    int32_t* start = a.start + p * K;
+    int32_t* length = a.length + p * K;
+    float* score = a.score + p * K;
+    if (cand < 0 || cand >= a.N || n < 1 || n > K) {                      // block-uniform: nothing of the gallery or of q is read
+        if (tid < K) { start[tid] = -1; length[tid] = 0; score[tid] = -INFINITY; }
+        if (tid == 0) a.total[p] = -INFINITY;
+        return;
+    }
+    frame_products(a.q + list * K * a.ldq, a.ldq, n, a.frames + (long)cand * a.ld_row, F, d, FM, lane, wave);
+    if (tid < FM) valid[tid] = (tid < F && a.mask[(long)cand * F + tid] != 0) ? 1 : 0;
+    if (tid <= FM) { G[n & 1][tid] = 0.f; G[(n & 1) ^ 1][tid] = -INFINITY; }       // T_n = 0 wherever the last window ends
+    __syncthreads();
+
+    const float* trow = a.normalize && tid < F ? a.wnorm + ((long)cand * F + tid) * F : nullptr;
+    for (int k = n - 1; k >= 0; --k) {
+        const float* gn = G[(k + 1) & 1];
+        float* gk = G[k & 1];
+        if (tid < FM) {
+            float best = -INFINITY;                                       // no window, or none with steps k + 1 .. after it
+            int bl = 0;
+            if (tid < F) {
+                windows_from(d + k * FM, valid, trow, F, tid, a.lmin, a.lmax, a.normalize, [&](int L, float w) {
+                    const float v = w + gn[tid + L];
+                    if (v > best) { best = v; bl = L; }                   // the shortest among equals stays
+                });
+            }
+            A[tid] = best; len[k * FM + tid] = (unsigned char)bl;
+        }
+        __syncthreads();
+        if (wave == 0) {                                                  // lane l holds starts l and l + 64
+            float v0 = A[lane], v1 = A[lane + 64];
+            int i0 = lane, i1 = lane + 64;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float u0 = __shfl_down(v0, o, 64), u1 = __shfl_down(v1, o, 64);
+                const int j0 = __shfl_down(i0, o, 64), j1 = __shfl_down(i1, o, 64);
+                if (lane + o < 64) { keep_first_max(v0, i0, u0, j0); keep_first_max(v1, i1, u1, j1); }
+            }
+            keep_first_max(v0, i0, __shfl(v1, 0, 64), __shfl(i1, 0, 64)); // the upper half follows every start of the lower
+            gk[lane] = v0; gk[lane + 64] = v1;
+            first[k * FM + lane] = (unsigned char)i0; first[k * FM + lane + 64] = (unsigned char)i1;
+            if (lane == 0) gk[FM] = -INFINITY;                            // a step that would begin past the last frame
+        }
+        __syncthreads();
+    }
+
+    const float tot = G[0][0];
+    const bool ok = tot > -INFINITY;                                      // all or nothing
+    if (tid < K && (tid >= n || !ok)) { start[tid] = -1; length[tid] = 0; score[tid] = -INFINITY; }
+    if (tid == 0) {
+        a.total[p] = ok ? tot : -INFINITY;
+        for (int k = 0, t = 0; ok && k < n; ++k) {
+            const int s = first[k * FM + t], L = len[k * FM + s];
+            const float* tr = a.normalize ? a.wnorm + ((long)cand * F + s) * F : nullptr;
+            float w = 0.f;
+            windows_from(d + k * FM, valid, tr, F, s, L, L, a.normalize, [&](int, float sc) { w = sc; });
+            start[k] = s; length[k] = L; score[k] = w;
+            t = s + L;
+        }
+    }
+}
+
+// the checks every entry point shares: the descriptor itself and its gallery side (UnivlMoment and UnivlStepAlign name it alike)
+template <typename D>
+int check_gallery(const char* who, const D* d) {
     UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
     UNIVL_CHECK_ARG(d->H == MM_H, UNIVL_EINVAL, "%s: H=%d (must be 768)", who, d->H);
     UNIVL_CHECK_ARG(d->F >= 1 && d->F <= UNIVL_MOMENT_F_MAX, UNIVL_EINVAL, "%s: F=%d (1 <= F <= %d)", who, d->F, UNIVL_MOMENT_F_MAX);
@@ -178,6 +299,17 @@ int check_gallery(const char* who, const UnivlMoment* d) {
     UNIVL_CHECK_ARG(d->frames && d->mask, UNIVL_EINVAL, "%s: null pointer (frames, mask)", who);
     UNIVL_CHECK_ARG(d->ld_row >= (int64_t)d->F * MM_H, UNIVL_EINVAL, "%s: ld_row=%lld (>= F * 768)", who, (long long)d->ld_row);
     UNIVL_CHECK_ARG(rows768_aligned(d->frames, d->ld_row), UNIVL_EALIGN, "%s: rows of frames must be 16-byte aligned", who);
+    return UNIVL_OK;
+}
+
+// what the two localisers ask of the lengths searched, the norm table and the query rows
+template <typename D>
+int check_search(const char* who, const D* d) {
+    UNIVL_CHECK_ARG(d->lmin >= 1 && d->lmin <= d->lmax && d->lmax <= d->F, UNIVL_EINVAL, "%s: lmin=%d lmax=%d (1 <= lmin <= lmax <= F=%d)", who,
+                    d->lmin, d->lmax, d->F);
+    UNIVL_CHECK_ARG(!d->normalize || d->wnorm != nullptr, UNIVL_EINVAL, "%s: null pointer (wnorm with normalize)", who);
+    UNIVL_CHECK_ARG(rows768_pitch(d->ldq), UNIVL_EINVAL, "%s: ldq=%lld (>= 768)", who, (long long)d->ldq);
+    UNIVL_CHECK_ARG(rows768_aligned(d->q, d->ldq), UNIVL_EALIGN, "%s: rows of q must be 16-byte aligned", who);
     return UNIVL_OK;
 }
 
@@ -199,22 +331,43 @@ extern "C" int univl_window_norms(const UnivlMoment* d, hipStream_t stream) {
 
 extern "C" int univl_moment_localize(const UnivlMoment* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);
-    const int rc = check_gallery("univl_moment_localize", d);
-    if (rc != UNIVL_OK) return rc;
     const char* who = "univl_moment_localize";
-    UNIVL_CHECK_ARG(d->lmin >= 1 && d->lmin <= d->lmax && d->lmax <= d->F, UNIVL_EINVAL, "%s: lmin=%d lmax=%d (1 <= lmin <= lmax <= F=%d)", who,
-                    d->lmin, d->lmax, d->F);
+    int rc = check_gallery(who, d);
+    if (rc != UNIVL_OK) return rc;
     UNIVL_CHECK_ARG(d->Nq >= 1 && d->K >= 1 && (int64_t)d->Nq * d->K <= INT_MAX, UNIVL_EINVAL, "%s: Nq=%d K=%d (both >= 1, Nq * K < 2^31)", who,
                     d->Nq, d->K);
     UNIVL_CHECK_ARG(d->q && d->rows && d->start && d->length && d->score, UNIVL_EINVAL, "%s: null pointer (q, rows, start, length, score)", who);
-    UNIVL_CHECK_ARG(!d->normalize || d->wnorm != nullptr, UNIVL_EINVAL, "%s: null pointer (wnorm with normalize)", who);
-    UNIVL_CHECK_ARG(rows768_pitch(d->ldq), UNIVL_EINVAL, "%s: ldq=%lld (>= 768)", who, (long long)d->ldq);
-    UNIVL_CHECK_ARG(rows768_aligned(d->q, d->ldq), UNIVL_EALIGN, "%s: rows of q must be 16-byte aligned", who);
+    rc = check_search(who, d);
+    if (rc != UNIVL_OK) return rc;
     LocArgs a;
     a.q = d->q; a.ldq = (long)d->ldq; a.frames = d->frames; a.ld_row = (long)d->ld_row; a.mask = d->mask; a.wnorm = d->wnorm; a.rows = d->rows;
     a.N = d->N; a.F = d->F; a.K = d->K; a.lmin = d->lmin; a.lmax = d->lmax; a.normalize = d->normalize;
     a.start = d->start; a.length = d->length; a.score = d->score;
     hipLaunchKernelGGL(moment_localize_kernel, dim3((unsigned)(d->Nq * d->K)), dim3(256), 0, stream, a);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_step_align_sizeof(void) { return (int)sizeof(UnivlStepAlign); }
+
+extern "C" int univl_step_align(const UnivlStepAlign* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    const char* who = "univl_step_align";
+    int rc = check_gallery(who, d);
+    if (rc != UNIVL_OK) return rc;
+    UNIVL_CHECK_ARG(d->K >= 1 && d->K <= UNIVL_STEP_K_MAX, UNIVL_EINVAL, "%s: K=%d (1 <= K <= %d)", who, d->K, UNIVL_STEP_K_MAX);
+    UNIVL_CHECK_ARG(d->Nl >= 1 && d->C >= 1 && (int64_t)d->Nl * d->C <= INT_MAX, UNIVL_EINVAL, "%s: Nl=%d C=%d (both >= 1, Nl * C < 2^31)", who,
+                    d->Nl, d->C);
+    UNIVL_CHECK_ARG(d->q && d->counts && d->rows && d->start && d->length && d->score && d->total, UNIVL_EINVAL,
+                    "%s: null pointer (q, counts, rows, start, length, score, total)", who);
+    rc = check_search(who, d);
+    if (rc != UNIVL_OK) return rc;
+    AlignArgs a;
+    a.q = d->q; a.ldq = (long)d->ldq; a.frames = d->frames; a.ld_row = (long)d->ld_row; a.mask = d->mask; a.wnorm = d->wnorm;
+    a.counts = d->counts; a.rows = d->rows;
+    a.N = d->N; a.F = d->F; a.C = d->C; a.K = d->K; a.lmin = d->lmin; a.lmax = d->lmax; a.normalize = d->normalize;
+    a.start = d->start; a.length = d->length; a.score = d->score; a.total = d->total;
+    hipLaunchKernelGGL(step_align_kernel, dim3((unsigned)(d->Nl * d->C)), dim3(256), 0, stream, a);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

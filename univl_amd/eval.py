@@ -16,7 +16,8 @@ CrossEntropyLoss(ignore_index=-1) of modeling.py:246-254 over a whole loader, wi
 session (univl_amd.score.CaptionScorer).
 
 Localisation: eval_localization scores where in its own video every text is found (retrieval.VideoIndex.localize) against annotated
-segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices."""
+segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices.  eval_step_alignment does it for ORDERED lists of steps laid over their video
+jointly (retrieval.VideoIndex.align_steps): step recall by the centre frame of every step's window, and mIoU."""
 import contextlib
 import math
 import os
@@ -163,6 +164,69 @@ def eval_localization(model, index, text_batches, targets, gt_start, gt_len, win
         out[name] = float(np.sum(10 * inter >= num * union)) / n
     out["n"], out["n_empty"] = n, int(np.sum(l == 0))
     return out
+
+
+def eval_step_alignment(model, index, step_batches, targets, gt_start, gt_len, window, device="cuda"):
+    """Action step localisation: every ordered list of steps is laid over ITS OWN video (VideoIndex.align_steps: all steps at once, in
+    order, never overlapping) and each step's window is compared with the annotated one.  index: a retrieval.VideoIndex(model,
+    keep_frames=True) holding the videos; step_batches: iterable of (input_ids [b, K, W], input_mask, segment_ids, counts [b]), the
+    loader's order -- a list's steps are its first counts texts; targets [n]: every list's gallery row; gt_start, gt_len [n, K]: step
+    k's annotated segment, frames gt_start .. gt_start + gt_len - 1, with gt_len == 0 for a step that is not annotated in this video:
+    it is still aligned (it holds its place in the order) but stays out of every denominator, as do the slots past counts; window =
+    (lmin, lmax): the length of a step's window -- with (1, 1) the recall is CrossTask's.  A list whose video cannot hold its steps
+    (or whose count is outside [1, K]) is infeasible: all its annotated steps are misses with IoU 0.  Returns, from one host read,
+      "recall"    annotated steps whose window's centre frame start + (length - 1) // 2 lies in the annotated segment / n_steps
+      "mIoU"      mean temporal IoU over the annotated steps (a float64 mean taken on the host over integer counts)
+      "n_lists", "n_steps" (annotated steps), "n_infeasible" (lists)
+      "hits", "annotated"   int64 arrays [n]: per list, for a macro average per task."""
+    if index.model is not model:
+        raise ValueError("eval_step_alignment: the index belongs to another model")
+    targets = torch.as_tensor(targets).reshape(-1).to(device=device, dtype=torch.int32)
+    gt_start, gt_len = (torch.as_tensor(x).to(device=device, dtype=torch.int32) for x in (gt_start, gt_len))
+    n = targets.numel()
+    if gt_start.dim() != 2 or gt_start.shape != gt_len.shape or gt_start.shape[0] != n:
+        raise ValueError("eval_step_alignment: %d targets, gt_start %s, gt_len %s (both [lists, steps])"
+                         % (n, tuple(gt_start.shape), tuple(gt_len.shape)))
+    if n == 0:
+        raise ValueError("eval_step_alignment: no lists")
+    if int(targets.min()) < 0 or int(targets.max()) >= len(index) or int(gt_len.min()) < 0 or int(gt_start.min()) < 0:
+        raise ValueError("eval_step_alignment: targets must lie in [0, %d), gt_start >= 0 and gt_len >= 0" % len(index))
+    K = gt_start.shape[1]
+    starts, lengths, totals, steps = [], [], [], []
+    row = 0
+    with _eval_mode(model):
+        for batch in step_batches:
+            input_ids, input_mask, segment_ids, counts = [t.to(device) for t in batch[:4]]
+            b = input_ids.shape[0]
+            if input_ids.dim() != 3 or input_ids.shape[1] != K or counts.numel() != b:
+                raise ValueError("eval_step_alignment: a batch of shape %s with %d counts, the annotation holds %d steps per list"
+                                 % (tuple(input_ids.shape), counts.numel(), K))
+            if row + b > n:
+                raise ValueError("eval_step_alignment: more lists than targets (%d)" % n)
+            s, l, _, tot = index.align_steps(input_ids, segment_ids, input_mask, counts, targets[row:row + b].reshape(b, 1), window)
+            starts.append(s[:, 0])
+            lengths.append(l[:, 0])
+            totals.append(tot[:, 0])
+            steps.append(counts.reshape(b).to(torch.int32))
+            row += b
+    if row != n:
+        raise ValueError("eval_step_alignment: %d lists for %d targets" % (row, n))
+    s, l, steps = torch.cat(starts), torch.cat(lengths), torch.cat(steps)          # an empty slot is (-1, 0): it meets no frame
+    annotated = (gt_len > 0) & (torch.arange(K, device=s.device)[None, :] < steps[:, None])
+    centre = s + torch.div(l - 1, 2, rounding_mode="floor")
+    hit = annotated & (l > 0) & (centre >= gt_start) & (centre < gt_start + gt_len)
+    inter = (torch.minimum(s + l, gt_start + gt_len) - torch.maximum(s, gt_start)).clamp_(min=0)
+    inter = torch.where(l > 0, inter, torch.zeros_like(inter))
+    union = l + gt_len - inter
+    infeasible = torch.isinf(torch.cat(totals)).to(torch.int32)
+    host = torch.cat([t.to(torch.int32).reshape(-1) for t in (hit, annotated, inter, union, infeasible)]).cpu().numpy().astype(np.int64)
+    hit, annotated, inter, union = (host[i * n * K:(i + 1) * n * K].reshape(n, K) for i in range(4))       # the one host read
+    n_steps = int(annotated.sum())
+    if n_steps == 0:
+        raise ValueError("eval_step_alignment: no annotated step")
+    on = annotated != 0
+    return {"recall": float(hit.sum()) / n_steps, "mIoU": float(np.mean(inter[on].astype(np.float64) / union[on].astype(np.float64))),
+            "n_lists": n, "n_steps": n_steps, "n_infeasible": int(host[4 * n * K:].sum()), "hits": hit.sum(1), "annotated": annotated.sum(1)}
 
 
 def ids_to_caption(tokenizer, ids):

@@ -792,12 +792,12 @@ def hub_gate(top1, hub):
     return gate
 
 
-def _moment_gallery(frames, mask, normalize):
-    """The gallery side of a Moment descriptor (window_norms and moment_localize)."""
+def _moment_gallery(frames, mask, normalize, desc=_lib.Moment):
+    """The gallery side of a Moment or StepAlign descriptor (window_norms, moment_localize and step_align)."""
     _require_gpu(frames, mask)
     assert frames.dtype == torch.float32 and frames.dim() == 3 and frames.stride(2) == 1 and frames.stride(1) == frames.shape[2]
     assert mask.dtype == torch.int64 and mask.shape == frames.shape[:2] and mask.is_contiguous()
-    d = _lib.Moment()
+    d = desc()
     d.N, d.F, d.H, d.normalize = frames.shape[0], frames.shape[1], frames.shape[2], 1 if normalize else 0
     d.frames, d.ld_row, d.mask = _p(frames), frames.stride(0) if d.N > 1 else d.F * d.H, _p(mask)     # one row: its stride means nothing
     return d
@@ -817,6 +817,15 @@ def window_norms(frames, mask, *, out=None):
     return t
 
 
+def _moment_table(who, d, wnorm, normalize):
+    """d.wnorm of a localiser: the table window_norms made of the same gallery, which a normalising model needs."""
+    if normalize:
+        if wnorm is None:
+            raise RuntimeError("%s: normalize=True needs wnorm (window_norms)" % who)
+        assert wnorm.dtype == torch.float32 and wnorm.shape == (d.N, d.F, d.F) and wnorm.is_contiguous()
+        d.wnorm = _p(wnorm)
+
+
 def moment_localize(q, frames, mask, rows, lmin, lmax, *, wnorm=None, normalize=True):
     """The best window of frames of gallery row rows[i, j] for query row i, every window scored in one launch (include/univl_hip.h:
     univl_moment_localize).  q: [Nq, 768] fp32 row-major view (row stride >= 768, rows 16-byte aligned); frames, mask: as
@@ -831,11 +840,7 @@ def moment_localize(q, frames, mask, rows, lmin, lmax, *, wnorm=None, normalize=
     assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == q.shape[0] and rows.is_contiguous()
     if q.shape[1] != frames.shape[2]:
         raise RuntimeError("moment_localize: q is %d wide, the frames %d" % (q.shape[1], frames.shape[2]))
-    if normalize:
-        if wnorm is None:
-            raise RuntimeError("moment_localize: normalize=True needs wnorm (window_norms)")
-        assert wnorm.dtype == torch.float32 and wnorm.shape == (d.N, d.F, d.F) and wnorm.is_contiguous()
-        d.wnorm = _p(wnorm)
+    _moment_table("moment_localize", d, wnorm, normalize)
     d.q, d.ldq, d.rows, d.Nq, d.K, d.lmin, d.lmax = _p(q), _ld(q), _p(rows), rows.shape[0], rows.shape[1], int(lmin), int(lmax)
     start = torch.empty(d.Nq, d.K, dtype=torch.int32, device=q.device)
     length = torch.empty(d.Nq, d.K, dtype=torch.int32, device=q.device)
@@ -843,6 +848,35 @@ def moment_localize(q, frames, mask, rows, lmin, lmax, *, wnorm=None, normalize=
     d.start, d.length, d.score = _p(start), _p(length), _p(score)
     _lib.check(_lib.lib().univl_moment_localize(_BYREF(d), _stream()), "moment_localize")
     return start, length, score
+
+
+def step_align(q, counts, frames, mask, rows, lmin, lmax, wnorm=None, normalize=True):
+    """Lays ordered lists of step vectors over gallery rows (include/univl_hip.h: univl_step_align): for list i and gallery row
+    rows[i, c], the windows (start, length) of its first counts[i] steps -- each of lmin .. lmax valid frames, in order, never
+    overlapping -- whose moment_localize scores have the largest sum.  q: [Nl, K, 768] fp32 (vectors contiguous, K <= STEP_K_MAX; slots
+    past counts[i] are padding and never read); counts: [Nl] int32; frames, mask, wnorm, normalize: as moment_localize's; rows: [Nl, C]
+    int32.  Returns (start, length, score [Nl, C, K] int32, int32, fp32; total [Nl, C] fp32): padding slots are (-1, 0, -inf); a pair
+    with no alignment, a row id outside the gallery or a count outside [1, K] is (-1, 0, -inf) in every slot with total -inf."""
+    d = _moment_gallery(frames, mask, normalize, _lib.StepAlign)
+    _require_gpu(q, counts, rows, wnorm)
+    assert q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
+    Nl, K = q.shape[:2]
+    ldq = q.stride(1) if K > 1 else q.stride(0) if Nl > 1 else q.shape[2]           # the stride of a dimension of one means nothing
+    assert Nl == 1 or q.stride(0) == K * ldq, "the lists of q must lie K rows apart"
+    assert counts.dtype == torch.int32 and counts.shape == (q.shape[0],) and counts.is_contiguous()
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == q.shape[0] and rows.is_contiguous()
+    if q.shape[2] != frames.shape[2]:
+        raise RuntimeError("step_align: q is %d wide, the frames %d" % (q.shape[2], frames.shape[2]))
+    _moment_table("step_align", d, wnorm, normalize)
+    d.Nl, d.C, d.K, d.lmin, d.lmax = Nl, rows.shape[1], K, int(lmin), int(lmax)
+    d.q, d.ldq, d.counts, d.rows = _p(q), ldq, _p(counts), _p(rows)
+    start = torch.empty(d.Nl, d.C, d.K, dtype=torch.int32, device=q.device)
+    length = torch.empty(d.Nl, d.C, d.K, dtype=torch.int32, device=q.device)
+    score = torch.empty(d.Nl, d.C, d.K, dtype=torch.float32, device=q.device)
+    total = torch.empty(d.Nl, d.C, dtype=torch.float32, device=q.device)
+    d.start, d.length, d.score, d.total = _p(start), _p(length), _p(score), _p(total)
+    _lib.check(_lib.lib().univl_step_align(_BYREF(d), _stream()), "step_align")
+    return start, length, score, total
 
 
 class AdamTables:

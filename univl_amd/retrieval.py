@@ -15,7 +15,10 @@ column term (include/univl_hip.h: univl_sim_colstat, univl_sim_topk_norm).  No r
 
 Moment search says WHERE in a video a text matches: VideoIndex(keep_frames=True).localize() scores every window of frames of a
 candidate video the way get_similarity_logits scores the whole video (include/univl_hip.h: univl_window_norms,
-univl_moment_localize) and returns the best one; search_moments() does that for the best videos of a search and ranks the moments."""
+univl_moment_localize) and returns the best one; search_moments() does that for the best videos of a search and ranks the moments.
+
+Step alignment says where every step of an ORDERED list of texts happens: align_steps() places all of them at once, in order and
+without overlap, by the same window score (univl_step_align) -- action step localisation."""
 import ctypes
 import math
 import numbers
@@ -198,18 +201,56 @@ class VideoIndex:
     @torch.no_grad()
     def localize_vectors(self, q, rows, window):
         """localize() for pooled query vectors the caller already holds ([Nq, 768] fp32 on the index's device)."""
-        if not self.keep_frames or self._frames is None:
-            raise ValueError("VideoIndex.localize needs an index built with keep_frames=True, with videos in it")
-        F = self._frames.shape[1]
-        lmin, lmax = (int(w) for w in window)
-        if not 1 <= lmin <= lmax <= F:
-            raise ValueError("VideoIndex.localize: window=(%d, %d), need 1 <= lmin <= lmax <= %d frames" % (lmin, lmax, F))
-        if F > _lib.MOMENT_F_MAX:
-            raise ValueError("VideoIndex.localize: videos of %d frames, at most %d" % (F, _lib.MOMENT_F_MAX))
+        lmin, lmax = self._check_window("localize", window)
         q = _query_rows(q)
         rows = torch.as_tensor(rows).to(device=q.device, dtype=torch.int32).reshape(q.shape[0], -1).contiguous()
         wnorm = self._window_norms() if self.normalize else None
         return ops.moment_localize(q, self._frames[:self._n], self._fmask[:self._n], rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
+
+    def _check_window(self, who, window):
+        """(lmin, lmax) of a localisation, or the ValueError every localiser raises: no frames kept, a bad window, videos too long."""
+        if not self.keep_frames or self._frames is None:
+            raise ValueError("VideoIndex.%s needs an index built with keep_frames=True, with videos in it" % who)
+        F = self._frames.shape[1]
+        lmin, lmax = (int(w) for w in window)
+        if not 1 <= lmin <= lmax <= F:
+            raise ValueError("VideoIndex.%s: window=(%d, %d), need 1 <= lmin <= lmax <= %d frames" % (who, lmin, lmax, F))
+        if F > _lib.MOMENT_F_MAX:
+            raise ValueError("VideoIndex.%s: videos of %d frames, at most %d" % (who, F, _lib.MOMENT_F_MAX))
+        return lmin, lmax
+
+    # ------------------------------------------------------------------------------------------ ordered step alignment
+    @torch.no_grad()
+    def align_steps(self, input_ids, token_type_ids, attention_mask, counts, rows, window=(1, 1)):
+        """Where every step of an ORDERED list of texts happens in gallery row rows[i, c].  The text tensors are [Nl, K, W]: list i's
+        steps are its first counts[i] texts, the others padding (encoded like any text, their vectors never read); K <= STEP_K_MAX.
+        rows: [Nl, C] gallery rows; window = (lmin, lmax): the length of a step's window, in frames -- (1, 1) is one frame per step.
+        Returns (start, length, score [Nl, C, K], total [Nl, C]) on the device: the windows, each scored as localize() scores it, in
+        order and never overlapping, whose scores have the largest sum (include/univl_hip.h: univl_step_align); padding slots are
+        (-1, 0, -inf); a video whose valid frames cannot hold all the steps is (-1, 0, -inf) in every slot with total -inf, and so is
+        a -1 row or a count outside [1, K].  With one step per list the result is localize()'s.  Needs keep_frames=True."""
+        Nl, K, _, _ = self._check_lists("align_steps", input_ids, window)
+        flat = (t.reshape(Nl * K, -1) for t in (input_ids, token_type_ids, attention_mask))
+        return self.align_vectors(self.pool_text(*flat)[0].view(Nl, K, H), counts, rows, window)
+
+    @torch.no_grad()
+    def align_vectors(self, q, counts, rows, window=(1, 1)):
+        """align_steps() for pooled step vectors the caller already holds ([Nl, K, 768] fp32 on the index's device)."""
+        Nl, K, lmin, lmax = self._check_lists("align_vectors", q, window)
+        q = _query_rows(q).view(Nl, K, H)
+        counts = torch.as_tensor(counts).to(device=q.device, dtype=torch.int32).reshape(Nl).contiguous()
+        rows = torch.as_tensor(rows).to(device=q.device, dtype=torch.int32).reshape(Nl, -1).contiguous()
+        wnorm = self._window_norms() if self.normalize else None
+        return ops.step_align(q, counts, self._frames[:self._n], self._fmask[:self._n], rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
+
+    def _check_lists(self, who, lists, window):
+        """(Nl, K, lmin, lmax) for a [Nl, K, .] tensor of step lists, after every refusal that needs no device work."""
+        lmin, lmax = self._check_window(who, window)
+        if lists.dim() != 3:
+            raise ValueError("VideoIndex.%s: step lists are [lists, steps, .] tensors, got %d dimensions" % (who, lists.dim()))
+        if not 1 <= lists.shape[1] <= _lib.STEP_K_MAX:
+            raise ValueError("VideoIndex.%s: lists of %d steps, need 1 .. %d" % (who, lists.shape[1], _lib.STEP_K_MAX))
+        return lists.shape[0], lists.shape[1], lmin, lmax
 
     @torch.no_grad()
     def search_moments(self, input_ids, token_type_ids, attention_mask, k=10, window=(1, 1), shortlist=None, bank=None):
