@@ -141,8 +141,8 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(UnivlEmbedText p, float*
                 else unsafeAtomicAdd(p.dword + id * N + col + e, dx);
                 if (!DET && p.dpos) unsafeAtomicAdd(p.dpos + (long)s * N + col + e, dx);
                 // token types 0 / 1 (every row of a batch hits the same one or two table rows) are combined per
-                // block below; anything else goes straight to the table
-                if (p.dtype_emb && tt > 1) unsafeAtomicAdd(p.dtype_emb + tt * N + col + e, dx);
+                // block below; anything else goes straight to the table (DET: embed_scatter_det_kernel on the type ids, from row 2)
+                if (!DET && p.dtype_emb && tt > 1) unsafeAtomicAdd(p.dtype_emb + tt * N + col + e, dx);
                 dxs[j][e] = dx;
             }
         }
@@ -212,10 +212,13 @@ extern "C" int univl_embed_text_fwd(const UnivlEmbedText* d, hipStream_t stream)
 
 namespace {
 // Deterministic scatter: token t owns destination row ids[t] iff no earlier token has the same id; the owner adds the rows of ALL
-// tokens with that id in token order, then adds the total to the table (one writer per table row and launch).
-__global__ __launch_bounds__(256) void embed_scatter_det_kernel(const int64_t* ids, const float* rows, long n, float scale, float* dword) {
+// tokens with that id in token order, then adds the total to the table (one writer per table row and launch).  Ids below min_id
+// are left out (the token-type rows 0 and 1 have a gather of their own).
+__global__ __launch_bounds__(256) void embed_scatter_det_kernel(const int64_t* ids, const float* rows, long n, float scale, float* dword,
+                                                                int64_t min_id = 0) {
     const long t = blockIdx.x;
     const int64_t id = ids[t];
+    if (id < min_id) return;                              // block-uniform
     int dup = 0;
     for (long j = threadIdx.x; j < t; j += 256) dup |= (ids[j] == id) ? 1 : 0;
     if (__syncthreads_or(dup)) return;
@@ -400,8 +403,12 @@ extern "C" int univl_embed_text_bwd(const UnivlEmbedText* d, hipStream_t stream)
             hipLaunchKernelGGL(embed_scatter_det_kernel, dim3((unsigned)T), block, 0, stream, d->ids, q.drows, T, 1.0f, d->dword);
         if (d->dpos)
             hipLaunchKernelGGL(embed_dpos_gather_kernel, dim3((unsigned)(((long)d->S * N + 255) / 256)), block, 0, stream, q.drows, d->B, d->S, d->dpos);
-        if (d->dtype_emb)
+        if (d->dtype_emb) {
             hipLaunchKernelGGL(embed_dtype_gather_kernel, dim3(N / 256, 2), block, 0, stream, d->type_ids, q.drows, T, d->dtype_emb);
+            if (d->type_ids)     // token types from 2 on: the atomic form adds them to the table in arrival order
+                hipLaunchKernelGGL(embed_scatter_det_kernel, dim3((unsigned)T), block, 0, stream, d->type_ids, q.drows, T, 1.0f, d->dtype_emb,
+                                   (int64_t)2);
+        }
         UNIVL_LAUNCH_CHECK();
         return UNIVL_OK;
     }
