@@ -129,11 +129,16 @@ __global__ __launch_bounds__(256) void tanh_bwd_kernel(const float* dy, const fl
 }
 
 // dU = dG * gelu'(U)  (BertPredictionHeadTransform backward: the GELU sits between a GEMM and a LayerNorm there,
-// module_bert.py:299-311, so it cannot ride on a GEMM epilogue)
+// module_bert.py:299-311, so it cannot ride on a GEMM epilogue).  Phi(u) = erfc(-u / sqrt 2) / 2 here, not common.h's 1 + erf: that sum
+// cancels in the negative tail (absolute error 3e-8 from u = -3.5 down, where the derivative is below 1e-4 and a bf16 result would
+// keep no correct digit); this kernel is bound by HBM, the GEMM epilogues keep the cheaper form.
+__device__ __forceinline__ float gelu_grad_tail_f(float x) {
+    return 0.5f * erfcf(x * -0.70710678118654752440f) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
+}
 template <typename T>
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* dg, const T* u, T* du, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-        du[i] = from_f32<T>(dg[i] * gelu_grad_f(to_f32<T>(u[i])));
+        du[i] = from_f32<T>(dg[i] * gelu_grad_tail_f(to_f32<T>(u[i])));
 }
 
 // out[c] += sum_r x[r, c]   (bias gradient of a projection whose weight gradient is produced transposed)
