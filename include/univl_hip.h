@@ -907,6 +907,51 @@ typedef struct UnivlMoment {
 int univl_moment_sizeof(void);
 int univl_window_norms(const UnivlMoment* d, hipStream_t stream);
 int univl_moment_localize(const UnivlMoment* d, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- n-best moments with temporal NMS
+ * SEVERAL windows per (query, gallery row) pair: greedy non-maximum suppression over univl_moment_localize's own candidates, on the
+ * device, for "R@n, IoU = m" tables and for texts that match a video in more than one place.  Candidate windows, their scores and
+ * ORDER (larger score first, then lower start, then smaller length) are exactly univl_moment_localize's.  For each pair, with every
+ * candidate alive at first, for m = 0 .. M - 1:
+ *   pick        the first live candidate under ORDER goes to slot m
+ *   suppress    the pick dies, and so does every live window w with  iou_den * inter(w, pick) > iou_num * union(w, pick);  inter and
+ *               union are counted in frames, in integers: no float enters a suppression decision
+ *   empty       when nothing is alive, slot m and all later slots are (-1, 0, -inf)
+ * A row id outside [0, N) gives (-1, 0, -inf) in all M slots, decided for the whole workgroup before anything of the gallery is read.
+ * Consequences: slot 0 is univl_moment_localize's triple bit for bit, and M = 1 is univl_moment_localize; iou_num == iou_den
+ * suppresses nothing but the pick itself, so the result is the plain top-M windows under ORDER; iou_num == 0 yields pairwise
+ * disjoint windows; the scores of a pair's slots never increase from slot to slot.
+ * One workgroup of 256 threads per pair, one launch, no workspace, no host read, no atomics, capturable.  The frame products and
+ * the visit of a start's windows are univl_moment_localize's device functions (the numerator grown by extension, the same
+ * denominator: that is what makes slot 0 bit-identical); thread s < F stores every score in LDS instead of folding it -- length-major
+ * and triangular, row L holding the F - L + 1 starts of length L, lengths lmin .. lmax only: at most 8 256 floats (33 KB) -- so the
+ * norm table is read once per window, not once per round.  A round is one walk per thread over its own stored scores (it marks what
+ * the previous pick suppresses with NaN, which no live score equals, and keeps its best survivor) and the reduction of the F bests
+ * that univl_moment_localize runs, under the same total order.
+ * PURITY: a pair's result is a function of its q row, the gallery row (frames, mask, table rows), (lmin, lmax), normalize and
+ * (M, iou_num, iou_den) only -- not of its place in the launch, the other pairs, N, or deterministic mode; the first M slots do not
+ * depend on M.
+ * Range: 1 <= M <= UNIVL_MOMENT_NBEST_MAX, 1 <= iou_den <= 1024, 0 <= iou_num <= iou_den; everything else as for
+ * univl_moment_localize; otherwise, or for a NULL pointer, UNIVL_EINVAL; rows of frames and q 16-byte aligned (UNIVL_EALIGN); all
+ * before any launch.  Behaviour on NaN or infinite values: unspecified. */
+#define UNIVL_MOMENT_NBEST_MAX 16
+typedef struct UnivlMomentNbest {
+    const float* frames; int64_t ld_row; /* [N, F, 768] fp32 frames of the gallery rows, ld_row floats between rows               */
+    const int64_t* mask;                 /* [N, F] int64, contiguous: 0 = not a frame                                             */
+    const float* wnorm;                  /* [N, F, F] fp32 from univl_window_norms (may be NULL with normalize = 0)               */
+    int32_t N, F, H;                     /* H must be 768                                                                         */
+    int32_t normalize;
+    const float* q; int64_t ldq;         /* [Nq, ldq] fp32 pooled queries                                                         */
+    const int32_t* rows;                 /* [Nq, K] candidate gallery rows; outside [0, N): (-1, 0, -inf) in every slot            */
+    int32_t Nq, K;
+    int32_t lmin, lmax;
+    int32_t M;                           /* windows per pair                                                                      */
+    int32_t iou_num, iou_den;            /* w dies iff iou_den * inter > iou_num * union                                          */
+    int32_t reserved;
+    int32_t* start; int32_t* length;     /* [Nq, K, M] each, written                                                              */
+    float* score;                        /* [Nq, K, M] written                                                                    */
+} UnivlMomentNbest;
+int univl_moment_nbest_sizeof(void);
+int univl_moment_nbest(const UnivlMomentNbest* d, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------- ordered step alignment
  * WHERE every step of an ORDERED list of texts happens in a video (action step localisation; with lmin = lmax = 1 the dynamic
  * programme of CrossTask: one frame per step, frames strictly increasing).  The gallery side -- frames, ld_row, mask, wnorm, N, F, H,

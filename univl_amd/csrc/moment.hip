@@ -1,12 +1,13 @@
-// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize, univl_step_align): the best-matching
-// window of frames of a gallery video for a pooled text vector, every window of the video scored in ONE launch -- and, for an ORDERED
-// list of step vectors, the best in-order, non-overlapping windows of all of them at once.
+// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize, univl_moment_nbest, univl_step_align):
+// the best-matching window of frames of a gallery video for a pooled text vector, every window of the video scored in ONE launch --
+// or its n best windows after temporal non-maximum suppression -- and, for an ORDERED list of step vectors, the best in-order,
+// non-overlapping windows of all of them at once.
 //
 // A window (s, L) covers frames s .. s + L - 1 of a row; u(s, L) is the sum of its frame vectors.  The score is the model's own --
 // the masked mean over the window, L2-normalised unless use_mil, dotted with the query -- written without the mean:
 //   normalising   (q . u) / max(|u|, 1e-12 L)          use_mil   (q . u) / L
 //
-// Three kernels, no host read, no LDS staging of frames, no float atomics, capturable:
+// Four kernels, no host read, no LDS staging of frames, no float atomics, capturable:
 //   norms      |u(s, L)| of every window of a row, a [F][F] table indexed (s, L - 1).  It depends on the video alone, so an index
 //              computes it once per row.  ONE WAVE OWNS A START s: lane l keeps the 12 columns 4 l + 256 j + c (j < 3, c < 4) of the
 //              running sum u(s, .) in registers, adds frame s + L - 1 to it (three 16-byte loads per lane, the next frame's already in
@@ -20,7 +21,14 @@
 //              frame or past lmax, divides by the table entry (or by L) and keeps its best window, the shortest among equals.  The F
 //              starts' bests are reduced under the total order (score descending, start ascending, length ascending), so the shape of
 //              that reduction cannot matter.
-//   align      one workgroup of 256 threads per (step list, candidate) pair.  The same frame products for every step vector of the list,
+//   nbest      the same workgroup per pair, but SEVERAL windows of it: greedy temporal NMS over localize's own candidates.  Thread s
+//              visits its windows as localize does and STORES every score in LDS -- length-major and triangular, row L holding the
+//              F - L + 1 starts of length L, so that neighbouring threads touch neighbouring words; lengths lmin .. lmax only: at most
+//              8 256 floats -- so the norm table is read once per window, not once per round.  A round: every thread walks its own
+//              stored scores, marks what the previous pick suppresses (NaN: no live score equals it; the IoU test is in integers) and
+//              keeps its best survivor; the F bests are reduced by localize's reduction, which EVERY wave runs on a double-buffered
+//              copy, so all threads know the pick after ONE barrier per round.  No thread reads another's scores.  36 KB of LDS.
+//   align     one workgroup of 256 threads per (step list, candidate) pair.  The same frame products for every step vector of the list,
 //              d[k][f], into LDS: a wave holds four frames in registers and walks the list, so the row is read once per pair.  Then the
 //              suffix programme of the contract, step n - 1 down to step 0: thread s < F grows start s's numerators exactly as localize
 //              does, adds G[k+1][s + L] and keeps A[k][s] and its length; wave 0 scans A[k] from the right into G[k][t] and the lowest
@@ -152,6 +160,20 @@ __device__ __forceinline__ void keep_better(float& v, int& k, float v2, int k2) 
     if (v2 > v || (v2 == v && k2 < k)) { v = v2; k = k2; }
 }
 
+// the first under that order of the UNIVL_MOMENT_F_MAX starts' bests (bv, bk), in every lane of the calling wave: lane l folds starts
+// l and l + 64, then the xor butterfly.  The order is total, so the shape of the reduction cannot matter.
+__device__ __forceinline__ void best_start(const float* bv, const int* bk, int lane, float& v, int& k) {
+    v = bv[lane];
+    k = bk[lane];
+    keep_better(v, k, bv[lane + 64], bk[lane + 64]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v2 = __shfl_xor(v, o, 64);
+        const int k2 = __shfl_xor(k, o, 64);
+        keep_better(v, k, v2, k2);
+    }
+}
+
 __global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
     __shared__ float d[UNIVL_MOMENT_F_MAX];          // frame products
     __shared__ int valid[UNIVL_MOMENT_F_MAX];
@@ -182,20 +204,91 @@ __global__ __launch_bounds__(256) void moment_localize_kernel(LocArgs a) {
     }
     __syncthreads();
     if (wave == 0) {
-        float v = bv[lane];
-        int k = bk[lane];
-        keep_better(v, k, bv[lane + 64], bk[lane + 64]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float v2 = __shfl_xor(v, o, 64);
-            const int k2 = __shfl_xor(k, o, 64);
-            keep_better(v, k, v2, k2);
-        }
+        float v;
+        int k;
+        best_start(bv, bk, lane, v, k);
         if (lane == 0) {
             const bool none = k == MM_NO_WINDOW;
             a.start[p] = none ? -1 : k >> 8;
             a.length[p] = none ? 0 : k & 255;
             a.score[p] = none ? -INFINITY : v;
+        }
+    }
+}
+
+struct NbestArgs {
+    LocArgs loc;                                     // start, length, score: [Nq, K, M]
+    int M, iou_num, iou_den;
+};
+
+// does the pick (ps, pl) suppress the live window (s, L)?  Frames, in integers; the pick itself dies whatever the threshold
+__device__ __forceinline__ bool suppressed(int s, int L, int ps, int pl, int num, int den) {
+    const int inter = max(0, min(s + L, ps + pl) - max(s, ps));
+    return (s == ps && L == pl) || den * inter > num * (L + pl - inter);
+}
+
+__global__ __launch_bounds__(256) void moment_nbest_kernel(NbestArgs b) {
+    constexpr int FM = UNIVL_MOMENT_F_MAX;
+    __shared__ float d[FM];                          // frame products
+    __shared__ int valid[FM];
+    __shared__ float bv[2][FM];                      // every start's best live window, of this round and of the one before
+    __shared__ int bk[2][FM];
+    __shared__ float sc[FM * (FM + 1) / 2];          // every window's score, length-major: row L holds starts 0 .. F - L       33 KB
+    const LocArgs& a = b.loc;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = a.F, M = b.M;
+    const long p = blockIdx.x;
+    const int cand = a.rows[p];
+    int32_t* start = a.start + p * M;
+    int32_t* length = a.length + p * M;
+    float* score = a.score + p * M;
+    if (cand < 0 || cand >= a.N) {                                        // block-uniform: nothing of the gallery is read
+        if (tid < M) { start[tid] = -1; length[tid] = 0; score[tid] = -INFINITY; }
+        return;
+    }
+    frame_products(a.q + (p / a.K) * a.ldq, a.ldq, 1, a.frames + (long)cand * a.ld_row, F, d, 0, lane, wave);
+    if (tid < FM) valid[tid] = (tid < F && a.mask[(long)cand * F + tid] != 0) ? 1 : 0;
+    __syncthreads();
+
+    // thread s owns start s: its windows are lengths lmin .. lend, word sc[row(L) + s] with row(lmin) = 0, row(L + 1) = row(L) + F - L + 1.
+    // No other thread reads or writes them, so the rounds need no barrier for sc and nothing of it has to be cleared.
+    const int s = tid, lmin = a.lmin;
+    float best = -INFINITY;
+    int key = MM_NO_WINDOW, lend = 0;
+    if (s < F) {
+        const float* t = a.normalize ? a.wnorm + ((long)cand * F + s) * F : nullptr;
+        int at = s;
+        windows_from(d, valid, t, F, s, lmin, a.lmax, a.normalize, [&](int L, float w) {
+            sc[at] = w;
+            at += F - L + 1;
+            lend = L;
+            if (key == MM_NO_WINDOW || w > best) { best = w; key = 256 * s + L; }        // moment_localize_kernel's fold: slot 0 is its triple
+        });
+    }
+    for (int m = 0;; ++m) {
+        if (tid < FM) { bv[m & 1][tid] = best; bk[m & 1][tid] = key; }
+        __syncthreads();                                                  // one barrier per round: the round after next writes this buffer again
+        float v;
+        int k;
+        best_start(bv[m & 1], bk[m & 1], lane, v, k);                     // every wave: all threads know the pick
+        if (k == MM_NO_WINDOW) {                                          // block-uniform: nothing is alive
+            if (tid >= m && tid < M) { start[tid] = -1; length[tid] = 0; score[tid] = -INFINITY; }
+            return;
+        }
+        const int ps = k >> 8, pl = k & 255;
+        if (tid == 0) { start[m] = ps; length[m] = pl; score[m] = v; }
+        if (m + 1 == M) return;
+        // the walk: what the pick suppresses dies (NaN: no live score equals it), the best survivor stays, the shortest among equals
+        best = -INFINITY;
+        key = MM_NO_WINDOW;
+        // (no branch but the store's, so that the loop unrolls and several reads of sc are in flight; a dead window may die again)
+#pragma unroll 4
+        for (int L = lmin, at = s; L <= lend; at += F - L + 1, ++L) {
+            const float w = sc[at];
+            const bool kill = suppressed(s, L, ps, pl, b.iou_num, b.iou_den);
+            if (kill) sc[at] = NAN;
+            const bool take = !kill && w == w && (key == MM_NO_WINDOW || w > best);
+            best = take ? w : best;
+            key = take ? 256 * s + L : key;
         }
     }
 }
@@ -344,6 +437,33 @@ extern "C" int univl_moment_localize(const UnivlMoment* d, hipStream_t stream) {
     a.N = d->N; a.F = d->F; a.K = d->K; a.lmin = d->lmin; a.lmax = d->lmax; a.normalize = d->normalize;
     a.start = d->start; a.length = d->length; a.score = d->score;
     hipLaunchKernelGGL(moment_localize_kernel, dim3((unsigned)(d->Nq * d->K)), dim3(256), 0, stream, a);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
+
+extern "C" int univl_moment_nbest_sizeof(void) { return (int)sizeof(UnivlMomentNbest); }
+
+extern "C" int univl_moment_nbest(const UnivlMomentNbest* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    const char* who = "univl_moment_nbest";
+    int rc = check_gallery(who, d);
+    if (rc != UNIVL_OK) return rc;
+    UNIVL_CHECK_ARG(d->M >= 1 && d->M <= UNIVL_MOMENT_NBEST_MAX, UNIVL_EINVAL, "%s: M=%d (1 <= M <= %d)", who, d->M, UNIVL_MOMENT_NBEST_MAX);
+    UNIVL_CHECK_ARG(d->iou_den >= 1 && d->iou_den <= 1024, UNIVL_EINVAL, "%s: iou_den=%d (1 <= iou_den <= 1024)", who, d->iou_den);
+    UNIVL_CHECK_ARG(d->iou_num >= 0 && d->iou_num <= d->iou_den, UNIVL_EINVAL, "%s: iou_num=%d (0 <= iou_num <= iou_den=%d)", who, d->iou_num,
+                    d->iou_den);
+    UNIVL_CHECK_ARG(d->Nq >= 1 && d->K >= 1 && (int64_t)d->Nq * d->K * d->M <= INT_MAX, UNIVL_EINVAL,
+                    "%s: Nq=%d K=%d (both >= 1, Nq * K * M < 2^31)", who, d->Nq, d->K);
+    UNIVL_CHECK_ARG(d->q && d->rows && d->start && d->length && d->score, UNIVL_EINVAL, "%s: null pointer (q, rows, start, length, score)", who);
+    rc = check_search(who, d);
+    if (rc != UNIVL_OK) return rc;
+    NbestArgs b;
+    LocArgs& a = b.loc;
+    a.q = d->q; a.ldq = (long)d->ldq; a.frames = d->frames; a.ld_row = (long)d->ld_row; a.mask = d->mask; a.wnorm = d->wnorm; a.rows = d->rows;
+    a.N = d->N; a.F = d->F; a.K = d->K; a.lmin = d->lmin; a.lmax = d->lmax; a.normalize = d->normalize;
+    a.start = d->start; a.length = d->length; a.score = d->score;
+    b.M = d->M; b.iou_num = d->iou_num; b.iou_den = d->iou_den;
+    hipLaunchKernelGGL(moment_nbest_kernel, dim3((unsigned)(d->Nq * d->K)), dim3(256), 0, stream, b);
     UNIVL_LAUNCH_CHECK();
     return UNIVL_OK;
 }

@@ -16,7 +16,8 @@ CrossEntropyLoss(ignore_index=-1) of modeling.py:246-254 over a whole loader, wi
 session (univl_amd.score.CaptionScorer).
 
 Localisation: eval_localization scores where in its own video every text is found (retrieval.VideoIndex.localize) against annotated
-segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices.  eval_step_alignment does it for ORDERED lists of steps laid over their video
+segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices, and with n_best = n the R{n}@ columns over the n windows that temporal
+non-maximum suppression leaves.  eval_step_alignment does it for ORDERED lists of steps laid over their video
 jointly (retrieval.VideoIndex.align_steps): step recall by the centre frame of every step's window, and mIoU."""
 import contextlib
 import math
@@ -128,16 +129,24 @@ def eval_retrieval_streamed(model, text_batches, video_batches, targets, device=
 
 
 @torch.no_grad()
-def eval_localization(model, index, text_batches, targets, gt_start, gt_len, window, device="cuda"):
+def eval_localization(model, index, text_batches, targets, gt_start, gt_len, window, device="cuda", n_best=1, nms=(1, 2)):
     """Step localisation: every text is localised in ITS OWN video and the window found is compared with the annotated one.
     index: a retrieval.VideoIndex(model, keep_frames=True) holding the videos; text_batches: iterable of (input_ids, input_mask,
     segment_ids), the loader's order; targets / gt_start / gt_len: for every text row, in order, its gallery row and its annotated
     segment, frames gt_start .. gt_start + gt_len - 1 (gt_len >= 1); window = (lmin, lmax): the lengths searched
     (VideoIndex.localize).  Temporal IoU over frame indices; a threshold is decided in integers (10 * inter >= 3 * union, ...), so no
     rounding enters a count.  A text whose video has no candidate window counts as IoU 0 and is reported in n_empty.
-    Returns {"mIoU", "R1@0.3", "R1@0.5", "R1@0.7"} (fractions of the n texts; mIoU a float64 mean taken on the host), "n", "n_empty"."""
+    Returns {"mIoU", "R1@0.3", "R1@0.5", "R1@0.7"} (fractions of the n texts; mIoU a float64 mean taken on the host), "n", "n_empty".
+    n_best = n > 1 (at most MOMENT_NBEST_MAX): every text is localised with VideoIndex.localize(n_best=n, nms=nms) and the dictionary
+    gains "R{n}@0.3", "R{n}@0.5", "R{n}@0.7": a text counts if ANY of its n windows meets the same integer threshold -- the "R@n, IoU = m"
+    columns of the moment-retrieval tables.  mIoU, R1@ and n_empty are those of slot 0, the window of n_best = 1.  Still one host read."""
+    from .retrieval import check_nbest
     if index.model is not model:
         raise ValueError("eval_localization: the index belongs to another model")
+    if n_best is None:
+        raise ValueError("eval_localization: n_best=None, need an integer (1: the best window alone)")
+    check_nbest("eval_localization", n_best, nms)
+    many = {"n_best": n_best, "nms": nms} if n_best > 1 else {}           # n_best = 1: the call, the launch and the dictionary of before
     as_i32 = lambda x: torch.as_tensor(x).reshape(-1).to(device=device, dtype=torch.int32)
     targets, gt_start, gt_len = as_i32(targets), as_i32(gt_start), as_i32(gt_len)
     n = targets.numel()
@@ -148,21 +157,25 @@ def eval_localization(model, index, text_batches, targets, gt_start, gt_len, win
     starts, lengths = [], []
     with _eval_mode(model):
         for input_ids, segment_ids, input_mask, row, b in _text_rows("eval_localization", text_batches, n, device):
-            s, l, _ = index.localize(input_ids, segment_ids, input_mask, targets[row:row + b].reshape(b, 1), window)
-            starts.append(s.reshape(-1))
-            lengths.append(l.reshape(-1))
+            s, l, _ = index.localize(input_ids, segment_ids, input_mask, targets[row:row + b].reshape(b, 1), window, **many)
+            starts.append(s.reshape(b, -1))
+            lengths.append(l.reshape(b, -1))
     if n == 0:
         raise ValueError("eval_localization: no texts")
-    s, l = torch.cat(starts), torch.cat(lengths)                          # an empty result is (-1, 0): it meets no frame
-    inter = (torch.minimum(s + l, gt_start + gt_len) - torch.maximum(s, gt_start)).clamp_(min=0)
+    s, l = torch.cat(starts), torch.cat(lengths)                          # [n, n_best]; an empty slot is (-1, 0): it meets no frame
+    g0, g1 = gt_start[:, None], (gt_start + gt_len)[:, None]
+    inter = (torch.minimum(s + l, g1) - torch.maximum(s, g0)).clamp_(min=0)
     inter = torch.where(l > 0, inter, torch.zeros_like(inter))
-    union = l + gt_len - inter
+    union = l + gt_len[:, None] - inter
     host = torch.stack([inter, union, l]).cpu().numpy().astype(np.int64)  # the one host read
     inter, union, l = host
-    out = {"mIoU": float(np.mean(inter.astype(np.float64) / union.astype(np.float64)))}
+    out = {"mIoU": float(np.mean(inter[:, 0].astype(np.float64) / union[:, 0].astype(np.float64)))}
     for name, num in (("R1@0.3", 3), ("R1@0.5", 5), ("R1@0.7", 7)):
-        out[name] = float(np.sum(10 * inter >= num * union)) / n
-    out["n"], out["n_empty"] = n, int(np.sum(l == 0))
+        out[name] = float(np.sum(10 * inter[:, 0] >= num * union[:, 0])) / n
+    out["n"], out["n_empty"] = n, int(np.sum(l[:, 0] == 0))
+    if n_best > 1:
+        for num in (3, 5, 7):
+            out["R%d@0.%d" % (n_best, num)] = float(np.sum(np.any(10 * inter >= num * union, axis=1))) / n
     return out
 
 

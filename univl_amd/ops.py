@@ -850,6 +850,32 @@ def moment_localize(q, frames, mask, rows, lmin, lmax, *, wnorm=None, normalize=
     return start, length, score
 
 
+def moment_nbest(q, frames, mask, rows, lmin, lmax, n_best, nms=(1, 2), *, wnorm=None, normalize=True):
+    """The n_best windows of gallery row rows[i, j] for query row i after greedy temporal non-maximum suppression, in one launch
+    (include/univl_hip.h: univl_moment_nbest).  Arguments as moment_localize's; 1 <= n_best <= MOMENT_NBEST_MAX; nms = (num, den),
+    integers with 1 <= den <= 1024 and 0 <= num <= den: a window dies when its temporal IoU with a pick exceeds num / den, decided
+    in integers (den * inter > num * union).  (1, 1) is the plain top n_best, (0, 1) gives disjoint windows.  Returns (start, length,
+    score), [Nq, K, n_best] int32, int32, fp32: slot 0 is moment_localize's triple bit for bit, the scores of a pair never increase
+    from slot to slot, and the slots past the last surviving window -- all of them for a row id outside the gallery -- are
+    (-1, 0, -inf)."""
+    d = _moment_gallery(frames, mask, normalize, _lib.MomentNbest)
+    _require_gpu(q, rows, wnorm)
+    _row_views(q)
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == q.shape[0] and rows.is_contiguous()
+    if q.shape[1] != frames.shape[2]:
+        raise RuntimeError("moment_nbest: q is %d wide, the frames %d" % (q.shape[1], frames.shape[2]))
+    _moment_table("moment_nbest", d, wnorm, normalize)
+    d.q, d.ldq, d.rows, d.Nq, d.K, d.lmin, d.lmax = _p(q), _ld(q), _p(rows), rows.shape[0], rows.shape[1], int(lmin), int(lmax)
+    d.M, d.iou_num, d.iou_den = int(n_best), int(nms[0]), int(nms[1])
+    M = max(d.M, 0)                                   # a bad n_best is the library's to refuse, with its message
+    start = torch.empty(d.Nq, d.K, M, dtype=torch.int32, device=q.device)
+    length = torch.empty(d.Nq, d.K, M, dtype=torch.int32, device=q.device)
+    score = torch.empty(d.Nq, d.K, M, dtype=torch.float32, device=q.device)
+    d.start, d.length, d.score = _p(start), _p(length), _p(score)
+    _lib.check(_lib.lib().univl_moment_nbest(_BYREF(d), _stream()), "moment_nbest")
+    return start, length, score
+
+
 def step_align(q, counts, frames, mask, rows, lmin, lmax, wnorm=None, normalize=True):
     """Lays ordered lists of step vectors over gallery rows (include/univl_hip.h: univl_step_align): for list i and gallery row
     rows[i, c], the windows (start, length) of its first counts[i] steps -- each of lmin .. lmax valid frames, in order, never

@@ -15,7 +15,8 @@ column term (include/univl_hip.h: univl_sim_colstat, univl_sim_topk_norm).  No r
 
 Moment search says WHERE in a video a text matches: VideoIndex(keep_frames=True).localize() scores every window of frames of a
 candidate video the way get_similarity_logits scores the whole video (include/univl_hip.h: univl_window_norms,
-univl_moment_localize) and returns the best one; search_moments() does that for the best videos of a search and ranks the moments.
+univl_moment_localize) and returns the best one -- or, with n_best=, the n best after temporal non-maximum suppression
+(univl_moment_nbest); search_moments() does that for the best videos of a search and ranks the moments.
 
 Step alignment says where every step of an ORDERED list of texts happens: align_steps() places all of them at once, in order and
 without overlap, by the same window score (univl_step_align) -- action step localisation."""
@@ -28,6 +29,7 @@ import torch
 from . import _lib, ops
 
 H = 768
+_NMS = (1, 2)              # the default suppression threshold of n-best localisation: temporal IoU above 1 / 2 (check_nbest knows it by identity)
 
 
 class VideoIndex:
@@ -190,22 +192,32 @@ class VideoIndex:
         return self._wnorm[:n]
 
     @torch.no_grad()
-    def localize(self, input_ids, token_type_ids, attention_mask, rows, window):
+    def localize(self, input_ids, token_type_ids, attention_mask, rows, window, n_best=None, nms=_NMS):
         """The best-matching window of frames of gallery row rows[i, j] for text i.  rows: [Nq, K] int32 gallery rows, search()'s
         indices say; window = (lmin, lmax): the lengths searched, in frames.  Returns (start, length, score), each [Nq, K] on the
         device: the window whose masked mean -- normalised unless use_mil, as get_similarity_logits scores a whole video -- has the
         largest inner product with the pooled text; equal scores by lower start, then smaller length; (-1, 0, -inf) where no window of
-        these lengths lies inside the valid frames, and for the -1 rows of a short search.  Needs keep_frames=True."""
-        return self.localize_vectors(self.pool_text(input_ids, token_type_ids, attention_mask)[0], rows, window)
+        these lengths lies inside the valid frames, and for the -1 rows of a short search.  Needs keep_frames=True.
+        n_best (an integer, 1 .. MOMENT_NBEST_MAX): SEVERAL windows per pair, each result [Nq, K, n_best] -- greedy temporal
+        non-maximum suppression in one launch (include/univl_hip.h: univl_moment_nbest): the best window, then the best of those whose
+        IoU in frames with every window taken so far is at most num / den, nms = (num, den) integers with 1 <= den <= 1024 and
+        0 <= num <= den, decided in integers.  Slot 0 is the window of the call without n_best, scores never increase along a pair's
+        slots, and the slots past the last survivor are (-1, 0, -inf).  nms=(1, 1) is the plain top n_best, (0, 1) disjoint windows."""
+        check_nbest("VideoIndex.localize", n_best, nms)
+        return self.localize_vectors(self.pool_text(input_ids, token_type_ids, attention_mask)[0], rows, window, n_best, nms)
 
     @torch.no_grad()
-    def localize_vectors(self, q, rows, window):
+    def localize_vectors(self, q, rows, window, n_best=None, nms=_NMS):
         """localize() for pooled query vectors the caller already holds ([Nq, 768] fp32 on the index's device)."""
+        check_nbest("VideoIndex.localize_vectors", n_best, nms)
         lmin, lmax = self._check_window("localize", window)
         q = _query_rows(q)
         rows = torch.as_tensor(rows).to(device=q.device, dtype=torch.int32).reshape(q.shape[0], -1).contiguous()
         wnorm = self._window_norms() if self.normalize else None
-        return ops.moment_localize(q, self._frames[:self._n], self._fmask[:self._n], rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
+        frames, mask = self._frames[:self._n], self._fmask[:self._n]
+        if n_best is None:
+            return ops.moment_localize(q, frames, mask, rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
+        return ops.moment_nbest(q, frames, mask, rows, lmin, lmax, n_best, nms, wnorm=wnorm, normalize=self.normalize)
 
     def _check_window(self, who, window):
         """(lmin, lmax) of a localisation, or the ValueError every localiser raises: no frames kept, a bad window, videos too long."""
@@ -253,15 +265,22 @@ class VideoIndex:
         return lists.shape[0], lists.shape[1], lmin, lmax
 
     @torch.no_grad()
-    def search_moments(self, input_ids, token_type_ids, attention_mask, k=10, window=(1, 1), shortlist=None, bank=None):
+    def search_moments(self, input_ids, token_type_ids, attention_mask, k=10, window=(1, 1), shortlist=None, bank=None, per_video=1, nms=_NMS):
         """The k best (video, window) moments for every text.  The `shortlist` (default k, at most TOPK_MAX) best videos by WHOLE-VIDEO
         score come from search_vectors -- through `bank` if one is given -- each is localised, and the shortlist is re-ordered by window
         score.  So the result is exhaustive over the index when shortlist >= len(index) and otherwise what it says: the best moments
         among the videos a whole-video search ranks first; a moment in a video that scores poorly as a whole is not found.
         Returns (score, idx, start, length), each [Nq, k] on the device, rows by descending window score, equal scores by lower row
         id first; videos without a candidate window come last (start -1, length 0, score -inf), the -1 rows of a short gallery after
-        them."""
+        them.
+        per_video=P > 1 (at most MOMENT_NBEST_MAX): every video of the shortlist is localised with n_best=P under nms (localize) and
+        the shortlist * P moments are ranked -- window score descending, then lower row id, then the earlier pick of a video -- so a
+        video may appear up to P times in a row of the result; 1 <= k <= shortlist * P, the shortlist itself (default: k, cut to
+        TOPK_MAX) still at most TOPK_MAX.  The empty slots of a video that has fewer than P windows rank with the videos without one."""
         k = int(k)
+        if per_video != 1:
+            return self._search_moments_nbest(input_ids, token_type_ids, attention_mask, k, window, shortlist, bank, per_video, nms)
+        check_nms("VideoIndex.search_moments", nms)
         shortlist = k if shortlist is None else int(shortlist)
         if not 1 <= k <= shortlist <= _lib.TOPK_MAX:
             raise ValueError("VideoIndex.search_moments: k=%d shortlist=%d, need 1 <= k <= shortlist <= %d" % (k, shortlist, _lib.TOPK_MAX))
@@ -270,6 +289,22 @@ class VideoIndex:
         q = self.pool_text(input_ids, token_type_ids, attention_mask)[0]
         _, idx = self.search_vectors(q, shortlist, None, bank)
         start, length, score = self.localize_vectors(q, idx, window)
+        sc, order = _rank_rows(score, idx, k)
+        return sc, idx.gather(1, order), start.gather(1, order), length.gather(1, order)
+
+    def _search_moments_nbest(self, input_ids, token_type_ids, attention_mask, k, window, shortlist, bank, P, nms):
+        who = "VideoIndex.search_moments"
+        check_nbest(who, P, nms, "per_video")
+        shortlist = min(k, _lib.TOPK_MAX) if shortlist is None else int(shortlist)
+        if not (1 <= shortlist <= _lib.TOPK_MAX and 1 <= k <= shortlist * P):
+            raise ValueError("%s: k=%d shortlist=%d per_video=%d, need 1 <= shortlist <= %d and 1 <= k <= shortlist * per_video"
+                             % (who, k, shortlist, P, _lib.TOPK_MAX))
+        if not self.keep_frames:
+            raise ValueError("%s needs an index built with keep_frames=True" % who)
+        q = self.pool_text(input_ids, token_type_ids, attention_mask)[0]
+        _, idx = self.search_vectors(q, shortlist, None, bank)
+        start, length, score = (t.flatten(1) for t in self.localize_vectors(q, idx, window, P, nms))
+        idx = idx.repeat_interleave(P, dim=1)             # column j * P + m: pick m of shortlist video j; the stable sorts keep m's order
         sc, order = _rank_rows(score, idx, k)
         return sc, idx.gather(1, order), start.gather(1, order), length.gather(1, order)
 
@@ -402,6 +437,24 @@ def _grown(buf, filled, cap, *shape, device, dtype=torch.float32, zero=False):
     if buf is not None and filled:
         new[:filled].copy_(buf[:filled])
     return new
+
+
+def check_nms(who, nms):
+    """The ValueError of a suppression threshold nms = (num, den), before any device work."""
+    ok = isinstance(nms, (tuple, list)) and len(nms) == 2 and all(isinstance(x, numbers.Integral) and not isinstance(x, bool) for x in nms)
+    if not ok or not (1 <= nms[1] <= 1024 and 0 <= nms[0] <= nms[1]):
+        raise ValueError("%s: nms=%r, need a pair of integers (num, den) with 1 <= den <= 1024 and 0 <= num <= den" % (who, nms))
+
+
+def check_nbest(who, n_best, nms, name="n_best"):
+    """The ValueErrors of (n_best=, nms=), before any device work: n_best None is one window per pair, and then nms must be left alone."""
+    if n_best is None:
+        if nms is not _NMS:
+            raise ValueError("%s: nms=%r without %s; suppression needs more than one window per pair" % (who, nms, name))
+        return
+    if isinstance(n_best, bool) or not isinstance(n_best, numbers.Integral) or not 1 <= n_best <= _lib.MOMENT_NBEST_MAX:
+        raise ValueError("%s: %s=%r, need an integer in [1, %d]" % (who, name, n_best, _lib.MOMENT_NBEST_MAX))
+    check_nms(who, nms)
 
 
 def check_bank_args(beta, hub_k):
