@@ -1000,6 +1000,67 @@ typedef struct UnivlStepAlign {
 } UnivlStepAlign;
 int univl_step_align_sizeof(void);
 int univl_step_align(const UnivlStepAlign* d, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- frame-wise segmentation
+ * WHICH of a SET of texts, if any, every frame of a video shows (action segmentation; COIN's frame accuracy is counted over such
+ * labels): the question of the three entries above asked from the video's side.  No order among the labels, a label may occur in
+ * several runs or not at all, and a background label stands for "none of these".  The gallery side -- frames, ld_row, mask, wnorm, N,
+ * F, H, normalize -- is UnivlMoment's.
+ * For label set i (its counts[i] = n label vectors q[i, 0 .. n - 1]; K is only the padding of a set) and gallery row v = rows[i, c],
+ * let f_0 < .. < f_{T-1} be the frames of v with mask != 0; a hole in the mask is simply skipped, the frames on its two sides are
+ * neighbours.  lambda = switch_penalty, b = background.
+ *   e(k, t)     k < n: the score univl_moment_localize gives window (f_t, 1) for q[i, k], bit for bit -- one frame product divided by
+ *               max(wnorm[v][f_t][0], 1e-12), or by 1 with normalize = 0.  The background label has index n and e(n, t) = b; b = -inf
+ *               means there is no background label
+ *   objective   the labelling y_0 .. y_{T-1} of largest  sum_t e(y_t, t) - lambda * #{t >= 1 : y_t != y_{t-1}}
+ *   result      EQUAL objectives and the fp32 order of the sums are decided by this suffix programme, which is the contract (all
+ *               of it additions, subtractions and comparisons in fp32; y ranges over 0 .. n, labels before the background):
+ *                 V[T-1][y] = e(y, T-1);   M[t] = max over y of V[t][y];   a[t] = the lowest y with V[t][y] == M[t]
+ *                 V[t][y]   = e(y, t) + max(V[t+1][y], M[t+1] - lambda)
+ *                 stay[t][y] = V[t+1][y] >= M[t+1] - lambda                                        -- a tie stays
+ *                 walk forward: y_0 = a[0];  y_{t+1} = y_t if stay[t][y_t], else a[t+1];  total = M[0]
+ *   outputs     label (int32) [Nl, C, F]: k for a label, -1 for the background, -2 on a masked frame; score (fp32) [Nl, C, F]: e(y_t, t)
+ *               of the label chosen, -inf on a masked frame; total (fp32) [Nl, C]; nseg (int32) [Nl, C]: the maximal runs of equal
+ *               NON-background labels over the valid frames in order.  All of them are written for every pair.
+ *   nothing to label   a row outside [0, N), counts[i] outside [1, K], or a row without a valid frame: label -2 and score -inf on all
+ *               F frames, total -inf, nseg 0.  The first two are decided for the whole workgroup before anything of the gallery or of
+ *               q is read.  q rows k >= counts[i] are never read
+ * Consequences: lambda = 0 is the arg-max of every frame by itself -- among equal scores the lowest label and the background last,
+ * except that a label which is among the equals of the next frame too is kept (a tie stays); a lambda larger than every difference of
+ * two sums of scores gives one label for the whole video; with n = 1 and b = -inf every valid frame gets label 0.
+ * One workgroup of 256 threads per (set, candidate): the frame products d[k][f] = q_k . x_f into LDS as univl_step_align makes them,
+ * turned into e(k, f) in place by univl_moment_localize's own visit of window (f, 1); then ONE wave runs the programme over the valid
+ * frames from the last to the first -- lane y holds V[.][y] and every lane the background's value, so UNIVL_SEGMENT_K_MAX labels and
+ * the background fit one wave; a frame costs one max butterfly over the wave, one ballot for a[t] (the maximum is exact, so the lowest
+ * lane that holds it is the lowest label that attains it), one ballot for stay[t][.] and one addition -- and walks forward.  The stay
+ * words (64 bits and the background's bit per frame) and a[.] never leave the registers.  LDS: 33 KB of scores (pitch 129 floats, so
+ * that the wave reads a column from 64 banks), 1.5 KB of one-frame norms, mask and valid-frame list.  One launch, no workspace, no
+ * host read, no atomics, capturable.
+ * PURITY: a pair's result is a function of its n vectors, the row's frames, mask and table, lambda, b and normalize only -- not of its
+ * place in the launch, the other pairs, K, C or deterministic mode.
+ * Range: UnivlMoment's for the gallery side; 1 <= K <= UNIVL_SEGMENT_K_MAX, Nl >= 1, C >= 1, Nl * C < 2^31, ldq >= 768 (a set's vectors
+ * are ldq floats apart, sets K * ldq), switch_penalty finite and >= 0, background a number or -inf (not NaN, not +inf); otherwise, or
+ * for a NULL pointer (wnorm may be NULL with normalize = 0), UNIVL_EINVAL; rows of frames and q 16-byte aligned (UNIVL_EALIGN); all
+ * before any launch.  Behaviour on NaN values in q or the frames: unspecified (no access leaves the buffers). */
+#define UNIVL_SEGMENT_K_MAX 64
+typedef struct UnivlFrameSegment {
+    const float* frames; int64_t ld_row; /* [N, F, 768] fp32 frames of the gallery rows, ld_row floats between rows               */
+    const int64_t* mask;                 /* [N, F] int64, contiguous: 0 = not a frame                                             */
+    const float* wnorm;                  /* [N, F, F] fp32 from univl_window_norms (may be NULL with normalize = 0)               */
+    int32_t N, F, H;                     /* H must be 768                                                                         */
+    int32_t normalize;
+    const float* q; int64_t ldq;         /* [Nl, K, ldq] fp32 pooled label vectors                                                */
+    const int32_t* counts;               /* [Nl] on the device: the labels of set i are its first counts[i] vectors               */
+    const int32_t* rows;                 /* [Nl, C] candidate gallery rows                                                        */
+    int32_t Nl, C, K;
+    float switch_penalty, background;    /* lambda >= 0, finite; b: the score of the background label on every frame, or -inf     */
+    int32_t reserved;
+    int32_t* label;                      /* [Nl, C, F] written: k, -1 background, -2 masked                                       */
+    float* score;                        /* [Nl, C, F] written                                                                    */
+    float* total;                        /* [Nl, C] written                                                                       */
+    int32_t* nseg;                       /* [Nl, C] written                                                                       */
+} UnivlFrameSegment;
+int univl_frame_segment_sizeof(void);
+int univl_frame_segment(const UnivlFrameSegment* d, hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

@@ -1,13 +1,14 @@
-// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize, univl_moment_nbest, univl_step_align):
-// the best-matching window of frames of a gallery video for a pooled text vector, every window of the video scored in ONE launch --
-// or its n best windows after temporal non-maximum suppression -- and, for an ORDERED list of step vectors, the best in-order,
-// non-overlapping windows of all of them at once.
+// Moment search on the device (include/univl_hip.h: univl_window_norms, univl_moment_localize, univl_moment_nbest, univl_step_align,
+// univl_frame_segment): the best-matching window of frames of a gallery video for a pooled text vector, every window of the video
+// scored in ONE launch -- or its n best windows after temporal non-maximum suppression -- for an ORDERED list of step vectors, the best
+// in-order, non-overlapping windows of all of them at once -- and, from the video's side, the label (or none) of every frame out of a
+// SET of label vectors.
 //
 // A window (s, L) covers frames s .. s + L - 1 of a row; u(s, L) is the sum of its frame vectors.  The score is the model's own --
 // the masked mean over the window, L2-normalised unless use_mil, dotted with the query -- written without the mean:
 //   normalising   (q . u) / max(|u|, 1e-12 L)          use_mil   (q . u) / L
 //
-// Four kernels, no host read, no LDS staging of frames, no float atomics, capturable:
+// Five kernels, no host read, no LDS staging of frames, no float atomics, capturable:
 //   norms      |u(s, L)| of every window of a row, a [F][F] table indexed (s, L - 1).  It depends on the video alone, so an index
 //              computes it once per row.  ONE WAVE OWNS A START s: lane l keeps the 12 columns 4 l + 256 j + c (j < 3, c < 4) of the
 //              running sum u(s, .) in registers, adds frame s + L - 1 to it (three 16-byte loads per lane, the next frame's already in
@@ -35,6 +36,13 @@
 //              start >= t that attains it; thread 0 walks forward from (k, t) = (0, 0) and writes the windows, re-growing each chosen
 //              window's numerator (at most F additions in all).  Only the lengths and first starts are kept per step (one byte each):
 //              26 KB of LDS, of which the products are 16.  Two barriers per step.
+//   segment   one workgroup of 256 threads per (label set, candidate) pair.  The same frame products for every label vector, then every
+//              thread turns its share of them into frame scores e(k, f) in place -- localize's visit of window (f, 1) -- and wave 0 runs
+//              the suffix programme of the contract over the valid frames, last to first: lane y holds V[.][y], every lane the
+//              background's value, so 64 labels and the background fit one wave; a frame costs one max butterfly, two ballots (who
+//              attains the maximum, who stays) and one add.  The stay words and first maxima stay in registers, frame t's in lane
+//              t & 63; the forward walk reads them by lane index.  Two barriers in all.  34 KB of LDS, of which the scores are 32 (pitch
+//              129: the wave reads a column).
 //
 // PURITY.  |u(s, L)| is a function of the row's frames s .. s + L - 1 alone, d_f of (q, x_f) alone, a numerator of d_s .. d_{s+L-1}
 // in ascending order: no value depends on the grid, the pair's place in the launch, the other pairs or deterministic mode.  Every sum
@@ -381,7 +389,131 @@ __global__ __launch_bounds__(256) void step_align_kernel(AlignArgs a) {
     }
 }
 
-// the checks every entry point shares: the descriptor itself and its gallery side (UnivlMoment and UnivlStepAlign name it alike)
+struct SegArgs {
+    const float* q; long ldq;
+    const float* frames; long ld_row;
+    const int64_t* mask;
+    const float* wnorm;
+    const int32_t* counts; const int32_t* rows;
+    int N, F, C, K, normalize;
+    float lambda, bg;
+    int32_t* label; float* score; float* total; int32_t* nseg;
+};
+
+__global__ __launch_bounds__(256) void frame_segment_kernel(SegArgs a) {
+    constexpr int FM = UNIVL_MOMENT_F_MAX, KM = UNIVL_SEGMENT_K_MAX;
+    constexpr int LD = FM + 1;                       // odd pitch: wave 0 reads a COLUMN of e (lane y, frame f) from 64 different banks
+    __shared__ float e[KM * LD];                     // d[k][f] = q_k . x_f, then e(k, f) in place                  32.25 KB
+    __shared__ float w1[FM];                         // the one-frame entries of the row's norm table
+    __shared__ int valid[FM];
+    __shared__ int vf[FM];                           // vf[t] = f_t, the t-th valid frame
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = a.F;
+    const long p = blockIdx.x, set = p / a.C;
+    const int cand = a.rows[p], n = a.counts[set];
+    int32_t* label = a.label + p * F;
+    float* score = a.score + p * F;
+    if (cand < 0 || cand >= a.N || n < 1 || n > a.K) {                    // block-uniform: nothing of the gallery or of q is read
+        if (tid < F) { label[tid] = -2; score[tid] = -INFINITY; }
+        if (tid == 0) { a.total[p] = -INFINITY; a.nseg[p] = 0; }
+        return;
+    }
+    frame_products(a.q + set * a.K * a.ldq, a.ldq, n, a.frames + (long)cand * a.ld_row, F, e, LD, lane, wave);
+    if (tid < FM) {
+        const int ok = (tid < F && a.mask[(long)cand * F + tid] != 0) ? 1 : 0;
+        valid[tid] = ok;
+        w1[tid] = (ok && a.normalize) ? a.wnorm[((long)cand * F + tid) * F] : 0.f;
+        if (tid < F && !ok) { label[tid] = -2; score[tid] = -INFINITY; }  // a masked frame: no other thread writes it
+    }
+    __syncthreads();
+
+    // e(k, f) over d[k][f] in place: the visit univl_moment_localize makes of window (f, 1), so the score is its score bit for bit
+    for (int i = tid; i < n * F; i += 256) {
+        const int k = i / F, f = i - k * F;
+        float* row = e + k * LD;
+        windows_from(row, valid, w1 + f, F, f, 1, 1, a.normalize, [&](int, float w) { row[f] = w; });
+    }
+    unsigned long long b0 = 0, b1 = 0;                                    // the valid frames, as wave 0 sees them
+    if (wave == 0) {
+        const int v0 = valid[lane], v1 = valid[lane + 64];
+        b0 = __ballot(v0);
+        b1 = __ballot(v1);
+        const unsigned long long below = (1ull << lane) - 1;
+        if (v0) vf[__popcll(b0 & below)] = lane;
+        if (v1) vf[__popcll(b0) + __popcll(b1 & below)] = lane + 64;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    const int T = __popcll(b0) + __popcll(b1);
+    if (T == 0) {                                                         // wave-uniform: nothing to label
+        if (lane == 0) { a.total[p] = -INFINITY; a.nseg[p] = 0; }
+        return;
+    }
+
+    // The suffix programme.  Lane y < n holds V[.][y]; every lane carries the background's V[.][n].  Frame t leaves two words behind,
+    // in lane t & 63 (w0, m0 for t < 64, w1, m1 above): the ballot of stay[t][.] and a[t] + 128 * stay[t][n].
+    const bool mine = lane < n;
+    const float* col = e + lane * LD;                                     // read by the lanes y < n alone
+    const float lambda = a.lambda, bg = a.bg;
+    float V = mine ? col[vf[T - 1]] : -INFINITY, Vb = bg, M;
+    int arg;
+    unsigned long long s0 = 0, s1 = 0;
+    int m0 = 0, m1 = 0;
+    // M[t] and a[t]: the maximum over the wave is exact, so the lowest lane that holds it is the lowest label that attains it -- the
+    // (value, index) fold of keep_first_max, with one value per exchange; the background enters last and only if strictly larger
+    auto top = [&]() {
+        M = wave_max(V);
+        const unsigned long long at = __ballot(mine && V == M);
+        arg = at ? __ffsll(at) - 1 : n;                                   // (no lane: NaN input, unspecified -- but never an index outside e)
+        if (Vb > M) { M = Vb; arg = n; }
+    };
+    auto keep = [&](int t, unsigned long long word, int m) {
+        if (lane == (t & 63)) {
+            if (t < 64) { s0 = word; m0 = m; } else { s1 = word; m1 = m; }
+        }
+    };
+    top();
+    keep(T - 1, 0ull, arg);
+    float enext = (mine && T >= 2) ? col[vf[T - 2]] : 0.f;
+    for (int t = T - 2; t >= 0; --t) {
+        const float ecur = enext;
+        if (mine && t > 0) enext = col[vf[t - 1]];                        // the next frame's score is in flight during this one's fold
+        const float thr = M - lambda;
+        const bool sb = Vb >= thr;                                        // a tie stays
+        const unsigned long long word = __ballot(mine && V >= thr);
+        V = mine ? ecur + fmaxf(V, thr) : -INFINITY;
+        Vb = bg + fmaxf(Vb, thr);
+        top();
+        keep(t, word, arg | (sb ? 128 : 0));
+    }
+
+    // the walk, wave-uniform: lane t & 63 keeps y_t
+    int y = 0, prev = -1, runs = 0, y0 = 0, y1 = 0, pm = 0;
+    unsigned long long pw = 0;
+    for (int t = 0; t < T; ++t) {
+        const unsigned long long word = t < 64 ? __shfl(s0, t, 64) : __shfl(s1, t - 64, 64);
+        const int m = t < 64 ? __shfl(m0, t, 64) : __shfl(m1, t - 64, 64);
+        const bool stay = t > 0 && (y == n ? (pm >> 7) & 1 : (int)((pw >> y) & 1));
+        if (!stay) y = m & 127;
+        runs += (y != n && y != prev) ? 1 : 0;
+        prev = y; pw = word; pm = m;
+        if (lane == (t & 63)) {
+            if (t < 64) y0 = y; else y1 = y;
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int t = lane + 64 * h, yy = h ? y1 : y0;
+        if (t < T) {
+            const int f = vf[t];
+            label[f] = yy == n ? -1 : yy;
+            score[f] = yy == n ? bg : e[yy * LD + f];
+        }
+    }
+    if (lane == 0) { a.total[p] = M; a.nseg[p] = runs; }
+}
+
+// the checks every entry point shares: the descriptor itself and its gallery side (UnivlMoment, UnivlStepAlign and UnivlFrameSegment
+// name it alike)
 template <typename D>
 int check_gallery(const char* who, const D* d) {
     UNIVL_CHECK_ARG(d != nullptr, UNIVL_EINVAL, "%s: null descriptor", who);
@@ -469,6 +601,35 @@ extern "C" int univl_moment_nbest(const UnivlMomentNbest* d, hipStream_t stream)
 }
 
 extern "C" int univl_step_align_sizeof(void) { return (int)sizeof(UnivlStepAlign); }
+
+extern "C" int univl_frame_segment_sizeof(void) { return (int)sizeof(UnivlFrameSegment); }
+
+extern "C" int univl_frame_segment(const UnivlFrameSegment* d, hipStream_t stream) {
+    UNIVL_ON_STREAM_DEVICE(stream);
+    const char* who = "univl_frame_segment";
+    const int rc = check_gallery(who, d);
+    if (rc != UNIVL_OK) return rc;
+    UNIVL_CHECK_ARG(d->K >= 1 && d->K <= UNIVL_SEGMENT_K_MAX, UNIVL_EINVAL, "%s: K=%d (1 <= K <= %d)", who, d->K, UNIVL_SEGMENT_K_MAX);
+    UNIVL_CHECK_ARG(d->Nl >= 1 && d->C >= 1 && (int64_t)d->Nl * d->C <= INT_MAX, UNIVL_EINVAL, "%s: Nl=%d C=%d (both >= 1, Nl * C < 2^31)", who,
+                    d->Nl, d->C);
+    UNIVL_CHECK_ARG(d->switch_penalty >= 0.f && d->switch_penalty <= FLT_MAX, UNIVL_EINVAL, "%s: switch_penalty=%g (finite, >= 0)", who,
+                    (double)d->switch_penalty);
+    UNIVL_CHECK_ARG(d->background <= FLT_MAX, UNIVL_EINVAL, "%s: background=%g (a number or -inf)", who, (double)d->background);
+    UNIVL_CHECK_ARG(d->q && d->counts && d->rows && d->label && d->score && d->total && d->nseg, UNIVL_EINVAL,
+                    "%s: null pointer (q, counts, rows, label, score, total, nseg)", who);
+    UNIVL_CHECK_ARG(!d->normalize || d->wnorm != nullptr, UNIVL_EINVAL, "%s: null pointer (wnorm with normalize)", who);
+    UNIVL_CHECK_ARG(rows768_pitch(d->ldq), UNIVL_EINVAL, "%s: ldq=%lld (>= 768)", who, (long long)d->ldq);
+    UNIVL_CHECK_ARG(rows768_aligned(d->q, d->ldq), UNIVL_EALIGN, "%s: rows of q must be 16-byte aligned", who);
+    SegArgs a;
+    a.q = d->q; a.ldq = (long)d->ldq; a.frames = d->frames; a.ld_row = (long)d->ld_row; a.mask = d->mask; a.wnorm = d->wnorm;
+    a.counts = d->counts; a.rows = d->rows;
+    a.N = d->N; a.F = d->F; a.C = d->C; a.K = d->K; a.normalize = d->normalize;
+    a.lambda = d->switch_penalty; a.bg = d->background;
+    a.label = d->label; a.score = d->score; a.total = d->total; a.nseg = d->nseg;
+    hipLaunchKernelGGL(frame_segment_kernel, dim3((unsigned)(d->Nl * d->C)), dim3(256), 0, stream, a);
+    UNIVL_LAUNCH_CHECK();
+    return UNIVL_OK;
+}
 
 extern "C" int univl_step_align(const UnivlStepAlign* d, hipStream_t stream) {
     UNIVL_ON_STREAM_DEVICE(stream);

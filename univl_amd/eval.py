@@ -18,7 +18,8 @@ session (univl_amd.score.CaptionScorer).
 Localisation: eval_localization scores where in its own video every text is found (retrieval.VideoIndex.localize) against annotated
 segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices, and with n_best = n the R{n}@ columns over the n windows that temporal
 non-maximum suppression leaves.  eval_step_alignment does it for ORDERED lists of steps laid over their video
-jointly (retrieval.VideoIndex.align_steps): step recall by the centre frame of every step's window, and mIoU."""
+jointly (retrieval.VideoIndex.align_steps): step recall by the centre frame of every step's window, and mIoU.  eval_segmentation
+labels every frame of a video out of a set of label texts (retrieval.VideoIndex.segment) and counts COIN's frame accuracy."""
 import contextlib
 import math
 import os
@@ -240,6 +241,68 @@ def eval_step_alignment(model, index, step_batches, targets, gt_start, gt_len, w
     on = annotated != 0
     return {"recall": float(hit.sum()) / n_steps, "mIoU": float(np.mean(inter[on].astype(np.float64) / union[on].astype(np.float64))),
             "n_lists": n, "n_steps": n_steps, "n_infeasible": int(host[4 * n * K:].sum()), "hits": hit.sum(1), "annotated": annotated.sum(1)}
+
+
+def eval_segmentation(model, index, label_batches, targets, gt_labels, switch_penalty=0.0, background=None, device="cuda"):
+    """Action segmentation: every frame of a video gets one of a set of label texts or the background (VideoIndex.segment), each set in
+    ITS OWN video, and the labels are compared with the annotated ones frame by frame -- COIN's frame accuracy, here in its zero-shot,
+    label-text form.  index: a retrieval.VideoIndex(model, keep_frames=True) holding the videos; label_batches: iterable of (input_ids
+    [b, K, W], input_mask, segment_ids, counts [b]), the loader's order -- a set's labels are its first counts texts; targets [n]: every
+    set's gallery row; gt_labels [n, F] integers: k for label k of the set, -1 for the background, -2 for a frame that is not annotated
+    and is never counted; a frame the video's mask excludes is not counted either.  switch_penalty, background: as VideoIndex.segment's.
+    Every decision is an integer comparison.  Returns, from one host read,
+      "frame_accuracy"      correct / annotated over all annotated valid frames
+      "frame_accuracy_fg"   the same over the frames whose annotation is a label, not the background (NaN without one)
+      "correct", "annotated"   int64 arrays [n]: per set, for a macro average per task
+      "n_lists", "n_frames" (annotated valid frames), "n_segments" (predicted runs of one label), "n_empty" (sets with nothing to
+      label: no valid frame, or a count outside [1, K])."""
+    from .retrieval import check_segment_args
+    if index.model is not model:
+        raise ValueError("eval_segmentation: the index belongs to another model")
+    check_segment_args("eval_segmentation", switch_penalty, background)
+    targets = torch.as_tensor(targets).reshape(-1).to(device=device, dtype=torch.int32)
+    gt = torch.as_tensor(gt_labels).to(device=device, dtype=torch.int32)
+    n = targets.numel()
+    if gt.dim() != 2 or gt.shape[0] != n:
+        raise ValueError("eval_segmentation: %d targets, gt_labels %s (need [lists, frames])" % (n, tuple(gt.shape)))
+    if n == 0:
+        raise ValueError("eval_segmentation: no lists")
+    if int(targets.min()) < 0 or int(targets.max()) >= len(index) or int(gt.min()) < -2:
+        raise ValueError("eval_segmentation: targets must lie in [0, %d) and gt_labels be >= -2" % len(index))
+    labels, totals, nsegs = [], [], []
+    row = 0
+    with _eval_mode(model):
+        for batch in label_batches:
+            input_ids, input_mask, segment_ids, counts = [t.to(device) for t in batch[:4]]
+            b = input_ids.shape[0]
+            if input_ids.dim() != 3 or counts.numel() != b:
+                raise ValueError("eval_segmentation: a batch of shape %s with %d counts (need [lists, labels, words] and one count per list)"
+                                 % (tuple(input_ids.shape), counts.numel()))
+            if row + b > n:
+                raise ValueError("eval_segmentation: more lists than targets (%d)" % n)
+            lab, _, tot, ns = index.segment(input_ids, segment_ids, input_mask, counts, targets[row:row + b].reshape(b, 1), switch_penalty,
+                                            background)
+            if lab.shape[2] != gt.shape[1]:
+                raise ValueError("eval_segmentation: gt_labels holds %d frames per list, the videos %d" % (gt.shape[1], lab.shape[2]))
+            labels.append(lab[:, 0])
+            totals.append(tot[:, 0])
+            nsegs.append(ns[:, 0])
+            row += b
+    if row != n:
+        raise ValueError("eval_segmentation: %d lists for %d targets" % (row, n))
+    lab = torch.cat(labels)                                               # [n, F]; -2 on a masked frame
+    counted = (gt != -2) & (lab != -2)
+    right = counted & (lab == gt)
+    fg = counted & (gt >= 0)
+    per_list = [t.to(torch.int32).sum(1, dtype=torch.int32) for t in (right, counted, right & fg, fg)]
+    host = torch.stack(per_list + [torch.cat(nsegs), torch.isinf(torch.cat(totals)).to(torch.int32)]).cpu().numpy().astype(np.int64)
+    correct, annotated, correct_fg, annotated_fg, nseg, empty = host                                                 # the one host read
+    n_frames, n_fg = int(annotated.sum()), int(annotated_fg.sum())
+    if n_frames == 0:
+        raise ValueError("eval_segmentation: no annotated valid frame")
+    return {"frame_accuracy": float(correct.sum()) / n_frames, "frame_accuracy_fg": float(correct_fg.sum()) / n_fg if n_fg else float("nan"),
+            "correct": correct, "annotated": annotated, "n_lists": n, "n_frames": n_frames, "n_segments": int(nseg.sum()),
+            "n_empty": int(empty.sum())}
 
 
 def ids_to_caption(tokenizer, ids):

@@ -793,7 +793,7 @@ def hub_gate(top1, hub):
 
 
 def _moment_gallery(frames, mask, normalize, desc=_lib.Moment):
-    """The gallery side of a Moment or StepAlign descriptor (window_norms, moment_localize and step_align)."""
+    """The gallery side of a Moment, StepAlign or FrameSegment descriptor (window_norms, moment_localize, step_align, frame_segment)."""
     _require_gpu(frames, mask)
     assert frames.dtype == torch.float32 and frames.dim() == 3 and frames.stride(2) == 1 and frames.stride(1) == frames.shape[2]
     assert mask.dtype == torch.int64 and mask.shape == frames.shape[:2] and mask.is_contiguous()
@@ -903,6 +903,40 @@ def step_align(q, counts, frames, mask, rows, lmin, lmax, wnorm=None, normalize=
     d.start, d.length, d.score, d.total = _p(start), _p(length), _p(score), _p(total)
     _lib.check(_lib.lib().univl_step_align(_BYREF(d), _stream()), "step_align")
     return start, length, score, total
+
+
+def frame_segment(q, counts, frames, mask, rows, switch_penalty, background=None, wnorm=None, normalize=True):
+    """Labels every frame of gallery rows out of sets of label vectors (include/univl_hip.h: univl_frame_segment): for set i and gallery
+    row rows[i, c], the labelling of the row's valid frames -- each frame one of the set's first counts[i] labels or the background --
+    with the largest sum of frame scores minus switch_penalty per change of label between neighbouring valid frames.  A frame's score
+    for a label is moment_localize's score of that one-frame window, bit for bit; for the background it is `background` (None: -inf, no
+    background label).  q: [Nl, K, 768] fp32 (vectors contiguous, K <= SEGMENT_K_MAX; slots past counts[i] are padding and never read);
+    counts: [Nl] int32; frames, mask, wnorm, normalize: as moment_localize's; rows: [Nl, C] int32; switch_penalty: finite, >= 0;
+    background: a number or -inf.  Returns (label [Nl, C, F] int32: k, -1 for the background, -2 on a masked frame; score [Nl, C, F]
+    fp32: the chosen label's frame score, -inf on a masked frame; total [Nl, C] fp32: the objective; nseg [Nl, C] int32: the runs of
+    equal non-background labels).  A row id outside the gallery, a count outside [1, K] or a row without a valid frame is -2 / -inf on
+    every frame with total -inf and nseg 0."""
+    d = _moment_gallery(frames, mask, normalize, _lib.FrameSegment)
+    _require_gpu(q, counts, rows, wnorm)
+    assert q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
+    Nl, K = q.shape[:2]
+    ldq = q.stride(1) if K > 1 else q.stride(0) if Nl > 1 else q.shape[2]           # the stride of a dimension of one means nothing
+    assert Nl == 1 or q.stride(0) == K * ldq, "the sets of q must lie K rows apart"
+    assert counts.dtype == torch.int32 and counts.shape == (q.shape[0],) and counts.is_contiguous()
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == q.shape[0] and rows.is_contiguous()
+    if q.shape[2] != frames.shape[2]:
+        raise RuntimeError("frame_segment: q is %d wide, the frames %d" % (q.shape[2], frames.shape[2]))
+    _moment_table("frame_segment", d, wnorm, normalize)
+    d.Nl, d.C, d.K = Nl, rows.shape[1], K
+    d.switch_penalty, d.background = float(switch_penalty), float("-inf") if background is None else float(background)
+    d.q, d.ldq, d.counts, d.rows = _p(q), ldq, _p(counts), _p(rows)
+    label = torch.empty(d.Nl, d.C, d.F, dtype=torch.int32, device=q.device)
+    score = torch.empty(d.Nl, d.C, d.F, dtype=torch.float32, device=q.device)
+    total = torch.empty(d.Nl, d.C, dtype=torch.float32, device=q.device)
+    nseg = torch.empty(d.Nl, d.C, dtype=torch.int32, device=q.device)
+    d.label, d.score, d.total, d.nseg = _p(label), _p(score), _p(total), _p(nseg)
+    _lib.check(_lib.lib().univl_frame_segment(_BYREF(d), _stream()), "frame_segment")
+    return label, score, total, nseg
 
 
 class AdamTables:

@@ -19,7 +19,10 @@ univl_moment_localize) and returns the best one -- or, with n_best=, the n best 
 (univl_moment_nbest); search_moments() does that for the best videos of a search and ranks the moments.
 
 Step alignment says where every step of an ORDERED list of texts happens: align_steps() places all of them at once, in order and
-without overlap, by the same window score (univl_step_align) -- action step localisation."""
+without overlap, by the same window score (univl_step_align) -- action step localisation.
+
+Segmentation asks from the video's side: segment() gives every frame of a video one of a SET of label texts or the background, by the
+one-frame window score and a penalty per change of label (univl_frame_segment) -- action segmentation, in its zero-shot form."""
 import ctypes
 import math
 import numbers
@@ -255,14 +258,48 @@ class VideoIndex:
         wnorm = self._window_norms() if self.normalize else None
         return ops.step_align(q, counts, self._frames[:self._n], self._fmask[:self._n], rows, lmin, lmax, wnorm=wnorm, normalize=self.normalize)
 
-    def _check_lists(self, who, lists, window):
-        """(Nl, K, lmin, lmax) for a [Nl, K, .] tensor of step lists, after every refusal that needs no device work."""
+    def _check_lists(self, who, lists, window, kmax=_lib.STEP_K_MAX):
+        """(Nl, K, lmin, lmax) for a [Nl, K, .] tensor of step lists (or label sets of at most kmax), after every refusal that needs no
+        device work."""
         lmin, lmax = self._check_window(who, window)
         if lists.dim() != 3:
             raise ValueError("VideoIndex.%s: step lists are [lists, steps, .] tensors, got %d dimensions" % (who, lists.dim()))
-        if not 1 <= lists.shape[1] <= _lib.STEP_K_MAX:
-            raise ValueError("VideoIndex.%s: lists of %d steps, need 1 .. %d" % (who, lists.shape[1], _lib.STEP_K_MAX))
+        if not 1 <= lists.shape[1] <= kmax:
+            raise ValueError("VideoIndex.%s: lists of %d steps, need 1 .. %d" % (who, lists.shape[1], kmax))
         return lists.shape[0], lists.shape[1], lmin, lmax
+
+    # ------------------------------------------------------------------------------------------ frame-wise segmentation
+    @torch.no_grad()
+    def segment(self, input_ids, token_type_ids, attention_mask, counts, rows, switch_penalty=0.0, background=None):
+        """Which of a SET of texts, if any, every frame of gallery row rows[i, c] shows (action segmentation).  The text tensors are
+        [Nl, K, W]: set i's labels are its first counts[i] texts, the others padding (encoded like any text, their vectors never read);
+        K <= SEGMENT_K_MAX.  rows: [Nl, C] gallery rows.  A frame scores for a label what localize() scores that one-frame window;
+        background: the score of "none of these" on every frame (None: no such label); switch_penalty >= 0 is paid at every change of
+        label between neighbouring valid frames -- 0 is the arg-max of every frame by itself, a large one gives the video one label.
+        Returns (label [Nl, C, F] int32: k, -1 background, -2 on a masked frame; score [Nl, C, F]: the chosen label's frame score; total
+        [Nl, C]: the objective; nseg [Nl, C]: the runs of equal non-background labels) on the device (include/univl_hip.h:
+        univl_frame_segment); a -1 row, a count outside [1, K] or a video without a valid frame is -2 / -inf throughout with total -inf
+        and nseg 0.  Labels need no order and may repeat or be absent.  Needs keep_frames=True."""
+        Nl, K = self._check_sets("segment", input_ids, switch_penalty, background)
+        flat = (t.reshape(Nl * K, -1) for t in (input_ids, token_type_ids, attention_mask))
+        return self.segment_vectors(self.pool_text(*flat)[0].view(Nl, K, H), counts, rows, switch_penalty, background)
+
+    @torch.no_grad()
+    def segment_vectors(self, q, counts, rows, switch_penalty=0.0, background=None):
+        """segment() for pooled label vectors the caller already holds ([Nl, K, 768] fp32 on the index's device)."""
+        Nl, K = self._check_sets("segment_vectors", q, switch_penalty, background)
+        q = _query_rows(q).view(Nl, K, H)
+        counts = torch.as_tensor(counts).to(device=q.device, dtype=torch.int32).reshape(Nl).contiguous()
+        rows = torch.as_tensor(rows).to(device=q.device, dtype=torch.int32).reshape(Nl, -1).contiguous()
+        wnorm = self._window_norms() if self.normalize else None
+        return ops.frame_segment(q, counts, self._frames[:self._n], self._fmask[:self._n], rows, switch_penalty, background, wnorm=wnorm,
+                                 normalize=self.normalize)
+
+    def _check_sets(self, who, sets, switch_penalty, background):
+        """(Nl, K) for a [Nl, K, .] tensor of label sets, after every refusal that needs no device work."""
+        Nl, K, _, _ = self._check_lists(who, sets, (1, 1), _lib.SEGMENT_K_MAX)
+        check_segment_args("VideoIndex.%s" % who, switch_penalty, background)
+        return Nl, K
 
     @torch.no_grad()
     def search_moments(self, input_ids, token_type_ids, attention_mask, k=10, window=(1, 1), shortlist=None, bank=None, per_video=1, nms=_NMS):
@@ -455,6 +492,18 @@ def check_nbest(who, n_best, nms, name="n_best"):
     if isinstance(n_best, bool) or not isinstance(n_best, numbers.Integral) or not 1 <= n_best <= _lib.MOMENT_NBEST_MAX:
         raise ValueError("%s: %s=%r, need an integer in [1, %d]" % (who, name, n_best, _lib.MOMENT_NBEST_MAX))
     check_nms(who, nms)
+
+
+def check_segment_args(who, switch_penalty, background):
+    """The ValueErrors of (switch_penalty=, background=) of a segmentation, before any device work; both travel as fp32."""
+    real = lambda x: isinstance(x, numbers.Real) and not isinstance(x, bool)
+    p32 = ctypes.c_float(switch_penalty).value if real(switch_penalty) else math.nan
+    if not (math.isfinite(p32) and p32 >= 0):
+        raise ValueError("%s: switch_penalty=%r, need a finite fp32 number >= 0" % (who, switch_penalty))
+    if background is not None:
+        b32 = ctypes.c_float(background).value if real(background) else math.nan
+        if math.isnan(b32) or b32 == math.inf:
+            raise ValueError("%s: background=%r, need a number below +inf in fp32 or -inf (None: no background label)" % (who, background))
 
 
 def check_bank_args(beta, hub_k):
