@@ -1061,6 +1061,58 @@ typedef struct UnivlFrameSegment {
 } UnivlFrameSegment;
 int univl_frame_segment_sizeof(void);
 int univl_frame_segment(const UnivlFrameSegment* d, hipStream_t stream);
+/* ---------------------------------------------------------------------------------------- video-to-video alignment
+ * A monotone alignment of the frames of TWO gallery rows (csrc/valign.hip): lay an annotated exemplar over another video of the
+ * same task and carry its frame labels across (local = 0), or find the segment two videos share (local = 1).  The four entries
+ * above ask a text about a video; this one needs no text at all.  The gallery side -- frames, ld_row, mask, N, F, H -- is
+ * UnivlMoment's; no norm table is read.
+ * THE SCORE IS ALWAYS THE COSINE OF TWO FRAMES, whatever the model's use_mil says: the model defines no video-video score, so there
+ * is no normalize switch here.
+ * For pair (a, b) = (ref[p], rows[p, c]) let f_0 < .. < f_{Ta-1} be the frames of a with mask != 0 and g_0 < .. < g_{Tb-1} those of
+ * b; a hole in a mask is simply skipped.  Every index written is a FRAME index (f_i, g_j), never a position.
+ *   e(i, j)     G(i, j) / (max(na_i, 1e-12f) * max(nb_j, 1e-12f)) - tau, where G(i, j) is the fp32 fmaf chain over k = 0 .. 767,
+ *               ascending from 0, of x_{f_i}[k] * y_{g_j}[k], and na_i, nb_j are sqrtf of the same chain over x * x.  These bits are
+ *               the contract whatever computes them (here the exact f32 MFMA, whose result is that chain), so e_ab(i, j) ==
+ *               e_ba(j, i) and no value depends on the pair's place in the launch, its company, C or deterministic mode
+ *   programme   additions and comparisons only.  The predecessors of (i, j) are taken in the order diagonal (i-1, j-1), up (i-1, j),
+ *               left (i, j-1); Pm is the largest H among those that exist, among equals the first in that order.
+ *                 local = 0   H(0, 0) = e(0, 0), otherwise H(i, j) = e(i, j) + Pm; the end cell is (Ta-1, Tb-1); the path walks the
+ *                             recorded predecessors back to (0, 0).  With tau = 1 this is classic DTW under the cosine distance
+ *                 local = 1   a cell with no predecessor, or with Pm <= 0, starts a path: H = e; otherwise H = e + Pm; the end cell
+ *                             is the largest H, then the lowest i, then the lowest j; the path walks back to its starting cell
+ *                             (Smith-Waterman without gaps scored apart; tau is what makes a poor cell negative)
+ *   outputs     all written for every pair.  score [P, C]: H at the end cell; path_len [P, C]; path_a, path_b [P, C, 2 F] int32: the
+ *               path's cells first to last as frame indices, -1 past path_len (a path holds at most Ta + Tb - 1 < 2 F cells);
+ *               match [P, C, F] int32: for frame g of b the a frame of the path cell in its column with the largest e, the lowest i
+ *               among equals; -1 for a valid frame the path does not visit (only with local), -2 for a masked frame; match_score
+ *               [P, C, F]: that cell's e, -inf where match < 0
+ *   nothing to align   ref[p] or rows[p, c] outside [0, N), or either video without a valid frame: score -inf, path_len 0, paths
+ *               -1, match -2 and match_score -inf on ALL F frames.  A row out of range is decided for the whole workgroup before
+ *               anything of the gallery is read
+ * One workgroup of 256 threads per pair; dynamic LDS: the 128 x 128 table of e at a pitch of 136 floats (69 632 B; the K slabs of the
+ * Gram phase overlay it), 7 KB static.  One launch, no workspace, no host read, no atomics, capturable.
+ * Range: UnivlMoment's for the gallery side; P >= 1, C >= 1, P * C * 2 F < 2^31, tau finite, local 0 or 1; otherwise, or for a NULL
+ * pointer, UNIVL_EINVAL; rows of frames 16-byte aligned (UNIVL_EALIGN); all before any launch.  Behaviour on NaN or infinite values
+ * in the frames: unspecified (no access leaves the buffers). */
+typedef struct UnivlVideoAlign {
+    const float* frames; int64_t ld_row; /* [N, F, 768] fp32 frames of the gallery rows, ld_row floats between rows               */
+    const int64_t* mask;                 /* [N, F] int64, contiguous: 0 = not a frame                                             */
+    int32_t N, F, H;                     /* H must be 768                                                                         */
+    int32_t local;                       /* 0: end to end; 1: the best common segment                                             */
+    const int32_t* ref;                  /* [P] exemplar gallery rows                                                             */
+    const int32_t* rows;                 /* [P, C] candidate gallery rows                                                         */
+    int32_t P, C;
+    float tau;                           /* subtracted from every cosine                                                          */
+    int32_t reserved;
+    float* score;                        /* [P, C] written                                                                        */
+    int32_t* path_len;                   /* [P, C] written                                                                        */
+    int32_t* path_a;                     /* [P, C, 2 F] written                                                                   */
+    int32_t* path_b;                     /* [P, C, 2 F] written                                                                   */
+    int32_t* match;                      /* [P, C, F] written                                                                     */
+    float* match_score;                  /* [P, C, F] written                                                                     */
+} UnivlVideoAlign;
+int univl_video_align_sizeof(void);
+int univl_video_align(const UnivlVideoAlign* d, hipStream_t stream);
 /* out[seg[e]] = sum(partials[start[e] .. start[e] + count[e])) for e < n: folds the per-wave partial sums written by the
  * weight-gradient GEMMs (UnivlGemm.sumsq) into the per-tensor sums of squares */
 int univl_sumsq_finish(const float* partials, const int32_t* seg, const int32_t* start, const int32_t* count, int32_t n,

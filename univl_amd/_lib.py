@@ -137,6 +137,14 @@ class FrameSegment(C.Structure):
                                       ("total", vp), ("nseg", vp)]
 
 
+class VideoAlign(C.Structure):
+    """include/univl_hip.h: UnivlVideoAlign -- the gallery side without a norm table, then the pairs, tau and the mode.  Not in
+    _STRUCTS: the library states its size through univl_video_align_sizeof (checked in lib())."""
+    _fields_ = [("frames", vp), ("ld_row", i64), ("mask", vp), ("N", i32), ("F", i32), ("H", i32), ("local", i32), ("ref", vp), ("rows", vp),
+                ("P", i32), ("C", i32), ("tau", f32), ("reserved", i32), ("score", vp), ("path_len", vp), ("path_a", vp), ("path_b", vp),
+                ("match", vp), ("match_score", vp)]
+
+
 class VocabScore(C.Structure):
     _fields_ = [("dtype", i32), ("rows", i32), ("V", i32), ("K", i32), ("x", vp), ("ldx", i64), ("table", vp), ("ldt", i64), ("bias", vp),
                 ("labels", vp), ("ignore_index", i32), ("slots", i32), ("seq_len", i32), ("reserved", i32), ("partial", vp),
@@ -232,7 +240,7 @@ def lib():
                  "univl_sample_step", "univl_caption_overlap", "univl_ngram_df", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd",
                  "univl_decode_constrain", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "univl_beam_group_step",
                  "univl_beam_pool_step", "univl_sim_colstat", "univl_sim_topk_norm", "univl_window_norms", "univl_moment_localize",
-                 "univl_moment_nbest", "univl_step_align", "univl_frame_segment"):
+                 "univl_moment_nbest", "univl_step_align", "univl_frame_segment", "univl_video_align"):
         getattr(L, name).argtypes = [vp, vp]
         getattr(L, name).restype = i32
     for name, st in (("univl_caption_overlap_sizeof", CaptionOverlap), ("univl_ngram_df_sizeof", NgramDf),
@@ -241,7 +249,7 @@ def lib():
                      ("univl_beam_pool_step_sizeof", BeamPoolStep), ("univl_sim_colstat_sizeof", SimColstat),
                      ("univl_sim_topk_norm_sizeof", SimTopkNorm), ("univl_moment_sizeof", Moment),
                      ("univl_moment_nbest_sizeof", MomentNbest), ("univl_step_align_sizeof", StepAlign),
-                     ("univl_frame_segment_sizeof", FrameSegment)):
+                     ("univl_frame_segment_sizeof", FrameSegment), ("univl_video_align_sizeof", VideoAlign)):
         f = getattr(L, name)
         f.argtypes, f.restype = [], i32
         if f() != C.sizeof(st):
@@ -348,7 +356,7 @@ EXPORTED = ["univl_last_error", "univl_version", "univl_struct_size", "univl_abi
             "univl_layernorm_fwd", "univl_layernorm_bwd", "univl_attention_fwd", "univl_attention_bwd", "univl_attention_bwd_fused", "univl_attention_fwd_fused",
             "univl_embed_text_fwd", "univl_embed_text_bwd", "univl_embed_scatter", "univl_rows_gather_sum", "univl_rows_zero", "univl_rows_append",
             "univl_rows_sumsq", "univl_zero_many", "univl_copy_many", "univl_pool_fwd", "univl_pool_bwd", "univl_pool_pair_fwd", "univl_pool_pair_bwd",
-            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_sim_colstat_sizeof", "univl_sim_colstat", "univl_sim_colstat_workspace", "univl_sim_topk_norm_sizeof", "univl_sim_topk_norm", "univl_hub_flags", "univl_hub_gate", "univl_moment_sizeof", "univl_window_norms", "univl_moment_localize", "univl_moment_nbest_sizeof", "univl_moment_nbest", "univl_step_align_sizeof", "univl_step_align", "univl_frame_segment_sizeof", "univl_frame_segment", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_group_step_sizeof", "univl_beam_group_step", "univl_beam_pool_step_sizeof", "univl_beam_pool_step", "univl_beam_pool_finish", "univl_sample_step", "univl_decode_constrain_sizeof", "univl_decode_constrain", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
+            "univl_maxmargin_loss", "univl_crossen_loss", "univl_milnce_loss", "univl_rank_counts", "univl_sim_topk", "univl_sim_topk_workspace", "univl_sim_colstat_sizeof", "univl_sim_colstat", "univl_sim_colstat_workspace", "univl_sim_topk_norm_sizeof", "univl_sim_topk_norm", "univl_hub_flags", "univl_hub_gate", "univl_moment_sizeof", "univl_window_norms", "univl_moment_localize", "univl_moment_nbest_sizeof", "univl_moment_nbest", "univl_step_align_sizeof", "univl_step_align", "univl_frame_segment_sizeof", "univl_frame_segment", "univl_video_align_sizeof", "univl_video_align", "univl_gather_rows", "univl_log_softmax_rows", "univl_beam_step", "univl_beam_group_step_sizeof", "univl_beam_group_step", "univl_beam_pool_step_sizeof", "univl_beam_pool_step", "univl_beam_pool_finish", "univl_sample_step", "univl_decode_constrain_sizeof", "univl_decode_constrain", "univl_caption_overlap_sizeof", "univl_caption_overlap", "univl_ngram_df_sizeof", "univl_ngram_df_tile", "univl_ngram_df_ws_bytes", "univl_ngram_df", "univl_consensus_pick", "univl_caption_advantage", "univl_beam_backtrack", "univl_beam_captions", "univl_scale_by_device_scalar", "univl_pair_concat_fwd", "univl_pair_concat_bwd", "univl_postype_fwd", "univl_postype_bwd", "univl_tanh_fwd",
             "univl_tanh_bwd", "univl_gelu_bwd", "univl_colsum", "univl_scale_ct_by_device_scalar", "univl_simdense_fwd", "univl_simdense_bwd", "univl_ce_loss", "univl_vocab_ce_fwd", "univl_vocab_ce_bwd", "univl_vocab_ce_weighted_sizeof", "univl_vocab_ce_weighted_fwd", "univl_vocab_ce_weighted_bwd", "univl_vocab_ce_smooth_sizeof", "univl_vocab_ce_smooth_fwd", "univl_vocab_ce_smooth_bwd", "univl_vocab_score", "univl_mfm_nce_loss", "univl_grad_sumsq", "univl_sumsq_finish",
             "univl_clip_coef", "univl_scale_grads", "univl_bert_adam", "univl_bert_adam_range", "univl_cast_bf16", "univl_cast_bf16_pair", "univl_cast_f32", "univl_bump_counter", "univl_probe_layouts", "univl_stamp"]
 

@@ -19,7 +19,8 @@ Localisation: eval_localization scores where in its own video every text is foun
 segments: mIoU and R1@0.3 / 0.5 / 0.7 over frame indices, and with n_best = n the R{n}@ columns over the n windows that temporal
 non-maximum suppression leaves.  eval_step_alignment does it for ORDERED lists of steps laid over their video
 jointly (retrieval.VideoIndex.align_steps): step recall by the centre frame of every step's window, and mIoU.  eval_segmentation
-labels every frame of a video out of a set of label texts (retrieval.VideoIndex.segment) and counts COIN's frame accuracy."""
+labels every frame of a video out of a set of label texts (retrieval.VideoIndex.segment) and counts COIN's frame accuracy;
+eval_label_transfer counts the same for labels carried over from an annotated exemplar video (retrieval.VideoIndex.align_videos)."""
 import contextlib
 import math
 import os
@@ -291,10 +292,7 @@ def eval_segmentation(model, index, label_batches, targets, gt_labels, switch_pe
     if row != n:
         raise ValueError("eval_segmentation: %d lists for %d targets" % (row, n))
     lab = torch.cat(labels)                                               # [n, F]; -2 on a masked frame
-    counted = (gt != -2) & (lab != -2)
-    right = counted & (lab == gt)
-    fg = counted & (gt >= 0)
-    per_list = [t.to(torch.int32).sum(1, dtype=torch.int32) for t in (right, counted, right & fg, fg)]
+    per_list = list(frame_label_counts(lab, gt))
     host = torch.stack(per_list + [torch.cat(nsegs), torch.isinf(torch.cat(totals)).to(torch.int32)]).cpu().numpy().astype(np.int64)
     correct, annotated, correct_fg, annotated_fg, nseg, empty = host                                                 # the one host read
     n_frames, n_fg = int(annotated.sum()), int(annotated_fg.sum())
@@ -303,6 +301,45 @@ def eval_segmentation(model, index, label_batches, targets, gt_labels, switch_pe
     return {"frame_accuracy": float(correct.sum()) / n_frames, "frame_accuracy_fg": float(correct_fg.sum()) / n_fg if n_fg else float("nan"),
             "correct": correct, "annotated": annotated, "n_lists": n, "n_frames": n_frames, "n_segments": int(nseg.sum()),
             "n_empty": int(empty.sum())}
+
+
+def frame_label_counts(pred, gt):
+    """The counters of eval_segmentation and eval_label_transfer for labels pred [.., F] (-1 background or not on the path, -2 a masked frame) against annotations
+    gt of the same shape (-2: not annotated): per-pair (correct, annotated, correct_fg, annotated_fg) as one [4, P, C] int32 device
+    tensor.  A frame counts if it is annotated and not masked; every decision is an integer comparison."""
+    counted = (gt != -2) & (pred != -2)
+    right = counted & (pred == gt)
+    fg = counted & (gt >= 0)
+    return torch.stack([t.to(torch.int32).sum(-1, dtype=torch.int32) for t in (right, counted, right & fg, fg)])
+
+
+def eval_label_transfer(index, ref, ref_labels, rows, gt_labels, tau=1.0):
+    """One-shot label transfer: the frame labels of annotated exemplar videos are carried to other videos of the same task along a
+    global alignment (VideoIndex.align_videos with local=False, then transfer_labels) and compared with those videos' annotations frame
+    by frame -- eval_segmentation's counters and conventions.  index: a retrieval.VideoIndex(keep_frames=True); ref [P]: the exemplars'
+    gallery rows; ref_labels [P, F] integers >= -1: their frame labels (-1 the background); rows [P, C]: the videos labelled from each;
+    gt_labels [P, C, F]: their annotations, k, -1 for the background, -2 for a frame that is not annotated and is never counted; a
+    frame the video's mask excludes is not counted either.  Returns, from one host read,
+      "frame_accuracy"      correct / annotated over all annotated valid frames
+      "frame_accuracy_fg"   the same over the frames annotated with a label, not the background (NaN without one)
+      "correct", "annotated"   int64 arrays [P, C]: per pair
+      "n_pairs", "n_frames" (annotated valid frames), "n_empty" (pairs with nothing to align)."""
+    result = index.align_videos(ref, rows, tau, False)
+    P, C, F = result.match.shape
+    dev = result.match.device
+    gt = torch.as_tensor(gt_labels).to(device=dev, dtype=torch.int32)
+    if gt.shape != (P, C, F):
+        raise ValueError("eval_label_transfer: gt_labels %s for %d exemplars, %d candidates each, %d frames" % (tuple(gt.shape), P, C, F))
+    pred = index.transfer_labels(ref_labels, result)
+    counts = frame_label_counts(pred, gt)
+    empty = (result.path_len == 0).to(torch.int32).unsqueeze(0)
+    host = torch.cat([counts, empty]).cpu().numpy().astype(np.int64)                                                 # the one host read
+    correct, annotated, correct_fg, annotated_fg, empty = host
+    n_frames, n_fg = int(annotated.sum()), int(annotated_fg.sum())
+    if n_frames == 0:
+        raise ValueError("eval_label_transfer: no annotated valid frame")
+    return {"frame_accuracy": float(correct.sum()) / n_frames, "frame_accuracy_fg": float(correct_fg.sum()) / n_fg if n_fg else float("nan"),
+            "correct": correct, "annotated": annotated, "n_pairs": P * C, "n_frames": n_frames, "n_empty": int(empty.sum())}
 
 
 def ids_to_caption(tokenizer, ids):

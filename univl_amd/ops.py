@@ -939,6 +939,39 @@ def frame_segment(q, counts, frames, mask, rows, switch_penalty, background=None
     return label, score, total, nseg
 
 
+def video_align(frames, mask, ref, rows, tau, local=False):
+    """A monotone alignment of the valid frames of gallery row ref[p] (the exemplar) and gallery row rows[p, c], for every p and c in
+    one launch (include/univl_hip.h: univl_video_align).  frames, mask: as window_norms'; ref: [P] int32; rows: [P, C] int32
+    contiguous; tau: finite, subtracted from every cosine; local: False lays the whole of one video over the whole of the other (with
+    tau = 1 classic DTW under the cosine distance), True finds the best common segment.  The cell score is ALWAYS the cosine of the two
+    frames minus tau -- the model defines no video-video score, so there is no normalize switch and no norm table.  Returns (score
+    [P, C] fp32, path_len [P, C] int32, path_a, path_b [P, C, 2 F] int32: the path's cells first to last as frame indices, -1 past
+    path_len; match [P, C, F] int32: for every frame of the candidate the exemplar frame it is matched with, -1 a valid frame the path
+    does not visit, -2 a masked frame; match_score [P, C, F] fp32: that cell's score, -inf where match < 0).  A row id outside the
+    gallery or a video without a valid frame gives (-inf, 0, -1, -1, -2, -inf) throughout."""
+    d = _lib.VideoAlign()
+    _require_gpu(frames, mask, ref, rows)
+    assert frames.dtype == torch.float32 and frames.dim() == 3 and frames.stride(2) == 1 and frames.stride(1) == frames.shape[2]
+    assert mask.dtype == torch.int64 and mask.shape == frames.shape[:2] and mask.is_contiguous()
+    assert ref.dtype == torch.int32 and ref.dim() == 1 and ref.is_contiguous()
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[0] == ref.shape[0] and rows.is_contiguous()
+    d.N, d.F, d.H = frames.shape
+    d.frames, d.ld_row, d.mask = _p(frames), frames.stride(0) if d.N > 1 else d.F * d.H, _p(mask)     # one row: its stride means nothing
+    d.P, d.C = rows.shape
+    d.tau, d.local = float(tau), int(local)
+    d.ref, d.rows = _p(ref), _p(rows)
+    dev = frames.device
+    score = torch.empty(d.P, d.C, dtype=torch.float32, device=dev)
+    path_len = torch.empty(d.P, d.C, dtype=torch.int32, device=dev)
+    path_a = torch.empty(d.P, d.C, 2 * d.F, dtype=torch.int32, device=dev)
+    path_b = torch.empty(d.P, d.C, 2 * d.F, dtype=torch.int32, device=dev)
+    match = torch.empty(d.P, d.C, d.F, dtype=torch.int32, device=dev)
+    match_score = torch.empty(d.P, d.C, d.F, dtype=torch.float32, device=dev)
+    d.score, d.path_len, d.path_a, d.path_b, d.match, d.match_score = (_p(t) for t in (score, path_len, path_a, path_b, match, match_score))
+    _lib.check(_lib.lib().univl_video_align(_BYREF(d), _stream()), "video_align")
+    return score, path_len, path_a, path_b, match, match_score
+
+
 class AdamTables:
     """Device copies of a UnivlSeg[] and a chunk table (adam_tables); keeps the tensors alive for the descriptors that point at them."""
 

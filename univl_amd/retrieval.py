@@ -22,7 +22,11 @@ Step alignment says where every step of an ORDERED list of texts happens: align_
 without overlap, by the same window score (univl_step_align) -- action step localisation.
 
 Segmentation asks from the video's side: segment() gives every frame of a video one of a SET of label texts or the background, by the
-one-frame window score and a penalty per change of label (univl_frame_segment) -- action segmentation, in its zero-shot form."""
+one-frame window score and a penalty per change of label (univl_frame_segment) -- action segmentation, in its zero-shot form.
+
+Video alignment needs no text: align_videos() lays the frames of one gallery video over those of another, monotonically
+(univl_video_align: DTW, or with local=True the best common segment), and transfer_labels() carries an exemplar's frame labels across."""
+import collections
 import ctypes
 import math
 import numbers
@@ -33,6 +37,14 @@ from . import _lib, ops
 
 H = 768
 _NMS = (1, 2)              # the default suppression threshold of n-best localisation: temporal IoU above 1 / 2 (check_nbest knows it by identity)
+
+
+class _DefaultTau(float):
+    """align_videos' default tau, told from a 1.0 the caller wrote by identity: local=True accepts no default."""
+
+
+_TAU_DTW = _DefaultTau(1.0)
+VideoAlignment = collections.namedtuple("VideoAlignment", "score path_len path_a path_b match match_score")
 
 
 class VideoIndex:
@@ -301,6 +313,45 @@ class VideoIndex:
         check_segment_args("VideoIndex.%s" % who, switch_penalty, background)
         return Nl, K
 
+    # ------------------------------------------------------------------------------------------ video-to-video alignment
+    @torch.no_grad()
+    def align_videos(self, ref, rows, tau=_TAU_DTW, local=False):
+        """A monotone alignment of the valid frames of gallery row ref[p] (the exemplar) with those of every gallery row rows[p, c].
+        ref: [P] gallery rows; rows: [P, C] (or [P]: one candidate each).  The score of a pair of frames is their cosine minus tau --
+        ALWAYS the cosine, also for a use_mil model: the model defines no video-video score.  local=False: the best path from the first
+        valid frames of both to the last ones (tau = 1: classic DTW under the cosine distance).  local=True: the best-scoring common
+        segment, free at both ends; tau is then what separates a match from a mismatch and MUST be given -- no default is invented
+        for it.  Returns a VideoAlignment (score [P, C], path_len [P, C], path_a, path_b [P, C, 2 F]: the path's cells first to last as
+        frame indices, -1 past path_len; match [P, C, F]: the exemplar frame every candidate frame is matched with, -1 not on the path,
+        -2 masked; match_score [P, C, F]) on the device (include/univl_hip.h: univl_video_align); a -1 row or a video without a valid
+        frame is (-inf, 0, -1, -1, -2, -inf) throughout.  Needs keep_frames=True."""
+        check_valign_args("VideoIndex.align_videos", tau, local, tau is not _TAU_DTW)
+        if not self.keep_frames or self._frames is None:
+            raise ValueError("VideoIndex.align_videos needs an index built with keep_frames=True, with videos in it")
+        ref = torch.as_tensor(ref)
+        rows = torch.as_tensor(rows)
+        if ref.dim() != 1 or ref.numel() == 0 or rows.dim() not in (1, 2) or rows.shape[0] != ref.shape[0] or rows.numel() == 0:
+            raise ValueError("VideoIndex.align_videos: ref %s and rows %s (need [pairs] and [pairs, candidates], neither empty)"
+                             % (tuple(ref.shape), tuple(rows.shape)))
+        dev = self._frames.device
+        ref = ref.to(device=dev, dtype=torch.int32).contiguous()
+        rows = rows.to(device=dev, dtype=torch.int32).reshape(ref.shape[0], -1).contiguous()
+        return VideoAlignment(*ops.video_align(self._frames[:self._n], self._fmask[:self._n], ref, rows, float(tau), bool(local)))
+
+    @torch.no_grad()
+    def transfer_labels(self, ref_labels, result):
+        """Carries frame labels of the exemplars across an alignment: ref_labels [P, F] integers, the labels of the frames of ref[p];
+        result: align_videos()'s.  Returns [P, C, F] int32: for every frame of every candidate the exemplar's label at match, where
+        match >= 0; match's own -1 (not on the path) or -2 (masked) elsewhere.  A device gather, no host read."""
+        match = result.match
+        labels = torch.as_tensor(ref_labels).to(device=match.device, dtype=torch.int32)
+        P, C, F = match.shape
+        if labels.shape != (P, F):
+            raise ValueError("VideoIndex.transfer_labels: ref_labels %s for an alignment of %d exemplars and %d frames"
+                             % (tuple(labels.shape), P, F))
+        got = torch.gather(labels.unsqueeze(1).expand(P, C, F), 2, match.clamp(min=0).to(torch.int64))
+        return torch.where(match >= 0, got, match)
+
     @torch.no_grad()
     def search_moments(self, input_ids, token_type_ids, attention_mask, k=10, window=(1, 1), shortlist=None, bank=None, per_video=1, nms=_NMS):
         """The k best (video, window) moments for every text.  The `shortlist` (default k, at most TOPK_MAX) best videos by WHOLE-VIDEO
@@ -492,6 +543,21 @@ def check_nbest(who, n_best, nms, name="n_best"):
     if isinstance(n_best, bool) or not isinstance(n_best, numbers.Integral) or not 1 <= n_best <= _lib.MOMENT_NBEST_MAX:
         raise ValueError("%s: %s=%r, need an integer in [1, %d]" % (who, name, n_best, _lib.MOMENT_NBEST_MAX))
     check_nms(who, nms)
+
+
+def check_valign_args(who, tau, local, tau_given=True):
+    """The ValueErrors of (tau=, local=) of a video alignment, before any device work; tau travels as fp32."""
+    if not (isinstance(local, numbers.Integral) and local in (0, 1)):
+        raise ValueError("%s: local=%r, need True or False" % (who, local))
+    if local and not tau_given:
+        raise ValueError("%s: local=True needs an explicit tau (the cosine below which two frames do not match)" % who)
+    real = isinstance(tau, numbers.Real) and not isinstance(tau, bool)
+    try:
+        t32 = ctypes.c_float(tau).value if real else math.nan
+    except OverflowError:
+        t32 = math.inf
+    if not math.isfinite(t32):
+        raise ValueError("%s: tau=%r, need a finite fp32 number" % (who, tau))
 
 
 def check_segment_args(who, switch_penalty, background):
